@@ -9,6 +9,10 @@ blocks already resident in HBM, i.e. one DAG level of the radix ops that BigUint
 (weak scaling; the path has no exchange step, so no data-path collective).
 
 Timed region: barrier + device sync, K steps, device sync + barrier; max over ranks.
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line.
+`--dump-outputs DIR` also writes what the last timed step computed (dump_outputs below).  Everything
+else is measured only with `--full`:
 roofline: the dominant kernel (blind rotate) timed live with HIP events on the engine's stream;
 algorithmic f64 flops per PBS = n * 2^18, peak = FP64 vector rate.
 cpu_baseline: the C oracle (same algorithm, same parameters) on host cores, rank 0, N=1 only.
@@ -53,20 +57,29 @@ def parse(argv=None):
     # product of the 8x8 limb products, profiles/r2/level_trace_r2c.txt), 42.7 rounds of the
     # throughput kernel's 768 resident workgroups
     ap.add_argument("--batch", type=int, default=32768, help="PBS per step per GPU")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample length")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel / roofline / latency-level timings, the host-buffer rate, "
+                         "the decryption spot check, the 256-bit op and sign legs, the fan-out legs (N > 1), the "
+                         "multi-bit parameter set, the CPU baseline and the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU-baseline sample length")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--detail", default=DETAIL_DEFAULT,
-                    help="side file for the per-run arrays, the multi-bit op legs and the CPU per-op replay")
+                    help="--full: side file for the per-run arrays, the multi-bit op legs and the CPU per-op replay")
     ap.add_argument("--seed", type=int, default=0xF11E51)
-    ap.add_argument("--no-ops", action="store_true", help="skip the 256-bit mul / sign wall-clock legs")
-    ap.add_argument("--no-multibit", action="store_true", help="skip the multi-bit (grouping 2) measurement")
+    ap.add_argument("--no-ops", action="store_true", help="--full: skip the 256-bit mul / sign wall-clock legs")
+    ap.add_argument("--no-multibit", action="store_true", help="--full: skip the multi-bit (grouping 2) measurement")
     ap.add_argument("--launch-deadline", type=float, default=LAUNCH_DEADLINE_S,
                     help="self-launched N > 1 runs: seconds before every rank is killed")
     # GPU-free rehearsal of the N > 1 control plane (the launcher test): every rank joins the gloo
     # group, times a barrier-bracketed sleep, takes the max over ranks, rank 0 prints the line
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------ launcher
@@ -499,10 +512,29 @@ def fanout_legs(ck, ctx, dist, rank, world, seed):
     return out
 
 
-def pbs_leg(a, kind, dist, rank, world, device):
+DUMP_ROWS = 2048   # ciphertexts of the last timed step kept by --dump-outputs (2048 x 2049 f64 = 33.6 MB)
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: the big-key LWE ciphertexts u64[B, 2049] that the last timed step left in the
+    caller's output buffer, as float64 (each torus word rounded to 53 bits): all B rows, or a fixed
+    seeded sample of DUMP_ROWS of them when B is larger, in `pbs_out.npy`; the rows' indices in
+    `pbs_out_rows.npy`.  Keys, inputs and sample depend only on the arguments, and the engine is
+    bit-reproducible, so two builds run with the same arguments can be compared file by file."""
+    B = out.shape[0]
+    rows = np.arange(B) if B <= DUMP_ROWS else np.sort(
+        np.random.default_rng(DUMP_SEED).choice(B, DUMP_ROWS, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "pbs_out.npy"), out[rows].astype(np.float64))
+    np.save(os.path.join(dirname, "pbs_out_rows.npy"), rows.astype(np.float64))
+
+
+def pbs_leg(a, kind, dist, rank, world, device, dump_dir=None):
     """one parameter set: keys, the timed batch of `a.batch` PBS per GPU (barrier + sync around exactly
-    a.steps steps, max over ranks), the live HIP-event kernel timing and a decryption spot check.
-    Returns (ck, ctx, result dict); the caller frees nothing (ctx.close() at exit)."""
+    a.steps steps, max over ranks); with a.full also the live HIP-event kernel timing, the latency
+    levels, the host-buffer rate and a decryption spot check.  `dump_dir`: dump_outputs of the last
+    timed step.  Returns (ck, ctx, result dict); the caller frees nothing (ctx.close() at exit)."""
     from fhe_sign import Context, default_params, generate_keys, multi_bit_params
 
     P = multi_bit_params() if kind == "multibit" else default_params()
@@ -539,22 +571,23 @@ def pbs_leg(a, kind, dist, rank, world, device):
 
     # before any throughput launch (cool chip) and again after the timed steps (clock under load):
     # both in the line, so a difference between them is the clock, measured in the same run
-    lat_before = latency_levels()
+    lat_before = latency_levels() if a.full else None
 
     for _ in range(a.warmup):
         ctx.pbs_device(d_in, B, d_lut, d_out)
     ctx.sync()
 
     # live per-kernel timing (HIP events on the engine stream) in separate untimed passes
-    ctx.enable_timing(True)
     ks_t, br_t = [], []
-    for _ in range(max(2, min(a.steps, 5))):
-        ctx.pbs_device(d_in, B, d_lut, d_out)
-        ks, br = ctx.last_pbs_timing()
-        ks_t.append(ks)
-        br_t.append(br)
-    ctx.enable_timing(False)
-    ctx.sync()
+    if a.full:
+        ctx.enable_timing(True)
+        for _ in range(max(2, min(a.steps, 5))):
+            ctx.pbs_device(d_in, B, d_lut, d_out)
+            ks, br = ctx.last_pbs_timing()
+            ks_t.append(ks)
+            br_t.append(br)
+        ctx.enable_timing(False)
+        ctx.sync()
 
     # shader clock over the timed steps: every workgroup of the blind rotate adds its lifetime in
     # s_memtime cycles and s_memrealtime 100 MHz ticks (fhe_ctx_enable_clock; two stamps per workgroup)
@@ -570,6 +603,34 @@ def pbs_leg(a, kind, dist, rank, world, device):
     dt = allmax(dist, dt)
     cycles, ticks, wgs = ctx.read_clock()
     ctx.enable_clock(False)
+
+    if dump_dir is not None:  # before anything else launches into d_out
+        last = np.zeros_like(cts)
+        ctx.d2h(last, d_out)
+        if rank == 0:
+            dump_outputs(dump_dir, last)
+        del last
+
+    res = {
+        "value": world * B * a.steps / dt,
+        "ms_per_step": dt / a.steps * 1e3,
+        "params": f"n={n},N=2048,k=1,pbs=2^23x1,ks=2^3x5,msg=4,carry=4,grouping={1 if kind == 'classic' else 2}",
+    }
+    if ticks and wgs:
+        ghz = cycles / ticks * 0.1  # s_memrealtime counts at 100 MHz
+        res["clock"] = {
+            "shader_ghz": ghz,
+            # clock-normalised cost (drift between boxes is clock): CU-cycles per bootstrap of the timed
+            # step (KS + BR + SE)
+            "cu_cycles_per_pbs": res["ms_per_step"] * 1e-3 * ghz * 1e9 * CUS / B,
+            "wg_cycles": cycles / wgs,  # one workgroup's lifetime (classic: two ciphertexts), shader cycles
+            "workgroups": wgs,
+            "source": "s_memtime / s_memrealtime of every blind-rotate workgroup over the timed steps",
+        }
+    if not a.full:
+        for d in (d_in, d_out, d_lut):
+            ctx.free(d)
+        return ck, ctx, res
 
     # host-buffer boundary (fhe_pbs_batch: H2D + KS/BR + D2H), reported beside `value`, never as it
     t0 = time.perf_counter()
@@ -602,10 +663,7 @@ def pbs_leg(a, kind, dist, rank, world, device):
     # per workgroup sharing it; multi-bit: one per workgroup): the bytes the blind rotate moves L2 -> CU
     # per launch, and their rate against the L2 peak
     l2_bytes = ((B + 1) // 2 if kind == "classic" else B) * bsk_bytes
-    res = {
-        "value": world * B * a.steps / dt,
-        "ms_per_step": dt / a.steps * 1e3,
-        "params": f"n={n},N=2048,k=1,pbs=2^23x1,ks=2^3x5,msg=4,carry=4,grouping={1 if kind == 'classic' else 2}",
+    res.update({
         "roofline": {
             "bound": "fp64_valu",
             "compute_pipe": "fp64 VALU (FFT butterflies; no dense contraction on the path)",
@@ -627,19 +685,9 @@ def pbs_leg(a, kind, dist, rank, world, device):
         },
         "pcie_inclusive_pbs_per_s": pcie_rate * world,  # per-rank host-buffer rate x ranks
         "latency_level_ms": lat,
-    }
-    if ticks and wgs:
-        ghz = cycles / ticks * 0.1  # s_memrealtime counts at 100 MHz
-        res["clock"] = {
-            "shader_ghz": ghz,
-            # clock-normalised cost (drift between boxes is clock): CU-cycles per bootstrap of the timed
-            # step (KS + BR + SE) and of the blind rotate alone (HIP-event kernel time)
-            "cu_cycles_per_pbs": res["ms_per_step"] * 1e-3 * ghz * 1e9 * CUS / B,
-            "br_cu_cycles_per_pbs": br_ms * 1e-3 * ghz * 1e9 * CUS / B,
-            "wg_cycles": cycles / wgs,  # one workgroup's lifetime (classic: two ciphertexts), shader cycles
-            "workgroups": wgs,
-            "source": "s_memtime / s_memrealtime of every blind-rotate workgroup over the timed steps",
-        }
+    })
+    if "clock" in res:  # the blind rotate alone (HIP-event kernel time), clock-normalised like cu_cycles_per_pbs
+        res["clock"]["br_cu_cycles_per_pbs"] = br_ms * 1e-3 * res["clock"]["shader_ghz"] * 1e9 * CUS / B
     return ck, ctx, res
 
 
@@ -670,21 +718,10 @@ MB_KEYS = (("biguint256_mul_seconds", "biguint256_mul_compat"), ("biguint256_mul
            ("div256_by_encrypted_seconds", "div256_by_encrypted"))
 
 
-def compose_line(a, world, cl, ops, mb, fan, cpu):
-    """(the one JSON line, the detail dict).  The line: the contract keys, compact roofline / clock /
-    multi-bit / fan-out / CPU-baseline summaries, every classic op's median seconds, then HEADLINE_KEYS
-    last (< LINE_MAX_BYTES; tests/test_bench_line.py).  The detail (side file, a.detail): the per-run
-    arrays, the reference-equivalent op/s, the README comparison, the multi-bit op legs and the CPU
-    per-op replay."""
+def line_head(a, world, cl):
+    """the contract keys of the JSON line: all that a plain run (no --full) prints, and the start of
+    compose_line's"""
     B = a.batch
-    traffic, traffic_src = pmc_traffic(B, (cl["roofline"]["kernel"],))
-    r = cl["roofline"]
-    roof = {k: r[k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "peak_measured", "frac_measured",
-                              "flops_per_pbs", "kernel_ms", "keyswitch_ms")}
-    roof["traffic"] = traffic
-    roof["traffic_source"] = traffic_src
-    roof["hbm"] = {k: r["hbm"][k] for k in ("achieved", "peak", "unit", "frac")}
-    roof["l2_to_cu"] = {k: r["l2"][k] for k in ("achieved", "peak", "unit", "frac")}
     res = {
         "metric": METRIC,
         "value": cl["value"],
@@ -705,10 +742,32 @@ def compose_line(a, world, cl, ops, mb, fan, cpu):
             "params": cl["params"],
             "parallelism": f"replicas x{world}",
         },
-        "roofline": roof,
     }
     if "clock" in cl:
         res["clock"] = {k: v for k, v in cl["clock"].items() if k != "source"}
+    return res
+
+
+def compose_line(a, world, cl, ops, mb, fan, cpu):
+    """(the one JSON line, the detail dict).  The line: the contract keys, compact roofline / clock /
+    multi-bit / fan-out / CPU-baseline summaries, every classic op's median seconds, then HEADLINE_KEYS
+    last (< LINE_MAX_BYTES; tests/test_bench_line.py).  The detail (side file, a.detail): the per-run
+    arrays, the reference-equivalent op/s, the README comparison, the multi-bit op legs and the CPU
+    per-op replay."""
+    B = a.batch
+    traffic, traffic_src = pmc_traffic(B, (cl["roofline"]["kernel"],))
+    r = cl["roofline"]
+    roof = {k: r[k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "peak_measured", "frac_measured",
+                              "flops_per_pbs", "kernel_ms", "keyswitch_ms")}
+    roof["traffic"] = traffic
+    roof["traffic_source"] = traffic_src
+    roof["hbm"] = {k: r["hbm"][k] for k in ("achieved", "peak", "unit", "frac")}
+    roof["l2_to_cu"] = {k: r["l2"][k] for k in ("achieved", "peak", "unit", "frac")}
+    res = line_head(a, world, cl)
+    clock = res.pop("clock", None)
+    res["roofline"] = roof
+    if clock is not None:
+        res["clock"] = clock
     res["pcie_inclusive_pbs_per_s"] = cl["pcie_inclusive_pbs_per_s"]
     detail = {"metric": METRIC, "roofline": r, "clock": cl.get("clock"), "latency_level_ms": cl["latency_level_ms"]}
     if mb is not None:
@@ -780,7 +839,14 @@ def main():
     B = a.batch
     # headline: the default (classic) parameters of configs[1]; the multi-bit blind rotation (same
     # client key, grouping 2) is measured beside it with the same protocol
-    ck, ctx, cl = pbs_leg(a, "classic", dist, rank, world, device)
+    ck, ctx, cl = pbs_leg(a, "classic", dist, rank, world, device, a.dump_outputs)
+    if not a.full:  # the plain run: the headline alone
+        if rank == 0:
+            print(json.dumps(_sig(line_head(a, world, cl)), separators=(",", ":")), file=out, flush=True)
+        ctx.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     ops, op_levels = (None, {}) if a.no_ops else ops_legs(ck, ctx, a.seed)
     if ops is not None and dist is not None:
         for k in ops:

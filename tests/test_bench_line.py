@@ -84,3 +84,43 @@ def test_line_short_with_headline_last(tmp_path, world):
     assert "multibit_ops" in detail and "vs_reference_readme" in detail
     assert "sign_fhe_with_k0_v0_callsite" in LEGS and "sign_fhe_with_k0_v0_callsite" in line["ops_s"]
     json.dumps(detail)
+
+
+def test_plain_line_is_the_head_of_the_full_line():
+    """without --full the line is line_head alone: the contract keys, built from the timed steps only
+    (no roofline, latency or host-buffer figure asked of the leg), with the values of the full line"""
+    a = bench.parse([])
+    assert not a.full and a.dump_outputs is None
+    full = _pbs_part("classic")
+    plain = {k: full[k] for k in ("value", "ms_per_step", "params", "clock")}
+    head = bench._sig(bench.line_head(a, 1, plain))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config"):
+        assert key in head
+    assert "roofline" not in head and "latency_level_ms" not in head
+    line, _ = bench.compose_line(a, 1, full, _ops(1.0), None, None, None)
+    for key in head:
+        assert line[key] == head[key], key
+    assert head["unit"] == "PBS/s" and head["dtype"] == "f64" and head["higher_is_better"] is True
+    assert head["steps"] == a.steps and head["ms_per_step"] == pytest.approx(236.46)
+
+
+def test_dump_outputs_is_a_fixed_sample_in_float64(tmp_path):
+    """--dump-outputs: every row of a small batch; of a large one the same seeded DUMP_ROWS rows on
+    every call, which at the engine's 2049-word ciphertexts stay under 64 MB"""
+    import numpy as np
+    assert bench.DUMP_ROWS * 2049 * 8 + bench.DUMP_ROWS * 8 <= 64 << 20
+    rng = np.random.default_rng(1)
+    small = rng.integers(0, 1 << 63, (48, 9), dtype=np.uint64)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    got = np.load(tmp_path / "s" / "pbs_out.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "s" / "pbs_out_rows.npy"), np.arange(48))
+    big = rng.integers(0, 1 << 63, (bench.DUMP_ROWS * 3 + 5, 3), dtype=np.uint64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    rows = np.load(tmp_path / "a" / "pbs_out_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == bench.DUMP_ROWS == len(set(rows.tolist()))
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "pbs_out_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "pbs_out.npy"), big[rows.astype(np.int64)].astype(np.float64))
+    assert sorted(os.listdir(tmp_path / "a")) == ["pbs_out.npy", "pbs_out_rows.npy"]

@@ -1,6 +1,6 @@
 #!/bin/bash
-# One GPU pass over the tree: the driver's GPU suite, smoke, and the default bench line (detail file and
-# logs under gpurun_out/, tagged $1).  Stops at the first step that faults, aborts or times out.
+# One GPU pass over the tree: the GPU suite, smoke, and the full bench line (logs tagged $1; the bench's
+# detail file at its default path).  Stops at the first step that faults, aborts or times out.
 set -u
 TAG=${1:-run}
 step() {  # name, timeout, command...
@@ -12,4 +12,4 @@ step() {  # name, timeout, command...
 }
 step gpu_tests 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests -m gpu
 step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"
-step bench 900 python -u bench.py --detail "gpurun_out/${TAG}_bench_detail.json"
+step bench 900 python -u bench.py --full
