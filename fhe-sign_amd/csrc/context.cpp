@@ -706,6 +706,138 @@ int fhe_pbs_batch_device(fhe_ctx* c, const uint64_t* d_in, size_t count, const u
     return c->pbs_device(d_in, count, d_lut, d_out);
 }
 
+namespace {
+// d_ms rows (stride ms_stride) -> host rows of n + 1 words, behind the keyswitch on the stream
+hipError_t copy_small(fhe_ctx* c, uint64_t* small, size_t count) {
+    const size_t row = ((size_t)c->p.n + 1) * 8;
+    return hipMemcpy2DAsync(small, row, c->d_ms, (size_t)c->ms_stride * 8, row, count, hipMemcpyDeviceToHost,
+                            c->stream);
+}
+struct DeviceFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+}  // namespace
+
+int fhe_keyswitch_batch(fhe_ctx* c, const uint64_t* in, size_t count, uint64_t* small) {
+    if (!c || (count && (!in || !small))) return FHE_ERR_INVALID;
+    if (!c->has_key) {
+        set_error("no server key installed (fhe_set_server_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    if (count == 0) return FHE_OK;
+    if (count > (size_t)0x7fffffff) {
+        set_error("batch too large");
+        return FHE_ERR_INVALID;
+    }
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    int rc = c->ensure_stage(count);
+    if (rc) return rc;
+    rc = c->ensure_ms(count);
+    if (rc) return rc;
+    FHE_HIP_CHECK(hipMemcpyAsync(c->d_stage_in, in, count * kBigCt * 8, hipMemcpyHostToDevice, c->stream));
+    FHE_HIP_CHECK(c->keyswitch(c->d_stage_in, nullptr, count));
+    FHE_HIP_CHECK(copy_small(c, small, count));
+    FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return FHE_OK;
+}
+
+int fhe_pbs_lincomb_batch(fhe_ctx* c, const uint64_t* blocks, size_t nblocks, const uint32_t* term_off,
+                          const uint32_t* term_src, const int64_t* term_coef, const uint64_t* cst,
+                          const uint32_t* lut_ids, size_t count, uint64_t* small, uint64_t* out) {
+    if (!c) return FHE_ERR_INVALID;
+    if (!c->has_key) {
+        set_error("no server key installed (fhe_set_server_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    if (count == 0) return FHE_OK;
+    if (!blocks || !nblocks || !term_off || !term_src || !term_coef || !cst || !lut_ids) {
+        set_error("null argument");
+        return FHE_ERR_INVALID;
+    }
+    if (count > (size_t)0x7fffffff || nblocks > (size_t)0x7fffffff) {
+        set_error("batch too large");
+        return FHE_ERR_INVALID;
+    }
+    // validate everything before anything is staged or launched
+    if (term_off[0] != 0) {
+        set_error("term_off must start at 0");
+        return FHE_ERR_INVALID;
+    }
+    size_t next = 0;  // terms of the wide items
+    for (size_t i = 0; i < count; ++i) {
+        if (term_off[i + 1] < term_off[i]) {
+            set_error("term_off must be non-decreasing");
+            return FHE_ERR_INVALID;
+        }
+        const uint32_t nt = term_off[i + 1] - term_off[i];
+        if (nt == 0 || nt > (uint32_t)kMaxWideTerms) {
+            set_error("an item needs 1 to 32 terms");
+            return FHE_ERR_INVALID;
+        }
+        for (uint32_t t = term_off[i]; t < term_off[i + 1]; ++t) {
+            if (term_src[t] >= nblocks) {
+                set_error("block index out of range");
+                return FHE_ERR_INVALID;
+            }
+            if (nt <= (uint32_t)kMaxTerms && (term_coef[t] < INT32_MIN || term_coef[t] > INT32_MAX)) {
+                set_error("coefficient of an inline item (at most 6 terms) outside int32");
+                return FHE_ERR_INVALID;
+            }
+        }
+        if (nt > (uint32_t)kMaxTerms) next += nt;
+        if (lut_ids[i] >= c->lut_ids.size()) {
+            set_error("unknown LUT id");
+            return FHE_ERR_INVALID;
+        }
+    }
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    int rc = c->ensure_stage(std::max(count, nblocks));
+    if (rc) return rc;
+    rc = c->ensure_ms(count);
+    if (rc) return rc;
+    rc = c->sync_luts();
+    if (rc) return rc;
+    // descriptors, then the wide items' term tables in PbsDesc-sized units (as Engine::flush stages them)
+    const size_t ndesc = count + (next * sizeof(TermExt) + sizeof(PbsDesc) - 1) / sizeof(PbsDesc);
+    PbsDesc* dev = nullptr;
+    FHE_HIP_CHECK(hipMalloc(&dev, ndesc * sizeof(PbsDesc)));
+    std::unique_ptr<void, DeviceFree> dev_guard(dev);
+    std::vector<PbsDesc> h(ndesc);
+    std::memset(h.data(), 0, ndesc * sizeof(PbsDesc));
+    TermExt* h_ext = reinterpret_cast<TermExt*>(h.data() + count);
+    const TermExt* d_ext = reinterpret_cast<const TermExt*>(dev + count);
+    size_t eo = 0;
+    for (size_t i = 0; i < count; ++i) {
+        PbsDesc& d = h[i];
+        const uint32_t t0 = term_off[i], nt = term_off[i + 1] - t0;
+        if (nt <= (uint32_t)kMaxTerms) {
+            for (uint32_t u = 0; u < nt; ++u) {
+                d.src[u] = c->d_stage_in + (size_t)term_src[t0 + u] * kBigCt;
+                d.coef[u] = (int32_t)term_coef[t0 + u];
+            }
+        } else {
+            for (uint32_t u = 0; u < nt; ++u)
+                h_ext[eo + u] = TermExt{c->d_stage_in + (size_t)term_src[t0 + u] * kBigCt, term_coef[t0 + u]};
+            d.src[0] = reinterpret_cast<const uint64_t*>(d_ext + eo);
+            eo += nt;
+        }
+        d.nterms = nt;
+        d.lut = lut_ids[i];
+        d.cst = cst[i];
+        d.dst = c->d_stage_out + i * kBigCt;
+    }
+    FHE_HIP_CHECK(hipMemcpyAsync(c->d_stage_in, blocks, nblocks * kBigCt * 8, hipMemcpyHostToDevice, c->stream));
+    FHE_HIP_CHECK(hipMemcpyAsync(dev, h.data(), ndesc * sizeof(PbsDesc), hipMemcpyHostToDevice, c->stream));
+    FHE_HIP_CHECK(c->keyswitch(nullptr, dev, count));
+    if (small) FHE_HIP_CHECK(copy_small(c, small, count));
+    if (out) {
+        FHE_HIP_CHECK(c->blind_rotate(dev, nullptr, nullptr, count));
+        FHE_HIP_CHECK(hipMemcpyAsync(out, c->d_stage_out, count * kBigCt * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    FHE_HIP_CHECK(hipStreamSynchronize(c->stream));  // h and dev live until here
+    return FHE_OK;
+}
+
 void* fhe_device_alloc(fhe_ctx* c, size_t bytes) {
     if (!c) return nullptr;
     if (hipSetDevice(c->device) != hipSuccess) return nullptr;

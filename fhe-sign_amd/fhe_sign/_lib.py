@@ -81,6 +81,9 @@ _SIGNATURES = [
     ("fhe_ctx_set_wide_threshold", C.c_int, [C.c_void_p, C.c_int]),
     ("fhe_ctx_set_br_kernel", C.c_int, [C.c_void_p, C.c_int]),
     ("fhe_ctx_set_ks_kernel", C.c_int, [C.c_void_p, C.c_int]),
+    ("fhe_keyswitch_batch", C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
+    ("fhe_pbs_lincomb_batch", C.c_int, [C.c_void_p, u64p, C.c_size_t, u32p, u32p, C.POINTER(C.c_int64), u64p, u32p,
+                                        C.c_size_t, u64p, u64p]),
     ("fhe_comm_unique_id", C.c_int, [C.POINTER(C.c_uint8)]),
     ("fhe_ctx_attach_comm", C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int]),
     ("fhe_ctx_attach_comm_timeout", C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_uint32]),

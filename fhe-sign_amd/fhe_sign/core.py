@@ -190,6 +190,41 @@ class Context:
         check(load().fhe_pbs_batch(self._h, ptr(cts), cts.shape[0], ptr(ids, C.c_uint32), ptr(out)))
         return out
 
+    def keyswitch(self, cts: np.ndarray) -> np.ndarray:
+        """the keyswitch alone (fhe_keyswitch_batch): (count, 2049) big LWE -> (count, n + 1) small LWE
+        words before the modulus switch, on the kernel set_ks_kernel selected"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, BIG_CT)
+        n = self.params.lwe_dimension if self.params is not None else 0
+        out = np.zeros((cts.shape[0], n + 1), np.uint64)
+        check(load().fhe_keyswitch_batch(self._h, ptr(cts), cts.shape[0], ptr(out)))
+        return out
+
+    def pbs_lincomb(self, blocks: np.ndarray, items, lut_ids, want_small: bool = True, want_out: bool = True):
+        """bootstraps of linear combinations through the radix layer's descriptors
+        (fhe_pbs_lincomb_batch): `items` is a list of ([(src, coef), ...], cst) over the rows of
+        `blocks`, item i through LUT lut_ids[i].  Returns (small, out): the keyswitched (count, n + 1)
+        words and the bootstrapped (count, 2049) blocks, None for the one not wanted."""
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint64).reshape(-1, BIG_CT)
+        count = len(items)
+        off = np.zeros(count + 1, np.uint32)
+        src, coef = [], []
+        for i, (terms, _) in enumerate(items):
+            src += [s for s, _ in terms]
+            coef += [c for _, c in terms]
+            off[i + 1] = len(src)
+        src = np.array(src + [0], np.uint32)  # never empty: a valid pointer for an item list without terms
+        coef = np.array(coef + [0], np.int64)
+        cst = np.array([c % (1 << 64) for _, c in items] + [0], np.uint64)
+        ids = np.ascontiguousarray(np.broadcast_to(np.asarray(lut_ids, np.uint32), (count,)))
+        n = self.params.lwe_dimension if self.params is not None else 0
+        small = np.zeros((count, n + 1), np.uint64) if want_small else None
+        out = np.zeros((count, BIG_CT), np.uint64) if want_out else None
+        check(load().fhe_pbs_lincomb_batch(
+            self._h, ptr(blocks), blocks.shape[0], ptr(off, C.c_uint32), ptr(src, C.c_uint32), ptr(coef, C.c_int64),
+            ptr(cst), ptr(ids, C.c_uint32), count, ptr(small) if want_small else None,
+            ptr(out) if want_out else None))
+        return small, out
+
     # device-resident helpers (bench)
     def alloc(self, nbytes: int) -> int:
         p = load().fhe_device_alloc(self._h, nbytes)

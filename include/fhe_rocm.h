@@ -177,6 +177,24 @@ int fhe_ctx_set_br_kernel(fhe_ctx* ctx, int kind);
 #define FHE_KS_VALU 0
 #define FHE_KS_MFMA 1
 int fhe_ctx_set_ks_kernel(fhe_ctx* ctx, int kind);
+/* The keyswitch alone: `count` big-key LWE blocks (host, count x 2049) -> small-key LWE (host,
+ * count x (n + 1) words, the 64-bit words before the modulus switch), on the kernel
+ * fhe_ctx_set_ks_kernel selected -- the same launch fhe_pbs_batch makes.  Synchronous.  count == 0 is
+ * fine; without a server key FHE_ERR_NO_KEY. */
+int fhe_keyswitch_batch(fhe_ctx* ctx, const uint64_t* in, size_t count, uint64_t* small);
+/* Bootstraps of linear combinations, as the radix layer issues them: item i is
+ *   PBS_lut_ids[i]( sum_{t in [term_off[i], term_off[i+1])} term_coef[t] * blocks[term_src[t]] + cst[i] )
+ * with cst[i] added to the body.  One descriptor per item: 1..6 terms in the inline form (coefficients
+ * must fit int32), 7..32 terms through a term table staged after the descriptors, exactly what the
+ * radix executor's flush stages and launches (keyswitch with the fused linear prologue, then the
+ * blind rotate the batch size selects).  `small` (nullable, count x (n + 1)) receives the keyswitched
+ * words, `out` (nullable, count x 2049) the bootstrapped blocks; the blind rotate runs only when
+ * `out` is given.  Host pointers; synchronous.  FHE_ERR_INVALID, before any kernel runs, for: an item
+ * with no term or more than 32, a block index >= nblocks, an inline coefficient outside int32, an
+ * unknown LUT id, term_off not starting at 0 or decreasing. */
+int fhe_pbs_lincomb_batch(fhe_ctx* ctx, const uint64_t* blocks, size_t nblocks, const uint32_t* term_off,
+                          const uint32_t* term_src, const int64_t* term_coef, const uint64_t* cst,
+                          const uint32_t* lut_ids, size_t count, uint64_t* small, uint64_t* out);
 
 /* ------------------------------------------------------------------- multi-GPU fan-out */
 /* One process per GPU.  All ranks run the same radix program on identical inputs
