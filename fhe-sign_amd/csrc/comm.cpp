@@ -686,14 +686,7 @@ int fhe_ctx_broadcast_server_key(fhe_ctx* c, int root) {
     std::swap(c->d_bsk, n_bsk);
     std::swap(c->d_bsk_e, n_e);
     drop_new();  // frees the previous key's buffers (null when there was none)
-    if (!(c->p.msg_carry() == p.msg_carry() && c->p.delta() == p.delta())) {
-        c->lut_ids.clear();
-        c->h_luts.clear();
-        c->luts_dirty = true;
-    }
-    c->p = p;
-    c->has_key = true;
-    return FHE_OK;
+    return c->adopt_key_params(p, c->has_key);
 }
 
 int fhe_ctx_set_fanout(fhe_ctx* c, uint32_t min_level, int emulate_ranks) {

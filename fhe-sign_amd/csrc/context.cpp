@@ -147,6 +147,24 @@ int fhe_ctx::ensure_ms(size_t count) {
     return FHE_OK;
 }
 
+int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
+    if (d_ms) {
+        FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read it
+        FHE_HIP_CHECK(hipFree(d_ms));
+        d_ms = nullptr;
+    }
+    ms_cap = 0;
+    ms_stride = 0;
+    if (!had_key || !(p.msg_carry() == np.msg_carry() && p.delta() == np.delta())) {
+        lut_ids.clear();
+        h_luts.clear();
+        luts_dirty = true;
+    }
+    p = np;
+    has_key = true;
+    return FHE_OK;
+}
+
 int fhe_ctx::ensure_stage(size_t count) {
     if (count <= stage_cap) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(stream));
@@ -580,6 +598,7 @@ int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
     if (!c || !sk) return FHE_ERR_INVALID;
     FHE_HIP_CHECK(hipSetDevice(c->device));
     const Params& p = sk->params;
+    const bool had_key = c->has_key;
     if (c->has_key) {
         FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
         FHE_HIP_CHECK(hipFree(c->d_ksk));
@@ -608,13 +627,9 @@ int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
     FHE_HIP_CHECK(launch_bsk_to_e(c->d_bsk, npoly, c->d_bsk_e, c->stream));
     FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
     FHE_HIP_CHECK(hipFree(d_std));
-    if (!c->has_key || !(c->p.msg_carry() == p.msg_carry() && c->p.delta() == p.delta())) {
-        c->lut_ids.clear();
-        c->h_luts.clear();
-        c->luts_dirty = true;
-    }
-    c->p = p;
-    c->has_key = true;
+    // the LUT tables survive a re-key with the same message space and delta (ids stay valid)
+    const int rc = c->adopt_key_params(p, had_key);
+    if (rc) return rc;
     if (!c->engine) {
         try {
             c->engine = new fhe::Engine(c);

@@ -148,6 +148,13 @@ struct fhe_ctx {
     size_t flags_cap = 0;
 
     int ensure_ms(size_t count);
+    // Commit point of every key install (fhe_set_server_key, the receivers of
+    // fhe_ctx_broadcast_server_key), called once the new key's device buffers are in place: drops
+    // what the previous key's parameters sized or encoded -- the d_ms workspace (row stride from n:
+    // a stride kept across a change of dimension would overlap the keyswitch's rows) and, unless the
+    // message space and delta are unchanged, the LUT tables (their ids then start again at 0) --
+    // and makes `np` the context's parameters.
+    int adopt_key_params(const fhe::Params& np, bool had_key);
     int ensure_ks(size_t count);
     // keyswitch of `count` inputs (contiguous big LWE in `in`, or descriptors) into d_ms
     hipError_t keyswitch(const uint64_t* in, const fhe::PbsDesc* desc, size_t count);

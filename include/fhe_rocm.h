@@ -38,7 +38,10 @@ extern "C" {
  * src/perf_test.rs:9).  polynomial_size 2048, glwe_dimension 1, pbs_level 1, ks_level 5,
  * ks_base_log 3 are fixed by the kernels; the others may vary. */
 typedef struct fhe_params {
-    uint32_t lwe_dimension;   /* n (834) */
+    uint32_t lwe_dimension;   /* n (834); 1 .. 2048, a multiple of the grouping.  Pinned word for word to the
+                               * oracle at 834 and at 1, 2, 15, 16, 255, 256, 833, 2048 (2, 16, 256, 2048
+                               * multi-bit too), every n <= 33 on the latency path
+                               * (tests/test_lwe_dims_gpu.py); a context may be re-keyed between them */
     uint32_t glwe_dimension;  /* k (1) */
     uint32_t polynomial_size; /* N (2048) */
     uint32_t pbs_base_log;    /* 23 */

@@ -112,3 +112,59 @@ def test_default_keys_are_drawn_from_os_entropy():
     for x, y in zip(sk.export(), ref_sk.export()):
         assert np.array_equal(x, y)
     assert load().fhe_generate_keys_keyed(C.byref(p), None, C.byref(ck.handle), C.byref(sk.handle)) != 0
+
+
+# ------------------------------------------------------------ LWE dimensions other than the default
+# The ABI takes any lwe_dimension in [1, 2048] that the grouping divides (Params::from_c); the sets
+# of tests/lwe_dims.py are the ones the GPU suite pins (tests/test_lwe_dims_gpu.py).
+from lwe_dims import MULTIBIT, SETS, oracle_params, product_params, set_id  # noqa: E402
+
+
+@pytest.fixture(scope="module", params=SETS, ids=set_id)
+def dim_keys(request):
+    n, g = request.param
+    ck, sk = generate_keys(product_params(n, g), seed=SEED)
+    ok = oracle.OracleKeys(SEED, oracle_params(n, g))
+    return n, g, ck, sk, ok
+
+
+def test_keys_identical_at_other_dimensions(dim_keys):
+    """secret keys, KSK and BSK word for word against the oracle's keygen at n != 834, and the exported
+    shapes follow n: KSK [2048][5][n + 1], BSK n (classic) or 3 n / 2 (multi-bit) GGSWs of 4 x 2048"""
+    n, g, ck, sk, ok = dim_keys
+    assert ck.params.lwe_dimension == sk.params.lwe_dimension == ok.params.n == n
+    lwe, glwe = ck.export()
+    assert lwe.shape == (n,) and glwe.shape == (2048,)
+    assert np.array_equal(lwe, ok.lwe_sk) and np.array_equal(glwe, ok.glwe_sk)
+    assert set(np.unique(lwe)) <= {0, 1}
+    ksk, bsk = sk.export()
+    ggsw = 3 * n // 2 if g == MULTIBIT else n
+    assert sk.params.ggsw_count() == ok.ggsw_count == ggsw
+    assert ksk.shape == (2048 * 5 * (n + 1),) and bsk.shape == (ggsw * 4 * 2048,)
+    assert np.array_equal(ksk, ok.ksk)
+    assert np.array_equal(bsk, ok.bsk)
+
+
+def test_encryption_identical_at_other_dimensions(dim_keys):
+    """big LWE encryption does not depend on n (the GLWE key's stream), and must not start to"""
+    _, _, ck, _, ok = dim_keys
+    ck.seed_encryption(77, 100)
+    r = ok.rng(77, 100)
+    for m in range(16):
+        a = ck.encrypt_block(m)
+        b = ok.encrypt(r, m)
+        assert np.array_equal(a, b)
+        assert ck.decrypt_block(a) == m
+        assert ok.decrypt(b) == m
+
+
+@pytest.mark.parametrize("n, grouping", [(0, 1), (2049, 1), (0, 2), (2050, 2), (1, 2), (15, 2), (833, 2), (2047, 2),
+                                         (3, 3), (834, 3), (16, 4)])
+def test_refused_dimensions_and_groupings(n, grouping):
+    """lwe_dimension outside [1, 2048], a multi-bit grouping that does not divide it, and any grouping
+    above 2: FHE_ERR_UNSUPPORTED (-5) from keygen, nothing allocated"""
+    from fhe_sign import FheError
+
+    with pytest.raises(FheError) as e:
+        generate_keys(product_params(n, grouping), seed=1)
+    assert e.value.code == -5

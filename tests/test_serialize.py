@@ -10,6 +10,7 @@ import pytest
 from fhe_sign import (BigUintFHE, ClientKey, Context, FheUint32, FheUint256, ServerKey, generate_keys,
                       set_server_key)
 from fhe_sign._lib import FheError
+from lwe_dims import MULTIBIT, SETS, product_params, set_id
 
 SEED = 0x5E71A1
 
@@ -40,6 +41,42 @@ def test_server_key_round_trip(keys):
     blob = sk.serialize()
     assert len(blob) > 100_000_000  # KSK + BSK, standard domain
     sk2 = ServerKey.deserialize(blob)
+    for a, b in zip(sk.export(), sk2.export()):
+        assert np.array_equal(a, b)
+
+
+@pytest.fixture(scope="module", params=SETS, ids=set_id)
+def dim_keys(request):
+    """keys at the LWE dimensions of tests/lwe_dims.py (every one != the default 834)"""
+    n, g = request.param
+    return (n, g) + generate_keys(product_params(n, g), seed=SEED)
+
+
+def test_client_key_round_trip_at_other_dimensions(dim_keys):
+    n, g, ck, _ = dim_keys
+    ck.seed_encryption(5, 100)
+    ck.encrypt_block(1)
+    ck2 = ClientKey.deserialize(ck.serialize())
+    assert (ck2.params.lwe_dimension, ck2.params.grouping) == (n, g)
+    lwe, glwe = ck2.export()
+    assert lwe.shape == (n,)
+    for a, b in zip(ck.export(), (lwe, glwe)):
+        assert np.array_equal(a, b)
+    for m in (0, 3, 15):
+        assert np.array_equal(ck.encrypt_block(m), ck2.encrypt_block(m))
+    assert ClientKey.deserialize(ck2.serialize()).serialize() == ck2.serialize()
+
+
+def test_server_key_round_trip_at_other_dimensions(dim_keys):
+    n, g, _, sk = dim_keys
+    blob = sk.serialize()
+    ggsw = 3 * n // 2 if g == MULTIBIT else n
+    words = 2048 * 5 * (n + 1) + ggsw * 4 * 2048
+    assert 8 * words < len(blob) < 8 * words + 4096  # the key words and a small frame: sizes follow n
+    sk2 = ServerKey.deserialize(blob)
+    del blob
+    assert (sk2.params.lwe_dimension, sk2.params.grouping) == (n, g)
+    assert sk2.params.ggsw_count() == ggsw
     for a, b in zip(sk.export(), sk2.export()):
         assert np.array_equal(a, b)
 
