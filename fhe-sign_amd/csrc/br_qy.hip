@@ -845,6 +845,363 @@ __global__ __launch_bounds__(256 * H, H == 1 ? 2 : 1) void k_blind_rotate_qy2(co
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// k_blind_rotate_qz: two ciphertexts per 4-wave workgroup like k_blind_rotate_qy2<1>, but in the
+// transform phases a wave owns ONE whole polynomial (16 points per lane) instead of 8 points of each
+// of the two ciphertexts.  Four register bits cover the ten stages in three phases (4 + 4 + 2), so the
+// A <-> B register <-> lane transposes (128 v_permlane32/16_swap per wave and CMUX in qy2) are gone:
+//
+//   phase  waves                        registers          lanes                          stages
+//   A      (ciphertext c, polynomial p) (b9 b8 b7 b6)      L5..L0 = ZA[] (b5..b0)         fwd 0-3, inv b6-b9
+//   B      (c, p)                       (b5 b4 b3 b2)      L5..L0 = ZB[] (b9..b6, b1, b0) fwd 4-7, inv b2-b5
+//   E      (b3, b2) = QW                (poly, b1, b0)     L5..L0 = QE[]                  as qy2, both c
+//
+// A <-> B: a wave-private LDS round trip through the wave's own polynomial region (no barrier);
+// B <-> E: across the four waves, one barrier each way.  Phase E, the key layout (k_bsk_to_e) and the
+// f64 operation sequence per ciphertext are qy2's: identical bits.  Forward stages 0-3 have wave-uniform
+// zetas (block indices of register bits only); stages 4-7 read 1 + 1 + 2 + 4 per-lane zetas from an LDS
+// table by (b9..b6), the inverse B stages 1 + 1 + 2 + 4 twiddles by (b1 b0), the inverse A stages
+// 1 + 1 + 2 + 4 from W in global memory (loop-invariant per lane); sibling blocks differ by exactly i
+// (fft_tables / zeta_table build them so).
+namespace {
+// layout parameters (tools/lds_layout_qz.py): additive weights of b0..b9, index bits on lane bits 5..0.
+// Every ds_read_b128 / ds_write_b128 of A, B and E is conflict-free, and ZA keeps each quad of lanes
+// inside one 128-byte line of the tables A's lanes index (untwist factors, inverse twiddles): the lane
+// order moved the step time more than the bank conflicts did
+constexpr int ZW[10] = {2, 16, 1, 4, 32, 8, 276, 550, 136, 71};
+constexpr int ZA[6] = {4, 1, 5, 3, 0, 2};
+constexpr int ZB[6] = {7, 8, 1, 9, 6, 0};
+
+FHE_DEV constexpr int zq(int idx) {
+    int p = 0;
+    for (int k = 0; k < 10; ++k)
+        if ((idx >> k) & 1) p += ZW[k];
+    return p;
+}
+constexpr int zq_max() {
+    int p = 0;
+    for (int k = 0; k < 10; ++k) p += ZW[k];
+    return p;
+}
+constexpr int ZR_SZ = zq_max() + 1;  // complex entries per polynomial region
+FHE_DEV constexpr int idx_zA(int L, int r) {  // r = (b9 b8 b7 b6)
+    int v = (r & 15) << 6;
+    for (int m = 0; m < 6; ++m) v |= bt(L, 5 - m) << ZA[m];
+    return v;
+}
+FHE_DEV constexpr int idx_zB(int L, int r) {  // r = (b5 b4 b3 b2)
+    int v = (r & 15) << 2;
+    for (int m = 0; m < 6; ++m) v |= bt(L, 5 - m) << ZB[m];
+    return v;
+}
+// LDS tables, 8 entries at stride 9 (conflict-free over the 16 values of the lane part):
+//   forward zetas by U4 = (b9 b8 b7 b6): Z[16 + U4], Z[32 + 2 U4], Z[64 + 4 U4 + 2 j] (j < 2),
+//                                        Z[128 + 8 U4 + 2 j] (j < 4)
+//   inverse twiddles by m2 = (b1 b0):    W[128 m2], W[64 m2], W[32 m2 + 128 j] (j < 2), W[16 m2 + 64 j] (j < 4)
+constexpr int ZZ_SZ = 16 * 9, ZT_SZ = 4 * 9;
+
+template <int K, class F>
+FHE_DEV void dit_pairs16(cplx (&x)[16], F&& tw) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        if (r >> K & 1) continue;
+        dit_bfly(x[r], x[r | (1 << K)], tw(r));
+    }
+}
+}  // namespace
+
+__global__ __launch_bounds__(256, 2) void k_blind_rotate_qz(const uint64_t* __restrict__ ms, int ms_stride,
+                                                            const PbsDesc* __restrict__ desc,
+                                                            const uint32_t* __restrict__ lut_idx,
+                                                            const uint64_t* __restrict__ luts,
+                                                            const cplx* __restrict__ bsk, const cplx* __restrict__ W,
+                                                            const cplx* __restrict__ ps, const cplx* __restrict__ Z,
+                                                            const cplx* __restrict__ mono, uint64_t* __restrict__ out,
+                                                            int n, int count, unsigned long long* __restrict__ clk) {
+    constexpr int NC = 2;
+    unsigned long long clk_t0 = 0, clk_r0 = 0;
+    if (clk) {
+        clk_t0 = __builtin_amdgcn_s_memtime();
+        clk_r0 = __builtin_amdgcn_s_memrealtime();
+    }
+    constexpr int ZL_Z = NC * 2 * ZR_SZ, ZL_T = ZL_Z + ZZ_SZ;
+    __shared__ __attribute__((aligned(16))) cplx s_lds[ZL_T + ZT_SZ];
+    cplx* s_z = s_lds + ZL_Z;
+    cplx* s_t = s_lds + ZL_T;
+    if (threadIdx.x < 128) {
+        const int U4 = threadIdx.x >> 3, k = threadIdx.x & 7;
+        const int zi = k == 0 ? 16 + U4 : k == 1 ? 32 + 2 * U4 : k < 4 ? 64 + 4 * U4 + 2 * (k - 2) : 128 + 8 * U4 + 2 * (k - 4);
+        s_z[9 * U4 + k] = Z[zi];
+    } else if (threadIdx.x < 128 + 32) {
+        const int m = (threadIdx.x - 128) >> 3, k = threadIdx.x & 7;
+        const int wi = k == 0 ? 128 * m : k == 1 ? 64 * m : k < 4 ? 32 * m + 128 * (k - 2) : 16 * m + 64 * (k - 4);
+        s_t[9 * m + k] = W[wi];
+    }
+    const int ct0 = blockIdx.x * NC;
+    const bool has0 = ct0 < count, has1 = ct0 + 1 < count;  // wave-uniform
+    const int cts[NC] = {has0 ? ct0 : count - 1, has1 ? ct0 + 1 : (has0 ? ct0 : count - 1)};
+    const int w = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 3), L = threadIdx.x & 63;
+    const int cw = w >> 1, p = w & 1;  // transform phases: this wave's ciphertext and polynomial
+    const int ctw = cw ? cts[1] : cts[0];
+    const bool hasw = cw ? has1 : has0;
+    const uint64_t* a_ct[NC] = {ms + (size_t)cts[0] * ms_stride, ms + (size_t)cts[1] * ms_stride};
+    cplx* reg = s_lds + w * ZR_SZ;  // region 2 c + p
+    const int v = idx_zA(L, 0);     // A layout: idx = 64 r + v (v = b5 .. b0)
+    const int iB = idx_zB(L, 0);
+    const int bA = zq(v), bB = zq(iB);
+    const int bE = zq(idx_E(w, L, 0));
+    const cplx* zt = s_z + 9 * (iB >> 6);  // (b9 .. b6) in B
+    const cplx* tt = s_t + 9 * (iB & 3);   // (b1 b0) in B
+    const int ie = idx_E(w, L, 0);
+    const int V = ie >> 2;
+    const cplx z8 = Z[256 + V], z9 = Z[512 + 2 * V];
+    uint32_t jm = 0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) jm |= (uint32_t)bt(ie, 9 - k) << k;
+    const uint32_t c4 = 4u * jm + 1u;
+    const int wb3 = QW1 == 3 ? bt(w, 1) : bt(w, 0), wb2 = QW1 == 3 ? bt(w, 0) : bt(w, 1);
+    const uint32_t kk = (uint32_t)__builtin_amdgcn_readfirstlane(wb3 + 2 * wb2);
+
+    double acc[32];  // coefficients 64 r + v (r < 16) and 1024 + 64 r + v of this wave's polynomial
+    {
+        const uint64_t* a_w = ms + (size_t)ctw * ms_stride;
+        const uint32_t btm = modswitch_2n(a_w[n]);
+        const int rotb = (int)((4096u - btm) & 4095u);
+        const uint64_t* lut = luts + (size_t)(desc ? desc[ctw].lut : lut_idx[ctw]) * 2048;
+#pragma unroll
+        for (int r = 0; r < 32; ++r) {
+            double a0 = 0.0;
+            if (p == 1) {
+                const uint32_t uu = (uint32_t)(64 * r + v - rotb) & 4095u;
+                a0 = neg_if((double)(int64_t)lut[uu & 2047u], (uu >> 11) << 31);
+            }
+            acc[r] = a0 * 0x1p-41;
+        }
+    }
+    uint32_t a_next[NC], a_next1[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        a_next[c] = modswitch_2n(a_ct[c][0]);
+        a_next1[c] = modswitch_2n(a_ct[c][1]);
+    }
+    const __amdgpu_buffer_rsrc_t mono_rs = table_rsrc(mono);
+    auto pair_factor = [&](uint32_t a) { return bptr{mono_rs, 0u, 16u * ((256u * kk * a) & 4095u)}[0]; };
+    auto lane_factor = [&](uint32_t a) { return bptr{mono_rs, ((c4 * a) & 4095u) * 16u, 0u}[0]; };
+    cplx Fn[NC], Ebn[NC], e0n[NC];  // e0n: the next step's e = lane factor x pair factor (exact when kk = 0)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) e0n[c] = cmul(lane_factor(a_next[c]), pair_factor(a_next[c]));
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t bsk_rs = table_rsrc(bsk), ps_rs = table_rsrc(ps), w_rs = table_rsrc(W);
+    const cplx* Zu = Z;  // uniform zetas of stages 0-3: Z[1], Z[2], Z[4], Z[6], Z[8], Z[10], Z[12], Z[14]
+    uint32_t upd = 0;
+    bool red_in = false;
+    for (int i = 0; i < n; ++i) {
+        uint32_t a[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            a[c] = a_next[c];
+            a_next[c] = a_next1[c];
+            a_next1[c] = modswitch_2n(a_ct[c][i + 2 <= n ? i + 2 : n]);
+        }
+        const bool reduce = (upd++ & 1u) != 0;
+        const bptr P{ps_rs, 16u * (uint32_t)v, 0u};
+        const bptr kb{bsk_rs, 16u * (uint32_t)L, (uint32_t)(i * 4096 + w * 256) * 16u};
+        cplx Kb[16];  // key slices [4 (row, column) + point k], shared by both ciphertexts
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if ((q & 3) < kKeyEarly) Kb[q] = kb[(q >> 2) * 1024 + (q & 3) * 64];
+        cplx x[16];
+        if (red_in) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) x[r].x = red_digit_s(acc[r]);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) x[r].y = red_digit_s(acc[r + 16]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) x[r] = make_double2(tor_digit_s(acc[r]), tor_digit_s(acc[r + 16]));
+        }
+        // ---- phase A: stages 0-3 (register bits 3..0 = b9..b6, uniform zetas)
+        dit_pairs16<3>(x, [&](int) { return Zu[1]; });
+        dit_pairs16<2>(x, [&](int r) { return (r >> 3) ? mul_i(Zu[2]) : Zu[2]; });
+        dit_pairs16<1>(x, [&](int r) {
+            const cplx base = Zu[4 + 2 * (r >> 3)];
+            return (r >> 2 & 1) ? mul_i(base) : base;
+        });
+        dit_pairs16<0>(x, [&](int r) {
+            const cplx base = Zu[8 + 2 * (r >> 2)];
+            return (r >> 1 & 1) ? mul_i(base) : base;
+        });
+        // ---- A -> B (wave-private LDS round trip)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) reg[bA + zq(idx_zA(0, r))] = x[r];
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) x[r] = reg[bB + zq(idx_zB(0, r))];
+        // ---- phase B: stages 4-7 (register bits 3..0 = b5..b2)
+        {
+            const cplx z4 = zt[0];
+            dit_pairs16<3>(x, [&](int) { return z4; });
+            const cplx z5 = zt[1];
+            dit_pairs16<2>(x, [&](int r) { return (r >> 3) ? mul_i(z5) : z5; });
+            const cplx z6[2] = {zt[2], zt[3]};
+            dit_pairs16<1>(x, [&](int r) {
+                const cplx base = z6[r >> 3];
+                return (r >> 2 & 1) ? mul_i(base) : base;
+            });
+            const cplx z7[4] = {zt[4], zt[5], zt[6], zt[7]};
+            dit_pairs16<0>(x, [&](int r) {
+                const cplx base = z7[r >> 2];
+                return (r >> 1 & 1) ? mul_i(base) : base;
+            });
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) reg[bB + zq(idx_zB(0, r))] = x[r];
+        cplx e0[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            e0[c] = e0n[c];
+            Fn[c] = pair_factor(a_next[c]);
+            Ebn[c] = lane_factor(a_next[c]);
+        }
+        __syncthreads();
+        // phase E at issue priority 1 until the second barrier, as in k_blind_rotate_qy2
+        __builtin_amdgcn_s_setprio(1);
+        // ---- phase E: both polynomials of each ciphertext at this wave's points, one ciphertext after the
+        // other (k_blind_rotate_qy2's, on this kernel's LDS map)
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if ((q & 3) >= kKeyEarly) Kb[q] = kb[(q >> 2) * 1024 + (q & 3) * 64];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            if (c) __builtin_amdgcn_sched_barrier(0);
+            cplx y[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) y[r] = s_lds[(2 * c + (r >> 2)) * ZR_SZ + bE + zq(idx_E(0, 0, r & 3))];
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if (!(r & 2)) dit_bfly(y[r], y[r + 2], z8);
+#pragma unroll
+            for (int r = 0; r < 8; r += 2) dit_bfly(y[r], y[r + 1], (r & 2) ? mul_i(z9) : z9);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const cplx d0 = y[k], d1 = y[4 + k];
+                const cplx o0 = mac2(d0, Kb[0 * 4 + k], d1, Kb[2 * 4 + k]);
+                const cplx o1 = mac2(d1, Kb[3 * 4 + k], d0, Kb[1 * 4 + k]);
+                const uint32_t tr = (uint32_t)((k >> 1) + 2 * (k & 1)) * a[c];
+                const cplx wv = k == 0 ? make_double2(e0[c].x - 1.0, e0[c].y) : turn_sel_m1(e0[c], tr);
+                y[k] = cmul(o0, wv);
+                y[4 + k] = cmul(o1, wv);
+            }
+            // ---- inverse: b0, b1 in E
+#pragma unroll
+            for (int r = 0; r < 8; r += 2) {
+                const cplx a0 = y[r], c0 = y[r + 1];
+                y[r] = cadd(a0, c0);
+                y[r + 1] = csub(a0, c0);
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                if (r & 2) continue;
+                dit_bfly_unit(y[r], y[r + 2], (r & 1) ? mul_negi(y[r + 2]) : y[r + 2]);
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) s_lds[(2 * c + (r >> 2)) * ZR_SZ + bE + zq(idx_E(0, 0, r & 3))] = y[r];
+        }
+        __builtin_amdgcn_s_setprio(0);
+        __syncthreads();
+        // ---- B (inverse): b2 (register bit 0), b3, b4, b5 (bit 3)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) x[r] = reg[bB + zq(idx_zB(0, r))];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) e0n[c] = cmul(Ebn[c], Fn[c]);  // loaded before the first barrier
+        {
+            const cplx w2 = conj_(tt[0]);
+            dit_pairs16<0>(x, [&](int) { return w2; });
+            const cplx w3 = tt[1];
+            dit_pairs16<1>(x, [&](int r) { return conj_((r & 1) ? mul_i(w3) : w3); });
+            const cplx w4[2] = {tt[2], tt[3]};
+            dit_pairs16<2>(x, [&](int r) {
+                const cplx base = w4[r & 1];
+                return conj_((r & 2) ? mul_i(base) : base);
+            });
+            const cplx w5[4] = {tt[4], tt[5], tt[6], tt[7]};
+            dit_pairs16<3>(x, [&](int r) {
+                const cplx base = w5[r & 3];
+                return conj_((r & 4) ? mul_i(base) : base);
+            });
+        }
+        // ---- B -> A (wave-private LDS round trip)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) reg[bB + zq(idx_zB(0, r))] = x[r];
+        wave_sync();
+        // inverse twiddles of phase A: W[8 v], W[4 v], W[2 v + 128 j], W[v + 64 j] (loop-invariant per lane)
+        const bptr W8{w_rs, 128u * (uint32_t)v, 0u}, W4{w_rs, 64u * (uint32_t)v, 0u};
+        const bptr W2{w_rs, 32u * (uint32_t)v, 0u}, W1{w_rs, 16u * (uint32_t)v, 0u};
+        const cplx w6 = conj_(W8[0]), w7 = W4[0];
+        const cplx w8[2] = {W2[0], W2[128]};
+        const cplx w9[4] = {W1[0], W1[64], W1[128], W1[192]};
+        cplx pst[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (!(r & 4)) pst[r] = P[1024 + 64 * r];  // the untwist factors of the last stage's pairs 0-3
+#pragma unroll
+        for (int r = 0; r < 16; ++r) x[r] = reg[bA + zq(idx_zA(0, r))];
+        // ---- A (inverse): b6 (register bit 0), b7, b8, b9 (bit 3)
+        dit_pairs16<0>(x, [&](int) { return w6; });
+        dit_pairs16<1>(x, [&](int r) { return conj_((r & 1) ? mul_i(w7) : w7); });
+        dit_pairs16<2>(x, [&](int r) {
+            const cplx base = w8[r & 1];
+            return conj_((r & 2) ? mul_i(base) : base);
+        });
+        // pairs 4-7's factors only now (w6 .. w8 are dead): all 16 at once with x, acc and the twiddles do
+        // not fit 256 registers
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (r & 4) pst[r] = P[1024 + 64 * r];
+        // the last stage pair by pair, each followed by its untwist and accumulation (point j = 64 r + v ->
+        // coefficients j, j + 1024), so the transform registers retire as the untwist factors arrive
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const cplx base = w9[r & 3];
+            dit_bfly(x[r], x[r + 8], conj_((r & 4) ? mul_i(base) : base));
+#pragma unroll
+            for (int q = r; q < 16; q += 8) {
+                const cplx y = cmul_acc(make_double2(acc[q], acc[q + 16]), x[q], pst[q]);
+                acc[q] = y.x;
+                acc[q + 16] = y.y;
+            }
+        }
+        red_in = reduce;
+    }
+    if (hasw) {
+        if (red_in) {
+#pragma unroll
+            for (int r = 0; r < 32; ++r) acc[r] = tor_red_s(acc[r]);
+        }
+        uint64_t* o = desc ? desc[ctw].dst : out + (size_t)ctw * 2049;
+        if (p == 0) {
+#pragma unroll
+            for (int r = 0; r < 32; ++r) {
+                const int j = 64 * r + v;
+                const uint64_t t = f64_to_torus(acc[r] * 0x1p41);
+                if (j == 0) o[0] = t;
+                else o[2048 - j] = 0ull - t;
+            }
+        } else if (v == 0) {
+            o[2048] = f64_to_torus(acc[0] * 0x1p41);
+        }
+    }
+    if (clk) {
+        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+        if (threadIdx.x == 0) {
+            atomicAdd(&clk[0], t1 - clk_t0);
+            atomicAdd(&clk[1], r1 - clk_r0);
+            atomicAdd(&clk[2], 1ull);
+        }
+    }
+}
+
 // Fourier BSK: blind-rotate layout (R = 4v + q, lane L' <-> idx = 4 (L' + 64 v) + q) -> E layout
 // [poly][wave e][point k][lane], one workgroup per polynomial.
 __global__ __launch_bounds__(256) void k_bsk_to_e(const cplx* __restrict__ src, cplx* __restrict__ dst) {
@@ -869,7 +1226,10 @@ hipError_t launch_blind_rotate_qy(const uint64_t* ms, int ms_stride, const PbsDe
                                   unsigned long long* clk, int two_per_wg, hipStream_t s) {
     if (count <= 0) return hipSuccess;
     if (grouping == 1 && two_per_wg > 0) {
-        if (two_per_wg == 2)
+        if (two_per_wg == 3)
+            hipLaunchKernelGGL(k_blind_rotate_qz, dim3((count + 1) / 2), dim3(256), 0, s, ms, ms_stride, desc, lut_idx,
+                               luts, bsk_e, tw, ps, zfull, mono, out, n, count, clk);
+        else if (two_per_wg == 2)
             hipLaunchKernelGGL(k_blind_rotate_qy2<2>, dim3((count + 3) / 4), dim3(512), 0, s, ms, ms_stride, desc,
                                lut_idx, luts, bsk_e, tw, ps, zfull, mono, out, n, count, clk);
         else

@@ -59,12 +59,12 @@ struct fhe_ctx {
     double2* d_mono = nullptr;      // monomial table E[4096] of the multi-bit blind rotation (mono_table)
     int8_t* d_ksk_planes = nullptr; // KSK as balanced signed-byte planes (ks_mfma.hip)
     int ks_kernel = FHE_KS_MFMA;
-    // classic throughput kernel (fhe_ctx_set_br_kernel): FHE_BR_AUTO = qy2 (two ciphertexts per workgroup)
-    // where its rounds of 1024 (256 CUs x 2 workgroups x 2) fill well -- from kQy2Min bootstraps on, and
-    // above 960 when the last round is more than three quarters full (1012: 7.45 vs 7.9 ms) -- qy below
-    // and between (qy2
+    // classic throughput kernel (fhe_ctx_set_br_kernel): FHE_BR_AUTO = qz (two ciphertexts per workgroup,
+    // one wave per polynomial; it replaced qy2 here, same quantisation) where its rounds of 1024 (256 CUs x
+    // 2 workgroups x 2) fill well -- from kQy2Min bootstraps on, and above 960 when the last round is more
+    // than three quarters full (qy2, 1012: 7.45 vs 7.9 ms) -- qy below and between (two per workgroup
     // quantises worse: profiles/r6/qy2_sizes_r6l.txt, qy_qy2_thresh_r6z.txt: 1024 -5 %, 2048 -2 %, 2560
-    // even, 1280 / 1536 +19 / +2 %); FHE_BR_QY / _QY2 / _QY4 force one kernel
+    // even, 1280 / 1536 +19 / +2 %); FHE_BR_QY / _QY2 / _QY4 / _QZ force one kernel
     int br_kernel = FHE_BR_AUTO;
     static constexpr int kQy2Min = 3072;
     static bool qy2_fills(size_t count) {

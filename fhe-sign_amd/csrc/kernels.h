@@ -69,7 +69,8 @@ hipError_t launch_lincomb(const PbsDesc* desc, int count, hipStream_t s);
 // (context.cpp zeta_table); grouping 2 = the multi-bit blind rotation on the multi-bit key; clk: null,
 // or the clock probe's accumulators {shader cycles, 100 MHz ticks, workgroups} (fhe_ctx_enable_clock);
 // two_per_wg (classic only): k_blind_rotate_qy2 -- 1: two ciphertexts per 4-wave workgroup sharing the key
-// stream, 2: two such halves per 8-wave workgroup
+// stream, 2: two such halves per 8-wave workgroup, 3: k_blind_rotate_qz (two per 4-wave workgroup, one wave
+// per polynomial in the transform phases)
 hipError_t launch_bsk_to_e(const double2* bsk, int npoly, double2* out, hipStream_t s);
 hipError_t launch_blind_rotate_qy(const uint64_t* ms, int ms_stride, const PbsDesc* desc, const uint32_t* lut_idx,
                                   const uint64_t* luts, const double2* bsk_e, const double2* tw, const double2* ps,

@@ -172,7 +172,12 @@ int fhe_ctx_set_wide_threshold(fhe_ctx* ctx, int threshold);
 #define FHE_BR_QY 4
 #define FHE_BR_QY2 5 /* br_qy.hip k_blind_rotate_qy2<1>: classic, two ciphertexts per workgroup sharing key slices */
 #define FHE_BR_QY4 6 /* k_blind_rotate_qy2<2>: two such pairs per 8-wave workgroup (the pairs' key reads meet in L1) */
-#define FHE_BR_AUTO 7 /* default: qy2<1> for classic levels of >= 3072 bootstraps, qy below and for multi-bit */
+/* default.  Classic levels go to k_blind_rotate_qz where its rounds of 1024 bootstraps (256 CUs x 2
+ * workgroups x 2 ciphertexts) fill well: every level of >= 3072, and a level above 960 whose last round
+ * is full or more than three quarters full (count % 1024 == 0 or > 768).  Every other level above the
+ * latency threshold, and every multi-bit level, goes to k_blind_rotate_qy. */
+#define FHE_BR_AUTO 7
+#define FHE_BR_QZ 9 /* br_qy.hip k_blind_rotate_qz: classic, two ciphertexts per workgroup, one wave per polynomial in the transforms (no lane transposes); 8 is not a kind */
 int fhe_ctx_set_br_kernel(fhe_ctx* ctx, int kind);
 
 /* Keyswitch: int8 matrix-core contraction against the KSK's byte planes (FHE_KS_MFMA, default) or
