@@ -9,6 +9,8 @@
 
 #include <future>
 
+#include <sys/random.h>
+
 #include "biguint.h"
 #include "fhe_rocm.h"
 #include "serial.h"
@@ -1280,5 +1282,201 @@ int fhe_biguint_deserialize(fhe_ctx* c, const uint8_t* buf, size_t len, fhe_bigu
         return FHE_OK;
     });
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------- seeded ciphertexts
+// tfhe-rs' CompressedFheUint: a public mask seed and one body per block (keys.h fhe_seeded); the masks
+// are regenerated at expansion, on the host (expand_seeded_host) or on the GPU (Engine::expand_seeded).
+// Payload of ser::kSeeded: params, u32 form, u32 count, 32 seed bytes, nblocks u64 bodies.
+namespace {
+int invalid(const std::string& why) {
+    set_error(why);
+    return FHE_ERR_INVALID;
+}
+// blocks of a form/count pair; false if the pair is malformed or exceeds the ChaCha counter range
+bool seeded_nblocks(uint32_t form, uint32_t count, size_t* nblocks, std::string* why) {
+    if (form == FHE_SEEDED_RADIX) {
+        if (!valid_bits(count)) {
+            *why = "seeded radix: num_bits must be even, >= 2 and <= FHE_RADIX_MAX_BITS";
+            return false;
+        }
+        *nblocks = count / 2;
+        return true;
+    }
+    if (form == FHE_SEEDED_BIGUINT) {
+        if ((uint64_t)count * kLimbBlocks > kSeededMaxBlocks) {
+            *why = "seeded BigUintFHE: more than 2^24 blocks (the mask stream's 32-bit block counter)";
+            return false;
+        }
+        *nblocks = (size_t)count * kLimbBlocks;
+        return true;
+    }
+    *why = "seeded object: unknown form";
+    return false;
+}
+int seeded_encrypt(fhe_client_key* ck, uint32_t form, uint32_t count, const std::vector<uint64_t>& pts,
+                   const uint8_t* mask_seed, fhe_seeded** out) {
+    return guarded([&] {
+        auto x = std::make_unique<fhe_seeded>();
+        x->params = ck->params;
+        x->form = form;
+        x->count = count;
+        if (mask_seed) {
+            std::memcpy(x->seed, mask_seed, 32);
+        } else {
+            for (size_t got = 0; got < 32;) {
+                const ssize_t k = getrandom(x->seed + got, 32 - got, 0);
+                if (k <= 0) {
+                    set_error("getrandom failed: no mask seed");
+                    return FHE_ERR_UNSUPPORTED;
+                }
+                got += (size_t)k;
+            }
+        }
+        x->bodies.resize(pts.size());
+        encrypt_seeded(ck, x->seed, pts.data(), pts.size(), x->bodies.data());
+        *out = x.release();
+        return FHE_OK;
+    });
+}
+// the checks of every GPU expansion, before anything is allocated or launched
+int seeded_expand_check(fhe_ctx* c, const fhe_seeded* x, uint32_t form) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x) return invalid("null seeded object");
+    if (x->form != form)
+        return invalid(form == FHE_SEEDED_RADIX ? "seeded object holds a BigUintFHE, not a radix integer"
+                                                : "seeded object holds a radix integer, not a BigUintFHE");
+    const Params &a = x->params, &b = c->p;
+    const struct {
+        const char* name;
+        uint32_t have, want;
+    } fields[] = {{"message_modulus", a.message_modulus, b.message_modulus},
+                  {"carry_modulus", a.carry_modulus, b.carry_modulus},
+                  {"lwe_dimension", a.n, b.n},
+                  {"pbs_base_log", a.pbs_base_log, b.pbs_base_log},
+                  {"ks_base_log", a.ks_base_log, b.ks_base_log},
+                  {"ks_level", a.ks_level, b.ks_level},
+                  {"lwe_noise_log2", a.lwe_noise_log2, b.lwe_noise_log2},
+                  {"glwe_noise_log2", a.glwe_noise_log2, b.glwe_noise_log2}};
+    for (const auto& f : fields)
+        if (f.have != f.want)
+            return invalid(std::string("seeded object's ") + f.name + " (" + std::to_string(f.have) +
+                           ") differs from the context's server key (" + std::to_string(f.want) + ")");
+    return FHE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fhe_radix_encrypt_seeded(fhe_client_key* ck, const uint64_t* words, uint32_t bits, const uint8_t* mask_seed,
+                             fhe_seeded** out) {
+    if (!ck || !words || !out || !valid_bits(bits)) return invalid("invalid arguments to fhe_radix_encrypt_seeded");
+    std::vector<uint64_t> pts(bits / 2);
+    for (uint32_t k = 0; k < bits / 2; ++k) pts[k] = (uint64_t)word_bits(words, 2 * k, bits) * ck->params.delta();
+    return seeded_encrypt(ck, FHE_SEEDED_RADIX, bits, pts, mask_seed, out);
+}
+
+int fhe_biguint_encrypt_seeded(fhe_client_key* ck, const uint32_t* limbs, size_t n, const uint8_t* mask_seed,
+                               fhe_seeded** out) {
+    if (!ck || !out || (n && !limbs)) return invalid("invalid arguments to fhe_biguint_encrypt_seeded");
+    if (n > kSeededMaxBlocks / kLimbBlocks)
+        return invalid("seeded BigUintFHE: more than 2^24 blocks (the mask stream's 32-bit block counter)");
+    return guarded([&] {
+        std::vector<uint64_t> pts(n * kLimbBlocks);
+        for (size_t i = 0; i < n; ++i)
+            for (uint32_t k = 0; k < kLimbBlocks; ++k)
+                pts[i * kLimbBlocks + k] = (uint64_t)((limbs[i] >> (2 * k)) & 3u) * ck->params.delta();
+        return seeded_encrypt(ck, FHE_SEEDED_BIGUINT, (uint32_t)n, pts, mask_seed, out);
+    });
+}
+
+int fhe_seeded_info(const fhe_seeded* x, uint32_t* form, uint32_t* count, size_t* nblocks) {
+    if (!x) return FHE_ERR_INVALID;
+    if (form) *form = x->form;
+    if (count) *count = x->count;
+    if (nblocks) *nblocks = x->bodies.size();
+    return FHE_OK;
+}
+
+int fhe_seeded_serialize(const fhe_seeded* x, uint8_t* buf, size_t cap, size_t* len) {
+    if (!x || !len) return FHE_ERR_INVALID;
+    return guarded([&] {
+        ser::Writer w;
+        w.b.reserve(80 + x->bodies.size() * 8);
+        w.params(x->params);
+        w.u32(x->form);
+        w.u32(x->count);
+        w.raw(x->seed, 32);
+        w.words(x->bodies.data(), x->bodies.size());
+        return ser::emit(ser::frame(ser::kSeeded, w.b), buf, cap, len);
+    });
+}
+
+int fhe_seeded_deserialize(const uint8_t* buf, size_t len, fhe_seeded** out) {
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        ser::Reader r;
+        std::string why;
+        Params p;
+        if (!ser::unframe(buf, len, ser::kSeeded, &r, &why) || !r.params(&p, &why)) return invalid(why);
+        const uint32_t form = r.u32(), count = r.u32();
+        size_t nblocks = 0;
+        if (!r.ok) return invalid("truncated seeded header");
+        if (!seeded_nblocks(form, count, &nblocks, &why)) return invalid(why);
+        // the length first: nothing is allocated for a count the payload does not back
+        if (r.n - r.off != 32 + nblocks * 8) return invalid("seeded object: block count inconsistent with the payload length");
+        auto x = std::make_unique<fhe_seeded>();
+        x->params = p;
+        x->form = form;
+        x->count = count;
+        r.take(x->seed, 32);
+        x->bodies.resize(nblocks);
+        if (!r.words(x->bodies.data(), nblocks) || !r.done()) return invalid("malformed seeded object");
+        *out = x.release();
+        return FHE_OK;
+    });
+}
+
+int fhe_seeded_expand_host(const fhe_seeded* x, uint64_t* cts, size_t nwords) {
+    if (!x || (!cts && !x->bodies.empty()) || nwords < x->bodies.size() * kBigCt)
+        return invalid("invalid arguments to fhe_seeded_expand_host (nblocks x 2049 words)");
+    return guarded([&] {
+        expand_seeded_host(x->seed, x->bodies.data(), x->bodies.size(), cts);
+        return FHE_OK;
+    });
+}
+
+int fhe_seeded_expand_radix(fhe_ctx* c, const fhe_seeded* x, fhe_radix** out) {
+    int rc = seeded_expand_check(c, x, FHE_SEEDED_RADIX);
+    if (rc) return rc;
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        Radix r;
+        r.blocks = c->engine->expand_seeded(x->seed, x->bodies.data(), x->bodies.size());
+        *out = wrap(std::move(r), x->count);
+        return FHE_OK;
+    });
+}
+
+int fhe_seeded_expand_biguint(fhe_ctx* c, const fhe_seeded* x, fhe_biguint** out) {
+    int rc = seeded_expand_check(c, x, FHE_SEEDED_BIGUINT);
+    if (rc) return rc;
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        const Blocks all = c->engine->expand_seeded(x->seed, x->bodies.data(), x->bodies.size());
+        auto v = std::make_unique<fhe_biguint>();
+        for (size_t at = 0; at < all.size(); at += kLimbBlocks) {
+            Radix d;
+            d.blocks.assign(all.begin() + at, all.begin() + at + kLimbBlocks);
+            v->v.digits.push_back(std::move(d));
+        }
+        *out = v.release();
+        return FHE_OK;
+    });
+}
+
+void fhe_seeded_destroy(fhe_seeded* x) { delete x; }
 
 }  // extern "C"

@@ -14,6 +14,11 @@ ChaChaKey chacha_stream_key(const uint32_t key[8], uint32_t stream);
 
 // out[q] = u64 word q of the stream (q < count; count / 8 blocks must stay below 2^32)
 hipError_t launch_chacha_u64(const ChaChaKey& k, uint64_t* out, uint64_t count, hipStream_t s);
+// seeded.hip: for b < nblocks, dst[b][0 .. 2048) = u64 words [2048 b, 2048 b + 2048) of the stream (ChaCha
+// blocks 256 b ..; nblocks <= 2^24 keeps the counter in 32 bits) and dst[b][2048] = bodies[b]; dst and
+// bodies are device arrays, every dst[b] a slot of 2049 words
+hipError_t launch_expand_seeded(const ChaChaKey& k, uint64_t* const* dst, const uint64_t* bodies, int nblocks,
+                                hipStream_t s);
 // ksk holds the KSK stream words ([rows][n + 1], rows = N * levels): bodies computed in place
 hipError_t launch_ksk_bodies(uint64_t* ksk, const uint64_t* lwe_sk, const uint64_t* glwe_sk, int n, int rows,
                              int levels, int base_log, int noise_log2, hipStream_t s);

@@ -11,46 +11,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "chacha_device.h"
 #include "keygen.h"
 
 namespace fhe {
 
 namespace {
 
-__device__ __forceinline__ uint32_t rotl32(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }
-__device__ __forceinline__ void qr(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d) {
-    a += b; d ^= a; d = rotl32(d, 16);
-    c += d; b ^= c; b = rotl32(b, 12);
-    a += b; d ^= a; d = rotl32(d, 8);
-    c += d; b ^= c; b = rotl32(b, 7);
-}
-
-// out[8 g .. 8 g + 8) = u64 words 8 g .. of the stream (block g: counter g, RFC 8439 layout as
-// keys.cpp ChaChaStream::refill; next_u64 = word 2k | word 2k+1 << 32)
+// out[8 g .. 8 g + 8) = u64 words 8 g .. of the stream (block g: counter g, chacha_device.h;
+// next_u64 = word 2k | word 2k+1 << 32)
 __global__ __launch_bounds__(256) void k_chacha_u64(ChaChaKey k, uint64_t* __restrict__ out, uint64_t count) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g * 8 >= count) return;
-    uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u,
-                      k.key[0], k.key[1], k.key[2], k.key[3], k.key[4], k.key[5], k.key[6], k.key[7],
-                      (uint32_t)g, k.nonce[0], k.nonce[1], k.nonce[2]};
-    uint32_t x[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) x[i] = s[i];
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        qr(x[0], x[4], x[8], x[12]);
-        qr(x[1], x[5], x[9], x[13]);
-        qr(x[2], x[6], x[10], x[14]);
-        qr(x[3], x[7], x[11], x[15]);
-        qr(x[0], x[5], x[10], x[15]);
-        qr(x[1], x[6], x[11], x[12]);
-        qr(x[2], x[7], x[8], x[13]);
-        qr(x[3], x[4], x[9], x[14]);
-    }
+    uint32_t o[16];
+    chacha_block(k, (uint32_t)g, o);
 #pragma unroll
     for (int w = 0; w < 8; ++w) {
         const uint64_t q = g * 8 + w;
-        if (q < count) out[q] = (uint64_t)(x[2 * w] + s[2 * w]) | ((uint64_t)(x[2 * w + 1] + s[2 * w + 1]) << 32);
+        if (q < count) out[q] = (uint64_t)o[2 * w] | ((uint64_t)o[2 * w + 1] << 32);
     }
 }
 

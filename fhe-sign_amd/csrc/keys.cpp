@@ -350,6 +350,52 @@ void encrypt_big_many(fhe_client_key* ck, const uint64_t* pts, size_t n, uint64_
     ck->enc_rng = probe;  // positioned after the n-th encryption
 }
 
+// ------------------------------------------------------------------------------ seeded form
+namespace {
+// fn(lo, hi, masks) over [0, n) on up to 16 host threads, each with a mask stream of its own seeked to
+// its first block (2048 u64 = 4096 stream words per block); block ranges only split the work
+template <class F>
+void seeded_blocks(const uint8_t seed[32], size_t n, F&& fn) {
+    const KeyWords key = bytes_key(seed);
+    auto range = [&](size_t lo, size_t hi) {
+        ChaChaStream masks(key, kStreamSeededMask);
+        masks.seek((uint64_t)lo * 2 * kBigDim);
+        fn(lo, hi, masks);
+    };
+    const size_t hw = std::max(1u, std::thread::hardware_concurrency());
+    const size_t T = std::min<size_t>(std::min<size_t>(hw, 16), n / 8);  // as encrypt_big_many: >= 8 blocks each
+    if (T <= 1) return range(0, n);
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < T; ++t) th.emplace_back([&, t] { range(n * t / T, n * (t + 1) / T); });
+    for (auto& x : th) x.join();
+}
+}  // namespace
+
+void encrypt_seeded(fhe_client_key* ck, const uint8_t seed[32], const uint64_t* pts, size_t n, uint64_t* bodies) {
+    std::vector<uint64_t> noise(n);  // the n stream words first: the stream advances by exactly n u64
+    ck->enc_rng.fill_u64(noise.data(), n);
+    const uint32_t nb = ck->params.glwe_noise_log2;
+    const uint64_t* sk = ck->glwe_sk.data();
+    seeded_blocks(seed, n, [&](size_t lo, size_t hi, ChaChaStream& masks) {
+        std::vector<uint64_t> a(kBigDim);
+        for (size_t i = lo; i < hi; ++i) {
+            masks.fill_u64(a.data(), kBigDim);
+            uint64_t dot = 0;
+            for (uint32_t j = 0; j < kBigDim; ++j) dot += a[j] * sk[j];
+            bodies[i] = dot + pts[i] + (uint64_t)tuniform_of(noise[i], nb);
+        }
+    });
+}
+
+void expand_seeded_host(const uint8_t seed[32], const uint64_t* bodies, size_t n, uint64_t* cts) {
+    seeded_blocks(seed, n, [&](size_t lo, size_t hi, ChaChaStream& masks) {
+        for (size_t i = lo; i < hi; ++i) {
+            masks.fill_u64(cts + i * kBigCt, kBigDim);
+            cts[i * kBigCt + kBigDim] = bodies[i];
+        }
+    });
+}
+
 uint64_t decrypt_phase_big(const fhe_client_key* ck, const uint64_t* ct) {
     uint64_t dot = 0;
     for (uint32_t j = 0; j < kBigDim; ++j) dot += ct[j] * ck->glwe_sk[j];

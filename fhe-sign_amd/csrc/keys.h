@@ -89,6 +89,11 @@ int64_t tuniform_of(uint64_t x, uint32_t log2_bound);
 
 // Stream ids (shared convention with the oracle so key bytes can be compared).
 enum : uint32_t { kStreamSecret = 1, kStreamKsk = 2, kStreamBsk = 3, kStreamEncrypt = 100 };
+// Mask stream of a seeded ciphertext (fhe_seeded below).  Keyed by the object's PUBLIC 32-byte seed, not
+// by the client's key: it shares nothing with the streams above.
+constexpr uint32_t kStreamSeededMask = 101;
+// The ChaCha block counter is 32 bits and one radix block takes 256 ChaCha blocks of masks.
+constexpr uint64_t kSeededMaxBlocks = 1ull << 24;
 
 }  // namespace fhe
 
@@ -97,6 +102,18 @@ struct fhe_client_key {
     std::vector<uint64_t> lwe_sk;   // n binary
     std::vector<uint64_t> glwe_sk;  // N binary (= big LWE key)
     fhe::ChaChaStream enc_rng;
+};
+
+// A seeded (compressed) fresh ciphertext: tfhe-rs' CompressedFheUint.  Host only, no context.
+// Block i's 2048 mask words are u64 words [2048 i, 2048 (i + 1)) of ChaChaStream(bytes_key(seed),
+// kStreamSeededMask) -- ChaCha block counter 256 i -- so only the seed and one body word per block are
+// kept: body_i = <mask_i, glwe_sk> + delta m_i + e_i.
+struct fhe_seeded {
+    fhe::Params params;
+    uint32_t form = 0;   // FHE_SEEDED_RADIX / FHE_SEEDED_BIGUINT
+    uint32_t count = 0;  // num_bits (radix) or nlimbs (BigUintFHE: 16 blocks per limb, limb 0 first)
+    uint8_t seed[32] = {};
+    std::vector<uint64_t> bodies;  // one per block, LSB block first
 };
 
 struct fhe_server_key {
@@ -114,6 +131,16 @@ void encrypt_big(fhe_client_key* ck, uint64_t plaintext, uint64_t* ct);
 // n encryptions (plaintexts already scaled), outputs and stream state identical to n encrypt_big
 // calls; large batches run on several host threads over seeked copies of the stream
 void encrypt_big_many(fhe_client_key* ck, const uint64_t* plaintexts, size_t n, uint64_t* cts);
+// Seeded encryption of n scaled plaintexts: bodies[i] as in fhe_seeded, masks from the PUBLIC `seed`
+// (32 bytes), noise e_i = tuniform_of(w_i, glwe_noise_log2) with w_i the next u64 of ck->enc_rng -- exactly
+// one stream word per block, in block order, whatever the number of host threads.  n <= kSeededMaxBlocks
+// (the caller checks).  A seed must never serve two objects under one client key: equal masks make
+// body - body' = delta (m - m') + e - e', which leaks the difference of the messages.
+void encrypt_seeded(fhe_client_key* ck, const uint8_t seed[32], const uint64_t* plaintexts, size_t n,
+                    uint64_t* bodies);
+// The full ciphertexts of a seeded object: cts[i] = mask_i (regenerated) then bodies[i]; n x 2049 words.
+// The word-for-word definition of the device expansion (seeded.hip).
+void expand_seeded_host(const uint8_t seed[32], const uint64_t* bodies, size_t n, uint64_t* cts);
 uint64_t decrypt_phase_big(const fhe_client_key* ck, const uint64_t* ct);
 uint64_t decode_block(const Params& p, uint64_t phase);  // value incl. carry, mod msg*carry
 }  // namespace fhe

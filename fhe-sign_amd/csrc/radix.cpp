@@ -13,6 +13,7 @@
 // Public structure only (degrees, trivial blocks) drives the schedule; no decision ever depends
 // on encrypted data.
 #include "radix.h"
+#include "keygen.h"
 
 #include <algorithm>
 #include <array>
@@ -1001,6 +1002,36 @@ Blocks Engine::upload_many(const uint64_t* cts, size_t n, uint32_t degree) {
     hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "upload");
     hip_check(launch_scatter_blocks(d_up_, d_dst, (int)n, ctx_->stream), "upload scatter");
     hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go
+    return out;
+}
+
+Blocks Engine::expand_seeded(const uint8_t seed[32], const uint64_t* bodies, size_t n) {
+    engine_check(host_mode_ == kDevice, "expand_seeded on a host-only engine");
+    engine_check(n <= kSeededMaxBlocks, "seeded object of more than 2^24 blocks");
+    Blocks out(n);
+    if (n == 0) return out;
+    const size_t words = 2 * n;  // the bodies, then the slot pointers
+    if (words > up_cap_) {
+        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
+        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
+        hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc upload");
+        up_cap_ = words;
+    }
+    std::vector<uint64_t*> dst(n);
+    for (size_t i = 0; i < n; ++i) {
+        out[i].slot = pool_->alloc();
+        out[i].degree = 3;
+        out[i].noise = 1;
+        dst[i] = out[i].slot->p;
+    }
+    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up_ + n);
+    hip_check(hipMemcpyAsync(d_up_, bodies, n * 8, hipMemcpyHostToDevice, ctx_->stream), "seeded bodies");
+    hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
+              "seeded slots");
+    const KeyWords key = bytes_key(seed);
+    hip_check(launch_expand_seeded(chacha_stream_key(key.data(), kStreamSeededMask), d_dst, d_up_, (int)n, ctx_->stream),
+              "seeded expansion");
+    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
     return out;
 }
 

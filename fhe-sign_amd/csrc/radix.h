@@ -182,6 +182,16 @@ public:
     // that reads the slots is recorded while the ciphertexts are being made, and the upload still
     // precedes every launch on the stream.  One pending deferred upload at a time.
     Blocks upload_deferred(size_t n, uint32_t degree, std::function<std::vector<uint64_t>()> fill);
+    // A seeded ciphertext's blocks (fhe_seeded: public mask seed + one body per block) expanded on the
+    // device: n fresh slots (degree 3, noise 1, as upload_many's), only the slot pointers and the bodies
+    // (16 B per block) staged through the upload buffer, the masks regenerated by seeded.hip into the
+    // slots -- word for word expand_seeded_host's output.  Stream-ordered like an upload: the slots are
+    // new, so nothing recorded in the deferred graph reads them; no flush, and a pending upload_deferred
+    // stays pending (it stages its own data when it runs).  Device engines only: the host modes (kDry,
+    // kSim, kHostFold) refuse, as they have no ciphertexts to expand into.  Issues no collective: it is
+    // deterministic and rank-local, so under an attached communicator EVERY rank must expand the same
+    // bytes (the fan-out's identical-inputs rule).
+    Blocks expand_seeded(const uint8_t seed[32], const uint64_t* bodies, size_t n);
     void download(const Block& b, uint64_t* ct);
     // the slot blocks' ciphertexts -> host, contiguous (one gather + one copy + one wait instead of a
     // round trip per block: the decryption of a 256-bit result is 128-144 blocks)

@@ -8,6 +8,10 @@
 //   payload params (9 x u32: n, pbs_base_log, ks_base_log, ks_level, lwe/glwe noise log2, msg,
 //           carry, grouping -- version 1 has no grouping word: classic) then the kind's fields
 //           (serial.cpp / capi_radix.cpp).
+//   kind 5 (seeded ciphertext, capi_radix.cpp): params | u32 form (0 radix, 1 BigUintFHE) | u32 count
+//           (num_bits, or nlimbs) | 32 seed bytes | nblocks u64 bodies (nblocks = num_bits / 2, or
+//           16 nlimbs; LSB block first).  The masks are not stored: block i's are u64 words [2048 i,
+//           2048 (i + 1)) of the ChaCha20 stream keyed by the seed, nonce {101, "ROCM", 0} (keys.h).
 // Readers check magic, version, kind, length, checksum, parameter ranges and every count before
 // touching memory, and refuse block metadata (degree, noise) outside the radix layer's budget, so a
 // corrupted or hostile buffer fails with FHE_ERR_INVALID instead of poisoning the scheduler.
@@ -22,7 +26,7 @@
 
 namespace fhe::ser {
 
-enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4 };
+enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4, kSeeded = 5 };
 constexpr uint32_t kVersion = 2;  // 2: params carry the blind-rotation grouping (9th word); 1 still read
 constexpr size_t kHeaderBytes = 32;
 

@@ -185,6 +185,15 @@ _SIGNATURES = [
     ("fhe_biguint_add", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("fhe_biguint_mul", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("fhe_biguint_mul_add", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fhe_radix_encrypt_seeded", C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("fhe_biguint_encrypt_seeded", C.c_int, [C.c_void_p, u32p, C.c_size_t, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_info", C.c_int, [C.c_void_p, u32p, u32p, C.POINTER(C.c_size_t)]),
+    ("fhe_seeded_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_seeded_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_expand_host", C.c_int, [C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_seeded_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_destroy", None, [C.c_void_p]),
     ("fhe_schnorr_public_key", C.c_int, [u8p, u8p]),
     ("fhe_schnorr_compute_nonce", C.c_int, [u8p, u8p, C.c_size_t, u8p, u8p]),
     ("fhe_schnorr_sign_with_k0", C.c_int, [u8p, C.c_size_t, u8p, u8p, u8p]),

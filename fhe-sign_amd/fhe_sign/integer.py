@@ -13,7 +13,7 @@ import threading
 
 import numpy as np
 
-from ._lib import check, load, ptr, serialize_with
+from ._lib import FheError, check, load, ptr, serialize_with
 
 COMPAT = 0  # exact replay of src/biguint.rs:214-254 incl. the wrapping add at :247-249
 FAST = 1    # true product/sum, single wide carry propagation
@@ -399,6 +399,143 @@ class BigUintFHE:
 
     __add__ = add
     __mul__ = mul
+
+
+SEEDED_RADIX, SEEDED_BIGUINT = 0, 1  # FHE_SEEDED_*
+
+
+def _mask_seed(seed):
+    """the C ABI's mask_seed argument: None (32 bytes of OS entropy, drawn by the engine) or 32 bytes"""
+    if seed is None:
+        return None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a mask seed is 32 bytes")
+    return seed
+
+
+class _Seeded:
+    """fhe_seeded: a public mask seed and one body word per block, on the host (no context).  A seed is
+    PUBLIC and must never serve two objects under one client key; leave `seed` None outside tests."""
+    FORM = None
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_seeded_destroy(self._h)
+            self._h = None
+
+    def _info(self):
+        form, count, nb = C.c_uint32(), C.c_uint32(), C.c_size_t()
+        check(load().fhe_seeded_info(self._h, C.byref(form), C.byref(count), C.byref(nb)))
+        return int(form.value), int(count.value), int(nb.value)
+
+    @property
+    def nblocks(self) -> int:
+        return self._info()[2]
+
+    def serialize(self) -> bytes:
+        """about 108 + 8 bytes per block (own format, include/fhe_rocm.h)"""
+        return serialize_with(load().fhe_seeded_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes):
+        h = C.c_void_p()
+        check(load().fhe_seeded_deserialize(data, len(data), C.byref(h)))
+        obj = _Seeded(h)
+        form = obj._info()[0]
+        if cls.FORM is not None and form != cls.FORM:
+            raise FheError(f"{cls.__name__}.deserialize: the bytes hold the other seeded form", -1)
+        obj.__class__ = CompressedBigUintFHE if form == SEEDED_BIGUINT else CompressedFheUint._kind(obj._info()[1])
+        return obj
+
+    def expand_host(self) -> np.ndarray:
+        """the full ciphertexts, (nblocks, 2049): masks regenerated on the host, body appended -- the
+        definition of what decompress() puts on the GPU"""
+        nb = self.nblocks
+        out = np.zeros((nb, 2049), np.uint64)
+        check(load().fhe_seeded_expand_host(self._h, ptr(out), out.size))
+        return out
+
+
+class CompressedFheUint(_Seeded):
+    """tfhe-rs' CompressedFheUint: try_encrypt on the client (no context), decompress on the server"""
+    FORM = SEEDED_RADIX
+    BITS = 0
+
+    @staticmethod
+    def _kind(bits):
+        return {32: CompressedFheUint32, 64: CompressedFheUint64, 128: CompressedFheUint128,
+                256: CompressedFheUint256, 8: CompressedFheUint8}.get(bits, CompressedFheUint)
+
+    @property
+    def bits(self) -> int:
+        return self._info()[1]
+
+    @classmethod
+    def try_encrypt(cls, value: int, client_key, bits=None, seed=None):
+        bits = bits or cls.BITS
+        w = _words(value, bits)
+        h = C.c_void_p()
+        check(load().fhe_radix_encrypt_seeded(client_key.handle, ptr(w), bits, _mask_seed(seed), C.byref(h)))
+        obj = cls._kind(bits).__new__(cls._kind(bits))
+        _Seeded.__init__(obj, h)
+        return obj
+
+    encrypt = try_encrypt
+
+    def decompress(self):
+        """the matching FheUint on this thread's context (masks regenerated on the GPU)"""
+        h = C.c_void_p()
+        check(load().fhe_seeded_expand_radix(_ctx().handle, self._h, C.byref(h)))
+        return FheUint._wrap(h, self.bits)
+
+
+class CompressedFheUint8(CompressedFheUint):
+    BITS = 8
+
+
+class CompressedFheUint32(CompressedFheUint):
+    BITS = 32
+
+
+class CompressedFheUint64(CompressedFheUint):
+    BITS = 64
+
+
+class CompressedFheUint128(CompressedFheUint):
+    BITS = 128
+
+
+class CompressedFheUint256(CompressedFheUint):
+    BITS = 256
+
+
+class CompressedBigUintFHE(_Seeded):
+    """BigUintFHE::new (src/biguint.rs:17-31) in the seeded form: 16 blocks per u32 limb"""
+    FORM = SEEDED_BIGUINT
+
+    @classmethod
+    def new(cls, value: int, client_key, seed=None):
+        limbs = np.array(to_u32_digits(value), dtype=np.uint32)
+        h = C.c_void_p()
+        check(load().fhe_biguint_encrypt_seeded(client_key.handle, ptr(limbs, C.c_uint32), limbs.size, _mask_seed(seed),
+                                                C.byref(h)))
+        return cls(h)
+
+    def __len__(self):
+        return self._info()[1]
+
+    def decompress(self) -> BigUintFHE:
+        h = C.c_void_p()
+        check(load().fhe_seeded_expand_biguint(_ctx().handle, self._h, C.byref(h)))
+        return BigUintFHE(h)
 
 
 LEVEL_SPLIT = 1 << 31  # FHE_LEVEL_SPLIT: the level was fanned out over the ranks

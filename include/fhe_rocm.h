@@ -478,6 +478,52 @@ void fhe_columns_destroy(fhe_columns* x);
 int fhe_biguint_serialize(fhe_ctx* ctx, const fhe_biguint* x, uint8_t* buf, size_t cap, size_t* len);
 int fhe_biguint_deserialize(fhe_ctx* ctx, const uint8_t* buf, size_t len, fhe_biguint** out);
 
+/* ------------------------------------------------- seeded (compressed) ciphertexts */
+/* A fresh ciphertext is 2049 words per block, of which the 2048 mask words are uniformly random and
+ * carry no information: a 256-bit value is 128 x 16,392 B = 2.1 MB.  The seeded form keeps a PUBLIC
+ * 32-byte mask seed and one body word per block (about 1.1 KB for 256 bits); whoever holds it
+ * regenerates the masks.  tfhe-rs' CompressedFheUint32::try_encrypt(..) / .decompress().  The handle
+ * lives on the host and needs no context; the parameter set travels with it.
+ *   masks   block i's 2048 mask words = u64 words [2048 i, 2048 (i + 1)) of the ChaCha20 stream whose key
+ *           is the 32 seed bytes (little-endian words) and whose nonce is {101, "ROCM", 0} (the key
+ *           streams' layout, block counter 256 i); it shares nothing with the client key's streams
+ *   bodies  body_i = <mask_i, big key> + delta m_i + e_i, e_i drawn from the next 64-bit word of the client
+ *           key's encryption stream: one word per block, so a serialized client key continues correctly
+ * THE SEED IS PUBLIC AND MUST NEVER BE USED FOR TWO OBJECTS UNDER ONE CLIENT KEY: equal masks make the
+ * difference of two bodies delta (m - m') + e - e', which leaks the difference of the messages.  Pass
+ * mask_seed = NULL (32 bytes from getrandom()) outside tests.  An object holds at most 2^24 blocks
+ * (the stream's 32-bit block counter); more is FHE_ERR_INVALID. */
+typedef struct fhe_seeded fhe_seeded;
+#define FHE_SEEDED_RADIX 0
+#define FHE_SEEDED_BIGUINT 1
+/* CompressedFheUint::try_encrypt: words little-endian, num_bits as fhe_radix_encrypt */
+int fhe_radix_encrypt_seeded(fhe_client_key* ck, const uint64_t* words, uint32_t num_bits,
+                             const uint8_t mask_seed[32] /* NULL: OS entropy */, fhe_seeded** out);
+/* the same for BigUintFHE::new (limbs as fhe_biguint_encrypt; nlimbs 0 is the empty vector, 0 blocks) */
+int fhe_biguint_encrypt_seeded(fhe_client_key* ck, const uint32_t* limbs, size_t nlimbs,
+                               const uint8_t mask_seed[32] /* NULL: OS entropy */, fhe_seeded** out);
+/* form (FHE_SEEDED_*), count (num_bits or nlimbs) and blocks; any output may be NULL */
+int fhe_seeded_info(const fhe_seeded* x, uint32_t* form, uint32_t* count, size_t* nblocks);
+/* Wire format (kind 5 of the keys' framed, checksummed format; size-query convention as above):
+ * params, u32 form, u32 count, 32 seed bytes, nblocks u64 bodies -- 108 + 8 nblocks bytes.  The
+ * reader checks magic, version, kind, length, checksum, parameter ranges, the form, num_bits (even,
+ * <= FHE_RADIX_MAX_BITS) and that the block count matches the payload length and is <= 2^24, all
+ * before it allocates.  tfhe-rs' wire format of compressed types is not reproduced (parity unpinned). */
+int fhe_seeded_serialize(const fhe_seeded* x, uint8_t* buf, size_t cap, size_t* len);
+int fhe_seeded_deserialize(const uint8_t* buf, size_t len, fhe_seeded** out);
+/* CompressedFheUint::decompress on the host: cts = nblocks x 2049 words (masks regenerated, body
+ * appended), nwords >= that.  The word-for-word definition of the GPU expansion, and what a client
+ * without a GPU uses. */
+int fhe_seeded_expand_host(const fhe_seeded* x, uint64_t* cts, size_t nwords);
+/* CompressedFheUint::decompress on the GPU of ctx: fresh block slots whose masks a gfx950 kernel
+ * regenerates (only seed and bodies cross the bus), stream-ordered like fhe_radix_encrypt's upload.
+ * FHE_ERR_NO_KEY without an installed server key; FHE_ERR_INVALID for the other form, and for parameters
+ * that differ from the installed key's (the message names the field), before anything is launched.  No
+ * collective is issued: under the multi-GPU fan-out every rank must expand the same bytes. */
+int fhe_seeded_expand_radix(fhe_ctx* ctx, const fhe_seeded* x, fhe_radix** out);
+int fhe_seeded_expand_biguint(fhe_ctx* ctx, const fhe_seeded* x, fhe_biguint** out);
+void fhe_seeded_destroy(fhe_seeded* x);
+
 /* ------------------------------------------------------------------- Schnorr / BIP-340 */
 /* The caller of the hot path (src/schnorr.rs).  32-byte scalars are big-endian.  The plaintext
  * EC / hash steps run on the host; the FHE block s = k + e*d runs on the GPU engine. */
