@@ -9,8 +9,6 @@
 
 #include <future>
 
-#include <sys/random.h>
-
 #include "biguint.h"
 #include "fhe_rocm.h"
 #include "serial.h"
@@ -1325,13 +1323,9 @@ int seeded_encrypt(fhe_client_key* ck, uint32_t form, uint32_t count, const std:
         if (mask_seed) {
             std::memcpy(x->seed, mask_seed, 32);
         } else {
-            for (size_t got = 0; got < 32;) {
-                const ssize_t k = getrandom(x->seed + got, 32 - got, 0);
-                if (k <= 0) {
-                    set_error("getrandom failed: no mask seed");
-                    return FHE_ERR_UNSUPPORTED;
-                }
-                got += (size_t)k;
+            if (!os_entropy32(x->seed)) {
+                set_error("getrandom failed: no mask seed");
+                return FHE_ERR_UNSUPPORTED;
             }
         }
         x->bodies.resize(pts.size());

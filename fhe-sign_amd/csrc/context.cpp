@@ -595,39 +595,37 @@ void fhe_ctx_destroy(fhe_ctx* c) {
     delete c;
 }
 
-int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
-    if (!c || !sk) return FHE_ERR_INVALID;
-    FHE_HIP_CHECK(hipSetDevice(c->device));
-    const Params& p = sk->params;
-    const bool had_key = c->has_key;
-    if (c->has_key) {
-        FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
-        FHE_HIP_CHECK(hipFree(c->d_ksk));
-        FHE_HIP_CHECK(hipFree(c->d_bsk));
-        FHE_HIP_CHECK(hipFree(c->d_bsk_e));
-        FHE_HIP_CHECK(hipFree(c->d_ksk_planes));
-        c->d_ksk_planes = nullptr;
-        c->d_ksk = nullptr;
-        c->d_bsk = nullptr;
-        c->d_bsk_e = nullptr;
-        c->has_key = false;
-    }
-    FHE_HIP_CHECK(hipMalloc(&c->d_ksk, sk->ksk.size() * 8));
-    FHE_HIP_CHECK(hipMemcpyAsync(c->d_ksk, sk->ksk.data(), sk->ksk.size() * 8, hipMemcpyHostToDevice, c->stream));
+namespace {
+struct DeviceFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+// The two ends every key install shares.  release_key: the stream is drained and the previous key's
+// buffers are freed -- from here until install_tail succeeds the context has no key.
+int release_key(fhe_ctx* c) {
+    if (!c->has_key) return FHE_OK;
+    FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+    FHE_HIP_CHECK(hipFree(c->d_ksk));
+    FHE_HIP_CHECK(hipFree(c->d_bsk));
+    FHE_HIP_CHECK(hipFree(c->d_bsk_e));
+    FHE_HIP_CHECK(hipFree(c->d_ksk_planes));
+    c->d_ksk_planes = nullptr;
+    c->d_ksk = nullptr;
+    c->d_bsk = nullptr;
+    c->d_bsk_e = nullptr;
+    c->has_key = false;
+    return FHE_OK;
+}
+// install_tail: d_ksk and the Fourier d_bsk are filled (or being filled on the stream); derive the byte
+// planes and the E layout, wait, adopt the parameters, create the engine.
+int install_tail(fhe_ctx* c, const Params& p, bool had_key) {
+    const int npoly = (int)(p.ggsw_count() * 4);
     FHE_HIP_CHECK(hipMalloc(&c->d_ksk_planes, fhe::ks_planes_bytes((int)p.n)));
     FHE_HIP_CHECK(launch_ksk_to_planes(c->d_ksk, (int)p.n, c->d_ksk_planes, c->stream));
-    const int npoly = (int)(p.ggsw_count() * 4);
-    uint64_t* d_std = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&d_std, sk->bsk.size() * 8));
-    FHE_HIP_CHECK(hipMalloc(&c->d_bsk, (size_t)npoly * 1024 * sizeof(double2)));
-    FHE_HIP_CHECK(hipMemcpyAsync(d_std, sk->bsk.data(), sk->bsk.size() * 8, hipMemcpyHostToDevice, c->stream));
-    FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, npoly, c->d_W, c->d_psi, c->d_bsk, c->stream));
     // two resident layouts: d_bsk for the latency kernel (br_wide.hip), d_bsk_e for the throughput
     // kernel (br_qy.hip); rounds 1-4 also kept br_quad.hip's and ran br_qx.hip (both retired in r5)
     FHE_HIP_CHECK(hipMalloc(&c->d_bsk_e, (size_t)npoly * 1024 * sizeof(double2)));
     FHE_HIP_CHECK(launch_bsk_to_e(c->d_bsk, npoly, c->d_bsk_e, c->stream));
     FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
-    FHE_HIP_CHECK(hipFree(d_std));
     // the LUT tables survive a re-key with the same message space and delta (ids stay valid)
     const int rc = c->adopt_key_params(p, had_key);
     if (rc) return rc;
@@ -640,6 +638,64 @@ int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
         }
     }
     return FHE_OK;
+}
+}  // namespace
+
+int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
+    if (!c || !sk) return FHE_ERR_INVALID;
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    const Params& p = sk->params;
+    const bool had_key = c->has_key;
+    int rc = release_key(c);
+    if (rc) return rc;
+    FHE_HIP_CHECK(hipMalloc(&c->d_ksk, sk->ksk.size() * 8));
+    FHE_HIP_CHECK(hipMemcpyAsync(c->d_ksk, sk->ksk.data(), sk->ksk.size() * 8, hipMemcpyHostToDevice, c->stream));
+    const int npoly = (int)(p.ggsw_count() * 4);
+    uint64_t* d_std = nullptr;
+    FHE_HIP_CHECK(hipMalloc(&d_std, sk->bsk.size() * 8));
+    std::unique_ptr<void, DeviceFree> std_guard(d_std);  // freed behind install_tail's wait
+    FHE_HIP_CHECK(hipMalloc(&c->d_bsk, (size_t)npoly * 1024 * sizeof(double2)));
+    FHE_HIP_CHECK(hipMemcpyAsync(d_std, sk->bsk.data(), sk->bsk.size() * 8, hipMemcpyHostToDevice, c->stream));
+    FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, npoly, c->d_W, c->d_psi, c->d_bsk, c->stream));
+    return install_tail(c, p, had_key);
+}
+
+// The seeded install: the bodies are the only upload (82 KB + half of the standard-domain BSK, which is
+// never allocated); seeded_key.hip regenerates the KSK masks in place and the BSK mask polynomials inside
+// the Fourier conversion.  Same device state as fhe_set_server_key of the host-expanded key.
+int fhe_set_server_key_seeded(fhe_ctx* c, const fhe_seeded_server_key* ssk) {
+    if (!c || !ssk) return FHE_ERR_INVALID;
+    const Params& p = ssk->params;
+    Params checked;
+    const char* why = nullptr;
+    if (!Params::from_c(p.to_c(), &checked, &why) || !seeded_key_rows_ok(p, &why) ||
+        ssk->ksk_bodies.size() != (size_t)kPolySize * p.ks_level ||
+        ssk->bsk_bodies.size() != (size_t)p.ggsw_count() * 2 * kPolySize) {
+        set_error(why ? why : "seeded server key: body counts differ from what its parameters need");
+        return FHE_ERR_UNSUPPORTED;
+    }
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    const bool had_key = c->has_key;
+    int rc = release_key(c);
+    if (rc) return rc;
+    const KeyWords key = bytes_key(ssk->seed);
+    const int rows = (int)(kPolySize * p.ks_level), npoly = (int)(p.ggsw_count() * 4);
+    uint64_t *d_kb = nullptr, *d_bb = nullptr;
+    FHE_HIP_CHECK(hipMalloc(&d_kb, ssk->ksk_bodies.size() * 8));
+    std::unique_ptr<void, DeviceFree> kb_guard(d_kb);  // both freed behind install_tail's wait
+    FHE_HIP_CHECK(hipMalloc(&d_bb, ssk->bsk_bodies.size() * 8));
+    std::unique_ptr<void, DeviceFree> bb_guard(d_bb);
+    FHE_HIP_CHECK(hipMalloc(&c->d_ksk, (size_t)rows * (p.n + 1) * 8));
+    FHE_HIP_CHECK(hipMalloc(&c->d_bsk, (size_t)npoly * 1024 * sizeof(double2)));
+    FHE_HIP_CHECK(hipMemcpyAsync(d_kb, ssk->ksk_bodies.data(), ssk->ksk_bodies.size() * 8, hipMemcpyHostToDevice,
+                                 c->stream));
+    FHE_HIP_CHECK(launch_expand_ksk(chacha_stream_key(key.data(), kStreamSeededKsk), c->d_ksk, d_kb, rows, (int)p.n,
+                                    c->stream));
+    FHE_HIP_CHECK(hipMemcpyAsync(d_bb, ssk->bsk_bodies.data(), ssk->bsk_bodies.size() * 8, hipMemcpyHostToDevice,
+                                 c->stream));
+    FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededBsk), d_bb, npoly, c->d_W,
+                                            c->d_psi, c->d_bsk, c->stream));
+    return install_tail(c, p, had_key);
 }
 
 int fhe_ctx_export_fourier_bsk(fhe_ctx* c, double* out, size_t len) {
@@ -729,9 +785,6 @@ hipError_t copy_small(fhe_ctx* c, uint64_t* small, size_t count) {
     return hipMemcpy2DAsync(small, row, c->d_ms, (size_t)c->ms_stride * 8, row, count, hipMemcpyDeviceToHost,
                             c->stream);
 }
-struct DeviceFree {
-    void operator()(void* p) const { (void)hipFree(p); }
-};
 }  // namespace
 
 int fhe_keyswitch_batch(fhe_ctx* c, const uint64_t* in, size_t count, uint64_t* small) {

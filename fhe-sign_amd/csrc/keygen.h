@@ -19,6 +19,15 @@ hipError_t launch_chacha_u64(const ChaChaKey& k, uint64_t* out, uint64_t count, 
 // bodies are device arrays, every dst[b] a slot of 2049 words
 hipError_t launch_expand_seeded(const ChaChaKey& k, uint64_t* const* dst, const uint64_t* bodies, int nblocks,
                                 hipStream_t s);
+// seeded_key.hip: for r < rows, ksk[r (n + 1) + t] = u64 word 2048 r + t of the stream for t < n (n <= 2048)
+// and ksk[r (n + 1) + n] = bodies[r]; nothing else is written
+hipError_t launch_expand_ksk(const ChaChaKey& k, uint64_t* ksk, const uint64_t* bodies, int rows, int n,
+                             hipStream_t s);
+// seeded_key.hip: launch_bsk_to_fourier (kernels.h) of the standard-domain key whose polynomial 2 r is u64
+// words [2048 r, 2048 r + 2048) of the stream and whose polynomial 2 r + 1 is bodies[2048 r ..], without
+// that key in memory; npoly = 4 ggsw, bodies holds npoly / 2 polynomials
+hipError_t launch_expand_bsk_fourier(const ChaChaKey& k, const uint64_t* bodies, int npoly, const double2* W,
+                                     const double2* psi, double2* out, hipStream_t s);
 // ksk holds the KSK stream words ([rows][n + 1], rows = N * levels): bodies computed in place
 hipError_t launch_ksk_bodies(uint64_t* ksk, const uint64_t* lwe_sk, const uint64_t* glwe_sk, int n, int rows,
                              int levels, int base_log, int noise_log2, hipStream_t s);

@@ -6,6 +6,8 @@
 // consumes the server key produced here.
 #include "keys.h"
 
+#include <sys/random.h>
+
 #include <algorithm>
 #include <cstring>
 #include <thread>
@@ -95,6 +97,15 @@ KeyWords bytes_key(const uint8_t* b) {
         k[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 |
                (uint32_t)b[4 * i + 3] << 24;
     return k;
+}
+
+bool os_entropy32(uint8_t out[32]) {
+    for (size_t got = 0; got < 32;) {
+        const ssize_t k = getrandom(out + got, 32 - got, 0);
+        if (k <= 0) return false;
+        got += (size_t)k;
+    }
+    return true;
 }
 
 void ChaChaStream::reset(const KeyWords& key, uint32_t stream) {
@@ -316,6 +327,94 @@ void generate_keys(const Params& p, const KeyWords& seed, fhe_client_key* ck, fh
             }
         });
     for (auto& th : pool) th.join();
+}
+
+// ------------------------------------------------------------------------------ seeded server key
+namespace {
+constexpr uint64_t kRowWords = 2048;  // u64 words between two rows' first mask words (256 ChaCha blocks)
+// fn(row, masks) for row < rows on generate_keys' pool (at most 16 threads, rows interleaved); each
+// thread owns a mask stream, seeked to a row's first word before fn runs
+template <class F>
+void seeded_key_rows(const KeyWords& key, uint32_t stream, uint32_t rows, F&& fn) {
+    unsigned nth = std::thread::hardware_concurrency();
+    if (nth == 0) nth = 4;
+    if (nth > 16) nth = 16;
+    if (nth > rows) nth = rows ? rows : 1;
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < nth; ++t)
+        pool.emplace_back([&, t] {
+            ChaChaStream masks(key, stream);
+            for (uint32_t r = t; r < rows; r += nth) {
+                masks.seek((uint64_t)r * kRowWords * 2);  // in 32-bit stream words
+                fn(r, masks);
+            }
+        });
+    for (auto& th : pool) th.join();
+}
+}  // namespace
+
+bool seeded_key_rows_ok(const Params& p, const char** why) {
+    if ((uint64_t)kPolySize * p.ks_level > kSeededMaxBlocks || 2ull * p.ggsw_count() > kSeededMaxBlocks ||
+        p.n > kRowWords) {
+        *why = "seeded server key: more rows than a mask stream's 32-bit block counter addresses";
+        return false;
+    }
+    return true;
+}
+
+void generate_seeded_server_key(fhe_client_key* ck, const uint8_t seed[32], fhe_seeded_server_key* out) {
+    const Params& p = ck->params;
+    const uint32_t n = p.n, N = kPolySize, L = p.ks_level, ngg = p.ggsw_count();
+    const uint32_t krows = N * L, brows = ngg * 2;
+    out->params = p;
+    std::memcpy(out->seed, seed, 32);
+    // the noise words first: the encryption stream advances by exactly krows + brows N words
+    out->ksk_bodies.resize(krows);
+    out->bsk_bodies.resize((size_t)brows * N);
+    ck->enc_rng.fill_u64(out->ksk_bodies.data(), krows);
+    ck->enc_rng.fill_u64(out->bsk_bodies.data(), (size_t)brows * N);
+    const KeyWords key = bytes_key(seed);
+    const uint64_t *s = ck->lwe_sk.data(), *S = ck->glwe_sk.data();
+    seeded_key_rows(key, kStreamSeededKsk, krows, [&](uint32_t r, ChaChaStream& masks) {
+        std::vector<uint64_t> a(n);
+        masks.fill_u64(a.data(), n);
+        uint64_t dot = 0;
+        for (uint32_t t = 0; t < n; ++t) dot += a[t] * s[t];
+        const uint32_t j = r / L, l = r % L;
+        const int64_t e = tuniform_of(out->ksk_bodies[r], p.lwe_noise_log2);
+        out->ksk_bodies[r] = dot + (S[j] << (64 - p.ks_base_log * (l + 1))) + (uint64_t)e;
+    });
+    seeded_key_rows(key, kStreamSeededBsk, brows, [&](uint32_t r, ChaChaStream& masks) {
+        std::vector<uint64_t> A(N);
+        masks.fill_u64(A.data(), N);
+        uint64_t* B = out->bsk_bodies.data() + (size_t)r * N;
+        for (uint32_t m = 0; m < N; ++m) B[m] = (uint64_t)tuniform_of(B[m], p.glwe_noise_log2);
+        negacyclic_binary_mac(B, A.data(), S);
+        const uint64_t g = p.ggsw_message(s, r / 2) << (64 - p.pbs_base_log);
+        if (r % 2)
+            B[0] += g;
+        else
+            for (uint32_t t = 0; t < N; ++t) B[t] -= g * S[t];
+    });
+}
+
+void expand_seeded_server_key_host(const fhe_seeded_server_key& ssk, fhe_server_key* sk) {
+    const Params& p = ssk.params;
+    const uint32_t n = p.n, N = kPolySize, krows = N * p.ks_level, brows = p.ggsw_count() * 2;
+    sk->params = p;
+    sk->ksk.assign((size_t)krows * (n + 1), 0);
+    sk->bsk.assign((size_t)brows * 2 * N, 0);
+    const KeyWords key = bytes_key(ssk.seed);
+    seeded_key_rows(key, kStreamSeededKsk, krows, [&](uint32_t r, ChaChaStream& masks) {
+        uint64_t* row = sk->ksk.data() + (size_t)r * (n + 1);
+        masks.fill_u64(row, n);
+        row[n] = ssk.ksk_bodies[r];
+    });
+    seeded_key_rows(key, kStreamSeededBsk, brows, [&](uint32_t r, ChaChaStream& masks) {
+        uint64_t* A = sk->bsk.data() + (size_t)r * 2 * N;
+        masks.fill_u64(A, N);
+        std::memcpy(A + N, ssk.bsk_bodies.data() + (size_t)r * N, (size_t)N * 8);
+    });
 }
 
 static void encrypt_with(ChaChaStream& rng, const fhe_client_key* ck, uint64_t pt, uint64_t* ct) {

@@ -53,6 +53,8 @@ struct Params {
 using KeyWords = std::array<uint32_t, 8>;
 KeyWords seed_key(uint64_t seed);
 KeyWords bytes_key(const uint8_t* key32);  // little-endian words
+// 32 bytes from getrandom(): the default public mask seed of the seeded objects below; false if it fails
+bool os_entropy32(uint8_t out[32]);
 
 // ChaCha20 block function (RFC 8439) as a deterministic stream of 64-bit words.
 class ChaChaStream {
@@ -94,6 +96,11 @@ enum : uint32_t { kStreamSecret = 1, kStreamKsk = 2, kStreamBsk = 3, kStreamEncr
 constexpr uint32_t kStreamSeededMask = 101;
 // The ChaCha block counter is 32 bits and one radix block takes 256 ChaCha blocks of masks.
 constexpr uint64_t kSeededMaxBlocks = 1ull << 24;
+// Mask streams of a seeded server key (fhe_seeded_server_key below), keyed by its PUBLIC seed as well.  A
+// row (one KSK row, one BSK mask polynomial) starts on a stride of 256 ChaCha blocks = 2048 u64 words, as
+// a seeded ciphertext's block does, so row r's words are [2048 r, 2048 r + 2048) whatever n is.
+constexpr uint32_t kStreamSeededKsk = 102;
+constexpr uint32_t kStreamSeededBsk = 103;
 
 }  // namespace fhe
 
@@ -122,8 +129,36 @@ struct fhe_server_key {
     std::vector<uint64_t> bsk;  // [n][row][poly][N] standard domain
 };
 
+// A seeded (compressed) server key: tfhe-rs' CompressedServerKey.  Host only.  Of the full key only the
+// bodies are kept; every mask word is regenerated from the PUBLIC seed:
+//   KSK row r = j ks_level + l: mask word t < n = u64 word 2048 r + t of ChaChaStream(bytes_key(seed),
+//       kStreamSeededKsk); ksk_bodies[r] = <mask, lwe_sk> + (S_j << (64 - ks_base_log (l + 1))) + e
+//   BSK GGSW q, row rho: mask polynomial A = u64 words [2048 (2 q + rho), + 2048) of stream kStreamSeededBsk;
+//       bsk_bodies[(2 q + rho) 2048 ..] = B = A * S + e, then row 1: B[0] += g m_q; row 0: B[t] -= g m_q S_t
+//       for every t (g = 1 << (64 - pbs_base_log)).  generate_keys puts row 0's gadget into the mask
+//       (A[0] += g); a mask that comes from a seed cannot hold it, and the phase B - A * S = e - g m_q S is
+//       the same, so every kernel consumes the expanded key unchanged.
+// One seed, one object: a seed is never reused for a second key, or for a seeded ciphertext, under the
+// same client key.
+struct fhe_seeded_server_key {
+    fhe::Params params;
+    uint8_t seed[32] = {};
+    std::vector<uint64_t> ksk_bodies;  // [N * ks_level]
+    std::vector<uint64_t> bsk_bodies;  // [ggsw][row][N]
+};
+
 namespace fhe {
 void generate_keys(const Params& p, const KeyWords& key, fhe_client_key* ck, fhe_server_key* sk);
+// The seeded server key of ck under the public `seed`.  Noise: exactly N ks_level + ggsw 2 N words of
+// ck->enc_rng, the KSK rows' first (row order), then the BSK's in (q, rho, m) order, all drawn before the
+// threaded pass: e = tuniform_of(w, lwe_noise_log2) (KSK) / tuniform_of(w, glwe_noise_log2) (BSK).
+void generate_seeded_server_key(fhe_client_key* ck, const uint8_t seed[32], fhe_seeded_server_key* out);
+// The full key of a seeded one: masks regenerated, bodies in place.  The word-for-word definition of the
+// device install (seeded_key.hip).
+void expand_seeded_server_key_host(const fhe_seeded_server_key& ssk, fhe_server_key* sk);
+// false (with a reason) if a key of these parameters has more rows than the 32-bit block counter of a
+// mask stream addresses; Params::from_c admits no such set, readers and the install check anyway
+bool seeded_key_rows_ok(const Params& p, const char** why);
 // the client-key half of generate_keys (secret keys, encryption stream); the device keygen
 // (context.cpp: fhe_generate_keys_device) uses it and derives the server key on the GPU
 void generate_secret_keys(const Params& p, const KeyWords& key, fhe_client_key* ck);

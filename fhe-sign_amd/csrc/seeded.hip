@@ -25,17 +25,11 @@ namespace fhe {
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // a slot is only 8-byte aligned; the slot pointers are loaded from memory, so the compiler cannot prove
 // them global and would emit flat stores: say so
 typedef __attribute__((address_space(1))) u32x4 g_u32x4_a8 __attribute__((aligned(8)));
 typedef __attribute__((address_space(1))) uint8_t g_u8;
 typedef __attribute__((address_space(1))) uint64_t g_u64;
-
-__device__ __forceinline__ uint32_t sel4(uint32_t i, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    const uint32_t lo = (i & 1) ? b : a, hi = (i & 1) ? d : c;
-    return (i & 2) ? hi : lo;
-}
 
 __global__ __launch_bounds__(256) void k_expand_seeded(ChaChaKey k, uint64_t* const* __restrict__ dst,
                                                        const uint64_t* __restrict__ bodies) {
@@ -45,28 +39,11 @@ __global__ __launch_bounds__(256) void k_expand_seeded(ChaChaKey k, uint64_t* co
     const uint32_t p = lane & 3, q = lane >> 2;
     uint32_t o[16];
     chacha_block(k, b * 256u + wave * 64u + p * 16u + q, o);
-    // y[r] = part p (words 4 p .. 4 p + 3) of the block held by quad position p ^ r
-    uint32_t y[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const uint32_t j = p ^ r;  // the part the partner needs from this lane
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t v = sel4(j, o[i], o[4 + i], o[8 + i], o[12 + i]);
-            y[r][i] = r ? (uint32_t)__shfl_xor((int)v, r, 4) : v;
-        }
-    }
+    u32x4 w[4];
+    chacha_quad_exchange(o, p, w);
     g_u8* base = (g_u8*)slot + wave * 4096u + lane * 16u;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {  // store s: the block of quad position s = y[p ^ s]
-        const uint32_t r = p ^ (uint32_t)s;
-        u32x4 w;
-        w.x = sel4(r, y[0][0], y[1][0], y[2][0], y[3][0]);
-        w.y = sel4(r, y[0][1], y[1][1], y[2][1], y[3][1]);
-        w.z = sel4(r, y[0][2], y[1][2], y[2][2], y[3][2]);
-        w.w = sel4(r, y[0][3], y[1][3], y[2][3], y[3][3]);
-        *(g_u32x4_a8*)(base + s * 1024) = w;
-    }
+    for (int s = 0; s < 4; ++s) *(g_u32x4_a8*)(base + s * 1024) = w[s];
     if (threadIdx.x == 0) ((g_u64*)slot)[2048] = bodies[b];
 }
 

@@ -2,6 +2,7 @@
 #include "serial.h"
 
 #include <cstring>
+#include <memory>
 #include <new>
 
 #include "context.h"
@@ -222,5 +223,101 @@ int fhe_server_key_deserialize(const uint8_t* buf, size_t len, fhe_server_key** 
     *out = sk;
     return FHE_OK;
 }
+
+// ------------------------------------------------------------------------- seeded server key
+// tfhe-rs' CompressedServerKey (keys.h fhe_seeded_server_key).  Payload of kSeededServerKey: params, 32
+// seed bytes, the KSK bodies, the BSK body polynomials; no counts -- the parameters fix them, and the
+// reader holds the payload length to exactly that before it allocates.
+int fhe_server_key_generate_seeded(fhe_client_key* ck, const uint8_t* mask_seed, fhe_seeded_server_key** out) {
+    if (!ck || !out) return fail("null argument");
+    const char* why = nullptr;
+    if (!seeded_key_rows_ok(ck->params, &why)) {
+        set_error(why);
+        return FHE_ERR_UNSUPPORTED;
+    }
+    uint8_t seed[32];
+    if (mask_seed) {
+        std::memcpy(seed, mask_seed, 32);
+    } else {
+        if (!os_entropy32(seed)) {
+            set_error("getrandom failed: no mask seed");
+            return FHE_ERR_UNSUPPORTED;
+        }
+    }
+    try {
+        std::unique_ptr<fhe_seeded_server_key> s(new fhe_seeded_server_key());
+        generate_seeded_server_key(ck, seed, s.get());
+        *out = s.release();
+    } catch (const std::exception& e) {
+        set_error(std::string("seeded keygen failed: ") + e.what());
+        return FHE_ERR_ALLOC;
+    }
+    return FHE_OK;
+}
+
+int fhe_seeded_server_key_params(const fhe_seeded_server_key* ssk, fhe_params* out) {
+    if (!ssk || !out) return FHE_ERR_INVALID;
+    *out = ssk->params.to_c();
+    return FHE_OK;
+}
+
+int fhe_seeded_server_key_serialize(const fhe_seeded_server_key* ssk, uint8_t* buf, size_t cap, size_t* len) {
+    if (!ssk || !len) return FHE_ERR_INVALID;
+    try {
+        Writer w;
+        w.b.reserve(80 + (ssk->ksk_bodies.size() + ssk->bsk_bodies.size()) * 8);
+        w.params(ssk->params);
+        w.raw(ssk->seed, 32);
+        w.words(ssk->ksk_bodies.data(), ssk->ksk_bodies.size());
+        w.words(ssk->bsk_bodies.data(), ssk->bsk_bodies.size());
+        return emit(frame(kSeededServerKey, w.b), buf, cap, len);
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return FHE_ERR_ALLOC;
+    }
+}
+
+int fhe_seeded_server_key_deserialize(const uint8_t* buf, size_t len, fhe_seeded_server_key** out) {
+    if (!out) return FHE_ERR_INVALID;
+    Reader r;
+    std::string why;
+    Params p;
+    if (!unframe(buf, len, kSeededServerKey, &r, &why) || !r.params(&p, &why)) return fail(why);
+    const char* w = nullptr;
+    if (!seeded_key_rows_ok(p, &w)) return fail(w);
+    // the length first: nothing is allocated unless the payload is exactly what the parameters need
+    const size_t nk = (size_t)kPolySize * p.ks_level, nb = (size_t)p.ggsw_count() * 2 * kPolySize;
+    if (r.n - r.off != 32 + (nk + nb) * 8)
+        return fail("seeded server key: payload length differs from what its parameters need");
+    try {
+        std::unique_ptr<fhe_seeded_server_key> s(new fhe_seeded_server_key());
+        s->params = p;
+        s->ksk_bodies.resize(nk);
+        s->bsk_bodies.resize(nb);
+        if (!r.take(s->seed, 32) || !r.words(s->ksk_bodies.data(), nk) || !r.words(s->bsk_bodies.data(), nb) ||
+            !r.done())
+            return fail("malformed seeded server key");
+        *out = s.release();
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return FHE_ERR_ALLOC;
+    }
+    return FHE_OK;
+}
+
+int fhe_seeded_server_key_expand_host(const fhe_seeded_server_key* ssk, fhe_server_key** out) {
+    if (!ssk || !out) return fail("null argument");
+    try {
+        std::unique_ptr<fhe_server_key> sk(new fhe_server_key());
+        expand_seeded_server_key_host(*ssk, sk.get());
+        *out = sk.release();
+    } catch (const std::exception& e) {
+        set_error(std::string("seeded key expansion failed: ") + e.what());
+        return FHE_ERR_ALLOC;
+    }
+    return FHE_OK;
+}
+
+void fhe_seeded_server_key_destroy(fhe_seeded_server_key* ssk) { delete ssk; }
 
 }  // extern "C"

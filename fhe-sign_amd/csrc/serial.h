@@ -12,6 +12,10 @@
 //           (num_bits, or nlimbs) | 32 seed bytes | nblocks u64 bodies (nblocks = num_bits / 2, or
 //           16 nlimbs; LSB block first).  The masks are not stored: block i's are u64 words [2048 i,
 //           2048 (i + 1)) of the ChaCha20 stream keyed by the seed, nonce {101, "ROCM", 0} (keys.h).
+//   kind 6 (seeded server key, serial.cpp): params | 32 seed bytes | 2048 ks_level u64 KSK bodies |
+//           ggsw 2 2048 u64 BSK body polynomials -- 100 + 8 (2048 ks_level + 4096 ggsw) bytes in all.  The
+//           masks are not stored: streams 102 (KSK) and 103 (BSK) under the seed, one row per 256 ChaCha
+//           blocks (keys.h fhe_seeded_server_key).
 // Readers check magic, version, kind, length, checksum, parameter ranges and every count before
 // touching memory, and refuse block metadata (degree, noise) outside the radix layer's budget, so a
 // corrupted or hostile buffer fails with FHE_ERR_INVALID instead of poisoning the scheduler.
@@ -26,7 +30,7 @@
 
 namespace fhe::ser {
 
-enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4, kSeeded = 5 };
+enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4, kSeeded = 5, kSeededServerKey = 6 };
 constexpr uint32_t kVersion = 2;  // 2: params carry the blind-rotation grouping (9th word); 1 still read
 constexpr size_t kHeaderBytes = 32;
 

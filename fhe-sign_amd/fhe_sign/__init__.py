@@ -5,12 +5,14 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
   FheUint{8,32,64}                    tfhe FheUint ops used by src/biguint.rs and src/perf_test.rs
   BigUintFHE (+, *)                   src/biguint.rs:8-265
   CompressedFheUint / CompressedBigUintFHE   tfhe's seeded ciphertexts (try_encrypt / decompress)
+  CompressedServerKey                 tfhe's seeded server key (new / decompress; Context.set_server_key
+                                      installs it on the GPU from its bodies)
   Schnorr.sign_fhe_with_k0 / sign_fhe src/schnorr.rs:154-290
 All ciphertext arithmetic runs on the GPU through lib/libfhe_rocm.so; this package only marshals.
 """
 from ._lib import FheError, FheParams, load  # noqa: F401
-from .core import (ClientKey, Context, ServerKey, comm_unique_id, default_params, generate_keys,  # noqa: F401
-                   multi_bit_params, tuning)
+from .core import (ClientKey, CompressedServerKey, Context, ServerKey, comm_unique_id, default_params,  # noqa: F401
+                   generate_keys, multi_bit_params, tuning)
 from .integer import (  # noqa: F401,E402
     COMPAT, FAST, PUBLIC, BigUintFHE, FheBool, FheUint, FheUint8, FheUint32, FheUint64, FheUint128, FheUint256, set_server_key,
     LEVEL_SPLIT, level_log, rank_pbs, stats, to_u32_digits,

@@ -194,6 +194,13 @@ _SIGNATURES = [
     ("fhe_seeded_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_seeded_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_seeded_destroy", None, [C.c_void_p]),
+    ("fhe_server_key_generate_seeded", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_server_key_params", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fhe_seeded_server_key_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_seeded_server_key_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_server_key_expand_host", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_set_server_key_seeded", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fhe_seeded_server_key_destroy", None, [C.c_void_p]),
     ("fhe_schnorr_public_key", C.c_int, [u8p, u8p]),
     ("fhe_schnorr_compute_nonce", C.c_int, [u8p, u8p, C.c_size_t, u8p, u8p]),
     ("fhe_schnorr_sign_with_k0", C.c_int, [u8p, C.c_size_t, u8p, u8p, u8p]),

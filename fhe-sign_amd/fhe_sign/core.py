@@ -113,6 +113,57 @@ class ServerKey:
         return ksk, bsk
 
 
+class CompressedServerKey:
+    """tfhe-rs' CompressedServerKey: a public 32-byte seed and the bodies of the server key (4.5x smaller
+    on the wire; include/fhe_rocm.h "seeded (compressed) server key").  Context.set_server_key(it)
+    regenerates the masks on the GPU (decompress_to_gpu); decompress() does it on the host."""
+
+    def __init__(self, handle, params: FheParams):
+        self._h = handle
+        self.params = params
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_seeded_server_key_destroy(self._h)
+            self._h = None
+
+    @classmethod
+    def _wrap(cls, h) -> "CompressedServerKey":
+        p = FheParams()
+        check(load().fhe_seeded_server_key_params(h, C.byref(p)))
+        return cls(h, p)
+
+    @classmethod
+    def new(cls, client_key: ClientKey, seed: bytes | None = None) -> "CompressedServerKey":
+        """seed=None (the default) draws the public mask seed from the OS; a given 32-byte seed is for tests.
+        One seed, one object: never reuse it under the same client key.  Advances the client key's
+        encryption stream (the noise words)."""
+        if seed is not None and len(seed) != 32:
+            raise ValueError("the mask seed is 32 bytes")
+        h = C.c_void_p()
+        check(load().fhe_server_key_generate_seeded(client_key.handle, seed, C.byref(h)))
+        return cls._wrap(h)
+
+    def serialize(self) -> bytes:
+        return serialize_with(load().fhe_seeded_server_key_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes) -> "CompressedServerKey":
+        h = C.c_void_p()
+        check(load().fhe_seeded_server_key_deserialize(data, len(data), C.byref(h)))
+        return cls._wrap(h)
+
+    def decompress(self) -> ServerKey:
+        """the full key on the host: the word-for-word definition of the GPU install"""
+        h = C.c_void_p()
+        check(load().fhe_seeded_server_key_expand_host(self._h, C.byref(h)))
+        return ServerKey(h, self.params)
+
+
 def comm_unique_id() -> bytes:
     """RCCL unique id (rank 0 creates it and shares it out of band, e.g. over torch.distributed)."""
     buf = (C.c_uint8 * 128)()
@@ -168,8 +219,12 @@ class Context:
     def __del__(self):
         self.close()
 
-    def set_server_key(self, sk: ServerKey) -> None:
-        check(load().fhe_set_server_key(self._h, sk.handle))
+    def set_server_key(self, sk: "ServerKey | CompressedServerKey") -> None:
+        """a CompressedServerKey is installed from its bodies: the masks are regenerated on the GPU"""
+        if isinstance(sk, CompressedServerKey):
+            check(load().fhe_set_server_key_seeded(self._h, sk.handle))
+        else:
+            check(load().fhe_set_server_key(self._h, sk.handle))
         self.params = sk.params
 
     def export_fourier_bsk(self) -> np.ndarray:

@@ -524,6 +524,57 @@ int fhe_seeded_expand_radix(fhe_ctx* ctx, const fhe_seeded* x, fhe_radix** out);
 int fhe_seeded_expand_biguint(fhe_ctx* ctx, const fhe_seeded* x, fhe_biguint** out);
 void fhe_seeded_destroy(fhe_seeded* x);
 
+/* ------------------------------------------------- seeded (compressed) server key */
+/* The server key is the largest object a client sends: 123,060,224 bytes at the default parameters, of
+ * which n of every n + 1 KSK words and every second BSK polynomial are public random masks.  The seeded
+ * key keeps a PUBLIC 32-byte seed and the bodies: 27,410,532 bytes (4.5x smaller; multi-bit 41.1 MB
+ * against 150.4 MB).  tfhe-rs' CompressedServerKey::new(&client_key) / .decompress() /
+ * .decompress_to_gpu().  The handle lives on the host and needs no context.
+ *   masks   ChaCha20 keyed by the 32 seed bytes (little-endian words), nonce {id, "ROCM", 0}; every row
+ *           starts on a stride of 256 ChaCha blocks (2048 u64 words):
+ *           KSK (id 102) row r = j ks_level + l: mask word t < n = u64 word 2048 r + t;
+ *           BSK (id 103) GGSW q, row rho in {0, 1}: mask coefficient m = u64 word 2048 (2 q + rho) + m
+ *   noise   2048 ks_level + ggsw 2 2048 words of the client key's encryption stream, the KSK rows' first,
+ *           then the BSK's in (q, rho, m) order, whatever the number of host threads: a serialized
+ *           client key continues correctly afterwards
+ *   bodies  KSK: <mask, s> + (S_j << (64 - ks_base_log (l + 1))) + e.  BSK, with g = 1 << (64 -
+ *           pbs_base_log) and m_q the GGSW's message: B = A * S + e, then row 1: B[0] += g m_q, row 0:
+ *           B[t] -= g m_q S_t for every t.  (fhe_generate_keys puts row 0's gadget into the mask, A[0] += g;
+ *           a mask that is regenerated from a seed cannot hold it.  The phase B - A * S = e - g m_q S is
+ *           the same, so the expanded key is consumed by every kernel unchanged -- but its words differ
+ *           from fhe_generate_keys' for the same client key.)
+ * THE SEED IS PUBLIC.  ONE SEED, ONE OBJECT: never reuse a seed for a second server key, or for a seeded
+ * ciphertext, under the same client key (the stream ids differ from the ciphertexts' 101, so a reuse is
+ * not the catastrophic case of equal ciphertext masks; the rule stands all the same).  Pass mask_seed =
+ * NULL (32 bytes from getrandom()) outside tests. */
+typedef struct fhe_seeded_server_key fhe_seeded_server_key;
+int fhe_server_key_generate_seeded(fhe_client_key* ck, const uint8_t mask_seed[32] /* NULL: OS entropy */,
+                                   fhe_seeded_server_key** out);
+int fhe_seeded_server_key_params(const fhe_seeded_server_key* ssk, fhe_params* out);
+/* Wire format (kind 6 of the keys' framed, checksummed format; size-query convention as above): params,
+ * 32 seed bytes, KSK bodies, BSK bodies -- 100 + 8 (2048 ks_level + 4096 ggsw) bytes.  The reader checks
+ * magic, version, kind, checksum, parameter ranges and that the payload length is exactly that of the
+ * parsed parameters, all before it allocates.  A full key's bytes (kind 2) are refused here, and these
+ * by fhe_server_key_deserialize.  tfhe-rs' wire format is not reproduced (parity unpinned). */
+int fhe_seeded_server_key_serialize(const fhe_seeded_server_key* ssk, uint8_t* buf, size_t cap, size_t* len);
+int fhe_seeded_server_key_deserialize(const uint8_t* buf, size_t len, fhe_seeded_server_key** ssk);
+/* CompressedServerKey::decompress on the host: an ordinary server key (masks regenerated, bodies in
+ * place; serializes with fhe_server_key_serialize).  The word-for-word definition of the GPU install,
+ * and what a server without this engine's GPU path uses. */
+int fhe_seeded_server_key_expand_host(const fhe_seeded_server_key* ssk, fhe_server_key** out);
+/* CompressedServerKey::decompress_to_gpu: leaves ctx in exactly the device state of
+ * fhe_set_server_key(ctx, expand_host(ssk)) -- KSK, byte planes, both Fourier BSK layouts, adopted
+ * parameters, LUT ids surviving a re-key, engine -- but uploads only the bodies: gfx950 kernels
+ * regenerate the KSK masks in place and the BSK mask polynomials inside the Fourier conversion, so the
+ * standard-domain BSK never exists on the device.  No secret is needed and no collective is issued:
+ * under the fan-out every rank may install the same bytes, or a root installed this way may
+ * fhe_ctx_broadcast_server_key.  Errors as fhe_set_server_key: FHE_ERR_INVALID for a NULL argument
+ * (context untouched), FHE_ERR_UNSUPPORTED for parameters the kernels do not take (context untouched),
+ * FHE_ERR_HIP for a device failure -- then the previous key is already released and the context has
+ * no key (FHE_ERR_NO_KEY from its operations) until a later install succeeds. */
+int fhe_set_server_key_seeded(fhe_ctx* ctx, const fhe_seeded_server_key* ssk);
+void fhe_seeded_server_key_destroy(fhe_seeded_server_key* ssk);
+
 /* ------------------------------------------------------------------- Schnorr / BIP-340 */
 /* The caller of the hot path (src/schnorr.rs).  32-byte scalars are big-endian.  The plaintext
  * EC / hash steps run on the host; the FHE block s = k + e*d runs on the GPU engine. */
