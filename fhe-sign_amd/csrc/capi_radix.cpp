@@ -1474,3 +1474,115 @@ int fhe_seeded_expand_biguint(fhe_ctx* c, const fhe_seeded* x, fhe_biguint** out
 void fhe_seeded_destroy(fhe_seeded* x) { delete x; }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------- compressed computed ciphertexts
+// tfhe-rs' CompressedCiphertextList of one value (compress.h): the device ends of it.  The host ends
+// (parameters, keys, fhe_compress_host, the wire kind, fhe_compressed_decrypt) are in compress_host.cpp.
+namespace {
+int compress_blocks(fhe_ctx* c, const std::vector<const Block*>& blocks, uint32_t form, uint32_t count,
+                    fhe_compressed_list** out) {
+    if (!c->has_comp) {
+        set_error("no compression key installed (fhe_set_compression_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    return guarded([&] {
+        auto x = std::make_unique<fhe_compressed_list>();
+        x->params = c->p;
+        x->cp = c->cp;
+        x->form = form;
+        x->count = count;
+        for (const Block* b : blocks) {
+            engine_check(b->degree < 16, "compress: block degree >= 16");
+            x->degrees.push_back((uint8_t)b->degree);
+        }
+        x->packed.resize(c->cp.packed_bytes(blocks.size()));
+        c->engine->compress(blocks, x->packed.data());
+        *out = x.release();
+        return FHE_OK;
+    });
+}
+int compressed_expand_check(fhe_ctx* c, const fhe_compressed_list* x, uint32_t form) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x) return invalid("null compressed list");
+    if (!c->has_comp) {
+        set_error("no compression key installed (fhe_set_compression_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    if (x->form != form)
+        return invalid(form == FHE_SEEDED_RADIX ? "compressed list holds a BigUintFHE, not a radix integer"
+                                                : "compressed list holds a radix integer, not a BigUintFHE");
+    uint32_t have = 0, want = 0;
+    if (const char* f = params_differ(x->params, c->p, &have, &want))
+        return invalid(std::string("compressed list's ") + f + " (" + std::to_string(have) +
+                       ") differs from the context's server key (" + std::to_string(want) + ")");
+    if (!(x->cp == c->cp)) return invalid("compressed list's compression parameters differ from the installed compression key's");
+    return FHE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fhe_radix_compress(fhe_ctx* c, const fhe_radix* x, fhe_compressed_list** out) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x || !out) return invalid("null argument to fhe_radix_compress");
+    std::vector<const Block*> blocks;
+    for (const Block& b : x->r.blocks) blocks.push_back(&b);
+    return compress_blocks(c, blocks, FHE_SEEDED_RADIX, x->bits, out);
+}
+
+int fhe_biguint_compress(fhe_ctx* c, const fhe_biguint* x, fhe_compressed_list** out) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x || !out) return invalid("null argument to fhe_biguint_compress");
+    std::vector<const Block*> blocks;
+    for (const Radix& d : x->v.digits) {
+        if (d.nblocks() != kLimbBlocks) return invalid("fhe_biguint_compress: a limb is not a 32-bit radix");
+        for (const Block& b : d.blocks) blocks.push_back(&b);
+    }
+    if (blocks.size() > kCompressedMaxBlocks) return invalid("compressed list of more than 2^24 blocks");
+    return compress_blocks(c, blocks, FHE_SEEDED_BIGUINT, (uint32_t)x->v.digits.size(), out);
+}
+
+int fhe_compressed_expand_radix(fhe_ctx* c, const fhe_compressed_list* x, fhe_radix** out) {
+    int rc = compressed_expand_check(c, x, FHE_SEEDED_RADIX);
+    if (rc) return rc;
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        Radix r;
+        r.blocks = c->engine->decompress(*x);
+        *out = wrap(std::move(r), x->count);
+        return FHE_OK;
+    });
+}
+
+int fhe_compressed_expand_biguint(fhe_ctx* c, const fhe_compressed_list* x, fhe_biguint** out) {
+    int rc = compressed_expand_check(c, x, FHE_SEEDED_BIGUINT);
+    if (rc) return rc;
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        const Blocks all = c->engine->decompress(*x);
+        auto v = std::make_unique<fhe_biguint>();
+        for (size_t at = 0; at < all.size(); at += kLimbBlocks) {
+            Radix d;
+            d.blocks.assign(all.begin() + at, all.begin() + at + kLimbBlocks);
+            v->v.digits.push_back(std::move(d));
+        }
+        *out = v.release();
+        return FHE_OK;
+    });
+}
+
+int fhe_compressed_extract_rows(fhe_ctx* c, const fhe_compressed_list* x, uint64_t* rows, size_t nwords) {
+    if (!x) return invalid("null compressed list");
+    int rc = compressed_expand_check(c, x, x->form);
+    if (rc) return rc;
+    if (!rows || nwords < x->degrees.size() * ((size_t)x->cp.lwe_dim() + 1)) return invalid("fhe_compressed_extract_rows: buffer too small");
+    return guarded([&] {
+        c->engine->extract_rows(*x, rows);
+        return FHE_OK;
+    });
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <memory>
 
+#include "compress_kernels.h"
 #include "kernels.h"
 #include "keygen.h"
 #include "radix.h"
@@ -148,6 +149,10 @@ int fhe_ctx::ensure_ms(size_t count) {
 }
 
 int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
+    if (has_comp) {  // a compression key does not outlive the server key it was installed after
+        const int rc = release_compression();
+        if (rc) return rc;
+    }
     if (d_ms) {
         FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read it
         FHE_HIP_CHECK(hipFree(d_ms));
@@ -162,6 +167,66 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
     }
     p = np;
     has_key = true;
+    return FHE_OK;
+}
+
+int fhe_ctx::release_compression() {
+    if (stream) FHE_HIP_CHECK(hipStreamSynchronize(stream));
+    void* ptrs[] = {d_pk_planes, d_cbsk, d_cbsk_e, d_pk_src, d_pk_digits, d_pk_body, d_pk_P, d_pk_out, d_cms, d_cpacked, d_cdesc};
+    for (void* q : ptrs)
+        if (q) (void)hipFree(q);
+    d_pk_planes = nullptr;
+    d_cbsk = d_cbsk_e = nullptr;
+    d_pk_src = nullptr;
+    d_pk_digits = nullptr;
+    d_pk_body = d_pk_P = nullptr;
+    d_pk_out = nullptr;
+    d_cms = nullptr;
+    d_cpacked = nullptr;
+    d_cdesc = nullptr;
+    pk_cap = cms_cap = 0;
+    cms_stride = 0;
+    has_comp = false;
+    return FHE_OK;
+}
+
+int fhe_ctx::ensure_pk(size_t count) {
+    if (count <= pk_cap) return FHE_OK;
+    FHE_HIP_CHECK(hipStreamSynchronize(stream));
+    void* old[] = {d_pk_src, d_pk_digits, d_pk_body, d_pk_P, d_pk_out};
+    for (void* q : old)
+        if (q) FHE_HIP_CHECK(hipFree(q));
+    d_pk_src = nullptr;
+    d_pk_digits = nullptr;
+    d_pk_body = d_pk_P = nullptr;
+    d_pk_out = nullptr;
+    pk_cap = 0;
+    const size_t cap = std::max<size_t>(count, 256);
+    FHE_HIP_CHECK(hipMalloc(&d_pk_src, cap * sizeof(uint64_t*)));
+    FHE_HIP_CHECK(hipMalloc(&d_pk_digits, fhe::pk_digits_bytes((int)cap, (int)cp.ell)));
+    FHE_HIP_CHECK(hipMalloc(&d_pk_body, cap * 8));
+    FHE_HIP_CHECK(hipMalloc(&d_pk_P, cap * cp.cols() * 8));
+    FHE_HIP_CHECK(hipMalloc(&d_pk_out, cp.glwes(cap) * (size_t)fhe::pk_out_stride((int)cp.k, (int)cp.N)));
+    pk_cap = cap;
+    return FHE_OK;
+}
+
+int fhe_ctx::ensure_cms(size_t count) {
+    if (count <= cms_cap) return FHE_OK;
+    FHE_HIP_CHECK(hipStreamSynchronize(stream));
+    void* old[] = {d_cms, d_cpacked, d_cdesc};
+    for (void* q : old)
+        if (q) FHE_HIP_CHECK(hipFree(q));
+    d_cms = nullptr;
+    d_cpacked = nullptr;
+    d_cdesc = nullptr;
+    cms_cap = 0;
+    const size_t cap = std::max<size_t>(count, 256);
+    cms_stride = (int)((cp.lwe_dim() + 1 + 7) / 8 * 8);
+    FHE_HIP_CHECK(hipMalloc(&d_cms, cap * cms_stride * 8));
+    FHE_HIP_CHECK(hipMalloc(&d_cpacked, cp.glwes(cap) * cp.glwe_bytes(cp.L)));
+    FHE_HIP_CHECK(hipMalloc(&d_cdesc, cap * sizeof(fhe::PbsDesc)));
+    cms_cap = cap;
     return FHE_OK;
 }
 
@@ -295,11 +360,16 @@ hipError_t fhe_ctx::keyswitch(const uint64_t* in, const fhe::PbsDesc* desc, size
 }
 
 hipError_t fhe_ctx::blind_rotate(const fhe::PbsDesc* desc, const uint32_t* lut_idx, uint64_t* out, size_t count) {
+    return blind_rotate(main_keys(), desc, lut_idx, out, count);
+}
+
+hipError_t fhe_ctx::blind_rotate(const BrKeys& ks, const fhe::PbsDesc* desc, const uint32_t* lut_idx, uint64_t* out,
+                                 size_t count) {
     if ((int)count <= wide_threshold)
-        return launch_blind_rotate_wide(d_ms, ms_stride, desc, lut_idx, d_luts, d_bsk, d_tw_wide, d_psi_wide,
-                                        d_zeta_wide, d_mono, (int)p.grouping, out, (int)count, (int)p.n, stream);
-    return launch_blind_rotate_qy(d_ms, ms_stride, desc, lut_idx, d_luts, d_bsk_e, d_tw_quad, d_psi_quad, d_zeta_full,
-                                  d_mono, (int)p.grouping, out, (int)count, (int)p.n,
+        return launch_blind_rotate_wide(ks.ms, ks.ms_stride, desc, lut_idx, d_luts, ks.bsk, d_tw_wide, d_psi_wide,
+                                        d_zeta_wide, d_mono, ks.grouping, out, (int)count, ks.n, stream);
+    return launch_blind_rotate_qy(ks.ms, ks.ms_stride, desc, lut_idx, d_luts, ks.bsk_e, d_tw_quad, d_psi_quad, d_zeta_full,
+                                  d_mono, ks.grouping, out, (int)count, ks.n,
                                   clock_probe ? d_clock : nullptr,
                                   br_kernel == FHE_BR_QZ || (br_kernel == FHE_BR_AUTO && qy2_fills(count)) ? 3
                                   : br_kernel == FHE_BR_QY2                                                ? 1
@@ -582,6 +652,7 @@ void fhe_ctx_destroy(fhe_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     delete c->engine;
     c->engine = nullptr;
+    (void)c->release_compression();
     c->release_comm();
     void* ptrs[] = {c->d_ksk, c->d_ksk_planes, c->d_ks_digits, c->d_ks_body, c->d_bsk, c->d_W, c->d_psi, c->d_tw_wide, c->d_psi_wide, c->d_tw_quad,
                     c->d_psi_quad, c->d_zeta_wide, c->d_mono, c->d_bsk_e, c->d_zeta_full, c->d_flags, c->d_luts, c->d_ms, c->d_stage_in, c->d_stage_out, c->d_stage_lut, c->d_gather, c->d_clock};
@@ -602,6 +673,10 @@ struct DeviceFree {
 // The two ends every key install shares.  release_key: the stream is drained and the previous key's
 // buffers are freed -- from here until install_tail succeeds the context has no key.
 int release_key(fhe_ctx* c) {
+    if (c->has_comp) {  // a compression key belongs to the server key it was installed after
+        const int rc = c->release_compression();
+        if (rc) return rc;
+    }
     if (!c->has_key) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
     FHE_HIP_CHECK(hipFree(c->d_ksk));
@@ -640,6 +715,53 @@ int install_tail(fhe_ctx* c, const Params& p, bool had_key) {
     return FHE_OK;
 }
 }  // namespace
+
+int fhe_set_compression_key(fhe_ctx* c, const fhe_compression_key* key) {
+    if (!c || !key) {
+        set_error("null argument to fhe_set_compression_key");
+        return FHE_ERR_INVALID;
+    }
+    if (!c->has_key || !c->engine) {
+        set_error("no server key installed: fhe_set_compression_key comes after fhe_set_server_key");
+        return FHE_ERR_NO_KEY;
+    }
+    uint32_t have = 0, want = 0;
+    // the decompression key is classic whatever the main grouping: compare the main sets field by field
+    if (const char* f = params_differ(key->params, c->p, &have, &want)) {
+        set_error(std::string("compression key's ") + f + " (" + std::to_string(have) +
+                  ") differs from the context's server key (" + std::to_string(want) + ")");
+        return FHE_ERR_INVALID;
+    }
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    int rc = c->release_compression();
+    if (rc) return rc;
+    const CompParams& cp = key->cp;
+    c->cp = cp;
+    uint64_t* d_std = nullptr;
+    const size_t std_words = std::max(key->pksk.size(), key->bsk.size());
+    FHE_HIP_CHECK(hipMalloc(&d_std, std_words * 8));
+    std::unique_ptr<void, DeviceFree> std_guard(d_std);
+    auto body = [&]() -> int {
+        FHE_HIP_CHECK(hipMalloc(&c->d_pk_planes, fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
+        FHE_HIP_CHECK(hipMemcpyAsync(d_std, key->pksk.data(), key->pksk.size() * 8, hipMemcpyHostToDevice, c->stream));
+        FHE_HIP_CHECK(launch_pksk_to_planes(d_std, (int)cp.ell, (int)cp.cols(), c->d_pk_planes, c->stream));
+        const int npoly = (int)(cp.lwe_dim() * 4);
+        FHE_HIP_CHECK(hipMalloc(&c->d_cbsk, (size_t)npoly * 1024 * sizeof(double2)));
+        FHE_HIP_CHECK(hipMalloc(&c->d_cbsk_e, (size_t)npoly * 1024 * sizeof(double2)));
+        FHE_HIP_CHECK(hipMemcpyAsync(d_std, key->bsk.data(), key->bsk.size() * 8, hipMemcpyHostToDevice, c->stream));
+        FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, npoly, c->d_W, c->d_psi, c->d_cbsk, c->stream));
+        FHE_HIP_CHECK(launch_bsk_to_e(c->d_cbsk, npoly, c->d_cbsk_e, c->stream));
+        FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+        return FHE_OK;
+    };
+    rc = body();
+    if (rc) {
+        (void)c->release_compression();
+        return rc;
+    }
+    c->has_comp = true;
+    return FHE_OK;
+}
 
 int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
     if (!c || !sk) return FHE_ERR_INVALID;

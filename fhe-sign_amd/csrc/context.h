@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "compress.h"
 #include "keys.h"
 #include "kernels.h"
 
@@ -167,4 +168,42 @@ struct fhe_ctx {
     int pbs_device(const uint64_t* d_in, size_t count, const uint32_t* d_lut, uint64_t* d_out);
     // blind rotate (+SE) of `count` modulus-switched inputs in d_ms, kernel chosen by batch size
     hipError_t blind_rotate(const fhe::PbsDesc* desc, const uint32_t* lut_idx, uint64_t* out, size_t count);
+    // The key set one blind rotation runs under: the two Fourier layouts, the LWE dimension, the grouping and
+    // the workspace holding the inputs.  main_keys() is what every bootstrap of the radix layer uses;
+    // comp_keys() the decompression key (classic, n = k' N', its own workspace: d_ms' stride is sized for p.n).
+    struct BrKeys {
+        const double2 *bsk, *bsk_e;
+        int n, grouping;
+        const uint64_t* ms;
+        int ms_stride;
+    };
+    BrKeys main_keys() const { return {d_bsk, d_bsk_e, (int)p.n, (int)p.grouping, d_ms, ms_stride}; }
+    BrKeys comp_keys() const { return {d_cbsk, d_cbsk_e, (int)cp.lwe_dim(), 1, d_cms, cms_stride}; }
+    hipError_t blind_rotate(const BrKeys& ks, const fhe::PbsDesc* desc, const uint32_t* lut_idx, uint64_t* out,
+                            size_t count);
+
+    // Compression key (fhe_set_compression_key; dropped by every server-key install): the packing KSK as
+    // byte planes (compress.hip), the decompression BSK in the two Fourier layouts, and the workspaces.
+    bool has_comp = false;
+    fhe::CompParams cp;
+    int8_t* d_pk_planes = nullptr;
+    double2* d_cbsk = nullptr;    // latency layout
+    double2* d_cbsk_e = nullptr;  // throughput (E) layout
+    // compression workspace, `pk_cap` blocks: slot pointers, digits, bodies, contraction output, packed stream
+    const uint64_t** d_pk_src = nullptr;
+    int8_t* d_pk_digits = nullptr;
+    uint64_t* d_pk_body = nullptr;
+    uint64_t* d_pk_P = nullptr;
+    uint8_t* d_pk_out = nullptr;
+    size_t pk_cap = 0;
+    // decompression workspace, `cms_cap` blocks: sample-extracted rows (stride cms_stride >= k' N' + 1),
+    // the uploaded 12-bit stream, one descriptor (LUT, destination slot) per block
+    uint64_t* d_cms = nullptr;
+    uint8_t* d_cpacked = nullptr;
+    fhe::PbsDesc* d_cdesc = nullptr;
+    size_t cms_cap = 0;
+    int cms_stride = 0;
+    int ensure_pk(size_t count);
+    int ensure_cms(size_t count);
+    int release_compression();  // waits for the stream, frees all of the above
 };

@@ -46,6 +46,9 @@ struct Params {
     }
 };
 
+// (The parameters and keys of the compressed computed ciphertexts -- tfhe-rs' compression parameters AS
+// RECALLED, like the defaults above -- are in compress.h: CompParams, fhe_compression_key.)
+
 // The 256-bit ChaCha20 key every key-generation stream is derived from (stream id = nonce word 0).
 // Production keys come from 32 bytes of OS entropy (fhe_generate_keys_keyed, generate_keys(seed=None)
 // in the Python mirror); `seed_key` expands a 64-bit test seed into {seed, "FHES", 0, ...} -- a

@@ -13,6 +13,7 @@
 // Public structure only (degrees, trivial blocks) drives the schedule; no decision ever depends
 // on encrypted data.
 #include "radix.h"
+#include "compress_kernels.h"
 #include "keygen.h"
 
 #include <algorithm>
@@ -1032,6 +1033,106 @@ Blocks Engine::expand_seeded(const uint8_t seed[32], const uint64_t* bodies, siz
     hip_check(launch_expand_seeded(chacha_stream_key(key.data(), kStreamSeededMask), d_dst, d_up_, (int)n, ctx_->stream),
               "seeded expansion");
     hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
+    return out;
+}
+
+// ------------------------------------------------------------------ compressed computed ciphertexts
+namespace {
+void need_compression(const fhe_ctx* c) {
+    if (!c->has_comp) throw EngineError(FHE_ERR_NO_KEY, "no compression key installed (fhe_set_compression_key)");
+}
+}  // namespace
+
+void Engine::compress(const std::vector<const Block*>& blocks, uint8_t* packed) {
+    engine_check(host_mode_ == kDevice, "compress on a host-only engine");
+    need_compression(ctx_);
+    const size_t n = blocks.size();
+    engine_check(n <= kCompressedMaxBlocks, "compressed list of more than 2^24 blocks");
+    if (n == 0) return;
+    const CompParams& cp = ctx_->cp;
+    // trivial blocks become ciphertexts (0, b) in slots of their own: the kernels see no special case
+    std::vector<size_t> triv;
+    for (size_t i = 0; i < n; ++i) {
+        engine_check(!blocks[i]->lazy(), "compress of a lazy block");
+        if (blocks[i]->trivial()) triv.push_back(i);
+    }
+    Blocks tmp;
+    if (!triv.empty()) {
+        std::vector<uint64_t> cts(triv.size() * kBigCt, 0ull);
+        for (size_t q = 0; q < triv.size(); ++q)
+            cts[q * kBigCt + kBigDim] = (uint64_t)blocks[triv[q]]->value * ctx_->p.delta();
+        tmp = upload_many(cts.data(), triv.size(), 0);
+    }
+    flush();
+    engine_check(ctx_->ensure_pk(n) == FHE_OK, "compression workspace");
+    std::vector<const uint64_t*> src(n);
+    for (size_t i = 0, q = 0; i < n; ++i) src[i] = blocks[i]->trivial() ? tmp[q++].slot->p : blocks[i]->slot->p;
+    hip_check(hipMemcpyAsync(ctx_->d_pk_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
+              "compress slots");
+    hip_check(launch_pack_keyswitch(ctx_->d_pk_src, (int)n, (int)cp.beta, (int)cp.ell, (int)cp.k, (int)cp.N, (int)cp.L,
+                                    ctx_->d_pk_planes, ctx_->d_pk_digits, ctx_->d_pk_body, ctx_->d_pk_P, ctx_->d_pk_out,
+                                    ctx_->stream),
+              "packing keyswitch");
+    const size_t G = cp.glwes(n), stride = (size_t)pk_out_stride((int)cp.k, (int)cp.N);
+    std::vector<uint8_t> stage(G * stride);
+    hip_check(hipMemcpyAsync(stage.data(), ctx_->d_pk_out, stage.size(), hipMemcpyDeviceToHost, ctx_->stream),
+              "compress download");
+    wait_check(ctx_, "compress");
+    // the device keeps every polynomial on a 32-bit word; the wire starts a GLWE on the next byte
+    uint8_t* out = packed;
+    for (size_t g = 0; g < G; ++g) {
+        const size_t bytes = cp.glwe_bytes(cp.bodies(n, g));
+        std::memcpy(out, stage.data() + g * stride, bytes);
+        out += bytes;
+    }
+}
+
+void Engine::extract_rows(const fhe_compressed_list& x, uint64_t* rows) {
+    engine_check(host_mode_ == kDevice, "decompress on a host-only engine");
+    need_compression(ctx_);
+    const size_t n = x.degrees.size();
+    if (n == 0) return;
+    const CompParams& cp = ctx_->cp;
+    engine_check(ctx_->ensure_cms(n) == FHE_OK, "decompression workspace");
+    hip_check(hipMemcpyAsync(ctx_->d_cpacked, x.packed.data(), x.packed.size(), hipMemcpyHostToDevice, ctx_->stream),
+              "compressed upload");
+    hip_check(launch_pk_unpack(ctx_->d_cpacked, (int)n, (int)cp.glwe_bytes(cp.L), (int)cp.L, (int)cp.N, (int)cp.k,
+                               ctx_->d_cms, ctx_->cms_stride, ctx_->stream),
+              "unpack");
+    if (rows) {
+        const size_t row = ((size_t)cp.lwe_dim() + 1) * 8;
+        hip_check(hipMemcpy2DAsync(rows, row, ctx_->d_cms, (size_t)ctx_->cms_stride * 8, row, n, hipMemcpyDeviceToHost,
+                                   ctx_->stream),
+                  "rows download");
+        hip_check(hipStreamSynchronize(ctx_->stream), "rows sync");
+    }
+}
+
+Blocks Engine::decompress(const fhe_compressed_list& x) {
+    const size_t n = x.degrees.size();
+    engine_check(host_mode_ == kDevice, "decompress on a host-only engine");
+    need_compression(ctx_);
+    Blocks out(n);
+    if (n == 0) return out;
+    std::vector<uint32_t> ident(ctx_->p.msg_carry());
+    for (uint32_t v = 0; v < ident.size(); ++v) ident[v] = v;
+    uint32_t lut = 0;
+    engine_check(ctx_->register_lut(ident.data(), &lut) == FHE_OK && ctx_->sync_luts() == FHE_OK, "identity table");
+    extract_rows(x, nullptr);
+    std::vector<PbsDesc> desc(n);
+    std::memset(desc.data(), 0, n * sizeof(PbsDesc));
+    for (size_t i = 0; i < n; ++i) {
+        out[i].slot = pool_->alloc();
+        out[i].degree = x.degrees[i];
+        out[i].noise = 1;
+        desc[i].lut = lut;
+        desc[i].dst = out[i].slot->p;
+    }
+    hip_check(hipMemcpyAsync(ctx_->d_cdesc, desc.data(), n * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream),
+              "decompress descriptors");
+    hip_check(ctx_->blind_rotate(ctx_->comp_keys(), ctx_->d_cdesc, nullptr, nullptr, n), "decompression blind rotate");
+    hip_check(hipStreamSynchronize(ctx_->stream), "decompress sync");  // host buffers may go, the staging be reused
+    pbs_count += n;
     return out;
 }
 

@@ -192,6 +192,17 @@ public:
     // deterministic and rank-local, so under an attached communicator EVERY rank must expand the same
     // bytes (the fan-out's identical-inputs rule).
     Blocks expand_seeded(const uint8_t seed[32], const uint64_t* bodies, size_t n);
+    // Compressed computed ciphertexts (compress.h).  compress: the blocks (slot or trivial; a trivial block goes
+    // through as the ciphertext (0, b)) -> the packed 12-bit GLWE streams, CompParams::packed_bytes(n) bytes,
+    // byte for byte pack_keyswitch_host's output.  Flushes like a download (a plain flush: rank-local under a
+    // communicator, no collective), then digits, matrix-core contraction, rotate / switch / pack, one copy
+    // back.  decompress: n fresh slots (noise 1, degrees from the list), stream-ordered like expand_seeded --
+    // no flush, no collective: the unpack + sample-extract kernel, then the blind rotate under the
+    // decompression key with the identity table.  Device engines with a compression key only.
+    void compress(const std::vector<const Block*>& blocks, uint8_t* packed);
+    Blocks decompress(const fhe_compressed_list& x);
+    // the unpack + sample-extract kernel alone: n x (k' N' + 1) words to the host (tests)
+    void extract_rows(const fhe_compressed_list& x, uint64_t* rows);
     void download(const Block& b, uint64_t* ct);
     // the slot blocks' ciphertexts -> host, contiguous (one gather + one copy + one wait instead of a
     // round trip per block: the decryption of a 256-bit result is 128-144 blocks)

@@ -16,6 +16,11 @@
 //           ggsw 2 2048 u64 BSK body polynomials -- 100 + 8 (2048 ks_level + 4096 ggsw) bytes in all.  The
 //           masks are not stored: streams 102 (KSK) and 103 (BSK) under the seed, one row per 256 ChaCha
 //           blocks (keys.h fhe_seeded_server_key).
+//   kinds 7 / 8 / 9 (compress_host.cpp; compressed computed ciphertexts): params | 7 x u32 compression params
+//           (k', N', L, pks_base_log, pks_level, pks_noise_log2, storage_log_modulus), then 7: k' N' u64 secret
+//           words; 8: the packing KSK u64[2048][pks_level][k' + 1][N'], the decompression BSK u64[k' N'][2][2][2048];
+//           9: u32 form | u32 count | u32 B | B degree bytes | per GLWE the 12-bit stream of k' N' + b_g values,
+//           each GLWE from a byte boundary -- 108 + B + sum_g ceil(12 (k' N' + b_g) / 8) bytes in all.
 // Readers check magic, version, kind, length, checksum, parameter ranges and every count before
 // touching memory, and refuse block metadata (degree, noise) outside the radix layer's budget, so a
 // corrupted or hostile buffer fails with FHE_ERR_INVALID instead of poisoning the scheduler.
@@ -30,7 +35,8 @@
 
 namespace fhe::ser {
 
-enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4, kSeeded = 5, kSeededServerKey = 6 };
+enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4, kSeeded = 5, kSeededServerKey = 6,
+                       kCompressionPrivateKey = 7, kCompressionKey = 8, kCompressedList = 9 };
 constexpr uint32_t kVersion = 2;  // 2: params carry the blind-rotation grouping (9th word); 1 still read
 constexpr size_t kHeaderBytes = 32;
 

@@ -32,6 +32,27 @@ class FheParams(C.Structure):
         return self.lwe_dimension if g == 1 else self.lwe_dimension // g * ((1 << g) - 1)
 
 
+class CompressionParams(C.Structure):
+    """fhe_compression_params (include/fhe_rocm.h "compressed computed ciphertexts")"""
+    _fields_ = [(name, C.c_uint32) for name in (
+        "glwe_dimension", "polynomial_size", "lwe_per_glwe", "pks_base_log", "pks_level", "pks_noise_log2",
+        "storage_log_modulus")]
+
+    def lwe_dim(self) -> int:
+        return self.glwe_dimension * self.polynomial_size
+
+    def packed_bytes(self, nblocks: int) -> int:
+        """sum over the GLWEs of ceil(12 (k' N' + b_g) / 8)"""
+        L, total = self.lwe_per_glwe, 0
+        for g in range((nblocks + L - 1) // L):
+            total += (12 * (self.lwe_dim() + min(L, nblocks - g * L)) + 7) // 8
+        return total
+
+    def wire_bytes(self, nblocks: int) -> int:
+        """a serialized CompressedCiphertextList: 108 header bytes, the degree bytes, the packed GLWEs"""
+        return 108 + nblocks + self.packed_bytes(nblocks)
+
+
 # fhe_test_transport (include/fhe_rocm.h): the host-staged test hook in place of RCCL
 TX_BCAST = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int)
 TX_ALLGATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -201,6 +222,33 @@ _SIGNATURES = [
     ("fhe_seeded_server_key_expand_host", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_set_server_key_seeded", C.c_int, [C.c_void_p, C.c_void_p]),
     ("fhe_seeded_server_key_destroy", None, [C.c_void_p]),
+    ("fhe_compression_params_default", C.c_int, [C.POINTER(CompressionParams)]),
+    ("fhe_compression_keys_generate", C.c_int,
+     [C.c_void_p, C.POINTER(CompressionParams), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("fhe_compression_key_params", C.c_int, [C.c_void_p, C.POINTER(FheParams), C.POINTER(CompressionParams)]),
+    ("fhe_compression_private_key_params", C.c_int, [C.c_void_p, C.POINTER(FheParams), C.POINTER(CompressionParams)]),
+    ("fhe_compression_key_export", C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t]),
+    ("fhe_compression_private_key_export", C.c_int, [C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_compression_private_key_destroy", None, [C.c_void_p]),
+    ("fhe_compression_key_destroy", None, [C.c_void_p]),
+    ("fhe_compression_private_key_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_compression_private_key_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_compression_key_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_compression_key_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_compress_host", C.c_int,
+     [C.c_void_p, u64p, C.c_size_t, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("fhe_compressed_info", C.c_int, [C.c_void_p, u32p, u32p, C.POINTER(C.c_size_t)]),
+    ("fhe_compressed_params", C.c_int, [C.c_void_p, C.POINTER(FheParams), C.POINTER(CompressionParams)]),
+    ("fhe_compressed_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_compressed_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_compressed_destroy", None, [C.c_void_p]),
+    ("fhe_compressed_decrypt", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_set_compression_key", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fhe_radix_compress", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_biguint_compress", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_compressed_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_compressed_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_compressed_extract_rows", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t]),
     ("fhe_schnorr_public_key", C.c_int, [u8p, u8p]),
     ("fhe_schnorr_compute_nonce", C.c_int, [u8p, u8p, C.c_size_t, u8p, u8p]),
     ("fhe_schnorr_sign_with_k0", C.c_int, [u8p, C.c_size_t, u8p, u8p, u8p]),

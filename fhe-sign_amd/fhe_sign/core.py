@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FheParams, check, load, ptr, serialize_with
+from ._lib import CompressionParams, FheParams, check, load, ptr, serialize_with
 
 BIG_CT = 2049  # big LWE ciphertext words
 
@@ -164,6 +164,91 @@ class CompressedServerKey:
         return ServerKey(h, self.params)
 
 
+def default_compression_params() -> CompressionParams:
+    p = CompressionParams()
+    check(load().fhe_compression_params_default(C.byref(p)))
+    return p
+
+
+class CompressionPrivateKey:
+    """tfhe-rs' CompressionPrivateKeys: the client's secret s' of the packed GLWEs (k' N' bits)"""
+
+    def __init__(self, handle):
+        self._h = handle
+        self.params = CompressionParams()
+        check(load().fhe_compression_private_key_params(handle, None, C.byref(self.params)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_compression_private_key_destroy(self._h)
+            self._h = None
+
+    def export(self) -> np.ndarray:
+        sk = np.zeros(self.params.lwe_dim(), np.uint64)
+        check(load().fhe_compression_private_key_export(self._h, ptr(sk), sk.size))
+        return sk
+
+    def serialize(self) -> bytes:
+        return serialize_with(load().fhe_compression_private_key_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes) -> "CompressionPrivateKey":
+        h = C.c_void_p()
+        check(load().fhe_compression_private_key_deserialize(data, len(data), C.byref(h)))
+        return cls(h)
+
+
+class CompressionKey:
+    """tfhe-rs' CompressionKey + DecompressionKey: the packing keyswitch key and the classic bootstrapping
+    key of dimension k' N' (include/fhe_rocm.h); Context.set_compression_key installs it"""
+
+    def __init__(self, handle):
+        self._h = handle
+        self.main_params, self.params = FheParams(), CompressionParams()
+        check(load().fhe_compression_key_params(handle, C.byref(self.main_params), C.byref(self.params)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_compression_key_destroy(self._h)
+            self._h = None
+
+    def export(self):
+        """(packing KSK [2048][level][k' + 1][N'], decompression BSK [k' N'][2][2][2048]) as flat uint64"""
+        c = self.params
+        pksk = np.zeros(2048 * c.pks_level * (c.glwe_dimension + 1) * c.polynomial_size, np.uint64)
+        bsk = np.zeros(c.lwe_dim() * 4 * 2048, np.uint64)
+        check(load().fhe_compression_key_export(self._h, ptr(pksk), pksk.size, ptr(bsk), bsk.size))
+        return pksk, bsk
+
+    def serialize(self) -> bytes:
+        return serialize_with(load().fhe_compression_key_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes) -> "CompressionKey":
+        h = C.c_void_p()
+        check(load().fhe_compression_key_deserialize(data, len(data), C.byref(h)))
+        return cls(h)
+
+
+class CompressionKeys:
+    @staticmethod
+    def generate(client_key: ClientKey, params: CompressionParams | None = None):
+        """(CompressionPrivateKey, CompressionKey) of client_key; advances its encryption stream by
+        k' N' + 2048 level (k' + 1) N' + 8192 k' N' words"""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(load().fhe_compression_keys_generate(client_key.handle, C.byref(params) if params is not None else None,
+                                                   C.byref(a), C.byref(b)))
+        return CompressionPrivateKey(a), CompressionKey(b)
+
+
 def comm_unique_id() -> bytes:
     """RCCL unique id (rank 0 creates it and shares it out of band, e.g. over torch.distributed)."""
     buf = (C.c_uint8 * 128)()
@@ -226,6 +311,10 @@ class Context:
         else:
             check(load().fhe_set_server_key(self._h, sk.handle))
         self.params = sk.params
+
+    def set_compression_key(self, key: "CompressionKey") -> None:
+        """after set_server_key; the next set_server_key drops it"""
+        check(load().fhe_set_compression_key(self._h, key.handle))
 
     def export_fourier_bsk(self) -> np.ndarray:
         out = np.zeros(self.params.ggsw_count() * 4 * 1024 * 2, np.float64)

@@ -13,7 +13,7 @@ import threading
 
 import numpy as np
 
-from ._lib import FheError, check, load, ptr, serialize_with
+from ._lib import CompressionParams, FheError, check, load, ptr, serialize_with
 
 COMPAT = 0  # exact replay of src/biguint.rs:214-254 incl. the wrapping add at :247-249
 FAST = 1    # true product/sum, single wide carry propagation
@@ -536,6 +536,106 @@ class CompressedBigUintFHE(_Seeded):
         h = C.c_void_p()
         check(load().fhe_seeded_expand_biguint(_ctx().handle, self._h, C.byref(h)))
         return BigUintFHE(h)
+
+
+class CompressedCiphertextList:
+    """tfhe-rs' CompressedCiphertextList holding one computed value: blocks packed into GLWEs under the
+    compression key, 12 bits per coefficient (include/fhe_rocm.h).  A host object: serialize / deserialize /
+    decrypt(private) need no context; decompress() brings it back onto this thread's GPU context."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_compressed_destroy(self._h)
+            self._h = None
+
+    def _info(self):
+        form, count, nb = C.c_uint32(), C.c_uint32(), C.c_size_t()
+        check(load().fhe_compressed_info(self._h, C.byref(form), C.byref(count), C.byref(nb)))
+        return int(form.value), int(count.value), int(nb.value)
+
+    @property
+    def nblocks(self) -> int:
+        return self._info()[2]
+
+    @property
+    def params(self) -> CompressionParams:
+        cp = CompressionParams()
+        check(load().fhe_compressed_params(self._h, None, C.byref(cp)))
+        return cp
+
+    @property
+    def bits(self) -> int:
+        form, count, _ = self._info()
+        return count if form == SEEDED_RADIX else 32 * count
+
+    @classmethod
+    def compress_host(cls, key, cts, degrees, form: int, count: int):
+        """the packing keyswitch on the host (fhe_compress_host): the definition of the GPU path"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2049)
+        deg = np.ascontiguousarray(np.broadcast_to(np.asarray(degrees, np.uint8), (cts.shape[0],)))
+        h = C.c_void_p()
+        check(load().fhe_compress_host(key.handle, ptr(cts), cts.shape[0], ptr(deg, C.c_uint8), form, count, C.byref(h)))
+        return cls(h)
+
+    def serialize(self) -> bytes:
+        """108 + nblocks + sum_g ceil(12 (k' N' + b_g) / 8) bytes"""
+        return serialize_with(load().fhe_compressed_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes):
+        h = C.c_void_p()
+        check(load().fhe_compressed_deserialize(data, len(data), C.byref(h)))
+        return cls(h)
+
+    def decrypt(self, private) -> int:
+        """the value, from the 12-bit GLWEs directly (BigUintFHE form: limb i at bits 32 i)"""
+        n = max(1, (self.bits + 63) // 64)
+        w = np.zeros(n, np.uint64)
+        check(load().fhe_compressed_decrypt(private.handle, self._h, ptr(w), n))
+        return sum(int(w[i]) << (64 * i) for i in range(n))
+
+    def decompress(self, ctx=None):
+        """FheUint or BigUintFHE on ctx (default: this thread's context), fresh noise"""
+        ctx = ctx or _ctx()
+        form, count, _ = self._info()
+        h = C.c_void_p()
+        if form == SEEDED_BIGUINT:
+            check(load().fhe_compressed_expand_biguint(ctx.handle, self._h, C.byref(h)))
+            return BigUintFHE(h)
+        check(load().fhe_compressed_expand_radix(ctx.handle, self._h, C.byref(h)))
+        return FheUint._wrap(h, count)
+
+    def extract_rows(self, ctx=None) -> np.ndarray:
+        """test hook: the unpack + sample-extract kernel's rows, (nblocks, k' N' + 1)"""
+        ctx = ctx or _ctx()
+        n = self.nblocks
+        out = np.zeros((n, self.params.lwe_dim() + 1), np.uint64)
+        check(load().fhe_compressed_extract_rows(ctx.handle, self._h, ptr(out), out.size))
+        return out
+
+
+def _compress_radix(self) -> CompressedCiphertextList:
+    """CompressedCiphertextListBuilder::push(self).build() on this thread's context"""
+    h = C.c_void_p()
+    check(load().fhe_radix_compress(_ctx().handle, self._h, C.byref(h)))
+    return CompressedCiphertextList(h)
+
+
+def _compress_biguint(self) -> CompressedCiphertextList:
+    h = C.c_void_p()
+    check(load().fhe_biguint_compress(_ctx().handle, self._h, C.byref(h)))
+    return CompressedCiphertextList(h)
+
+
+FheUint.compress = _compress_radix
+BigUintFHE.compress = _compress_biguint
 
 
 LEVEL_SPLIT = 1 << 31  # FHE_LEVEL_SPLIT: the level was fanned out over the ranks

@@ -575,6 +575,110 @@ int fhe_seeded_server_key_expand_host(const fhe_seeded_server_key* ssk, fhe_serv
 int fhe_set_server_key_seeded(fhe_ctx* ctx, const fhe_seeded_server_key* ssk);
 void fhe_seeded_server_key_destroy(fhe_seeded_server_key* ssk);
 
+/* ------------------------------------------------- compressed computed ciphertexts */
+/* Anything the server COMPUTES leaves the GPU as big-key LWE blocks of 2049 words: a 256-bit value is
+ * 2.1 MB through fhe_radix_serialize.  tfhe-rs' CompressedCiphertextList: the blocks are packed into GLWEs
+ * by a packing keyswitch under a dedicated compression key, every coefficient is modulus-switched to 12
+ * bits, and a bootstrap under a decompression key restores usable blocks.  A 256-bit value becomes
+ * 12 (1024 + 128) bits = 1,728 payload bytes + 128 degree bytes + the header.
+ *
+ * Parameters: tfhe-rs' COMP_PARAM_MESSAGE_2_CARRY_2_KS_PBS_TUNIFORM_2M64 AS RECALLED (no tfhe-rs source
+ * is at hand to pin them).  The decompression bootstrap uses the main set's pbs_base_log x 1 level
+ * (2^23 x 1) and glwe_noise_log2.  Accepted: polynomial_size a power of two in [8, 2048]; 1 <=
+ * glwe_dimension <= 8 with glwe_dimension * polynomial_size <= 2048; 1 <= lwe_per_glwe <= polynomial_size;
+ * pks_base_log * pks_level <= 32, 1 <= pks_base_log <= 7 (digits fit a signed byte);
+ * storage_log_modulus exactly 12 = log2(2 * 2048), so the decompression bootstrap's own modulus switch of
+ * a stored value is the identity.  Anything else: FHE_ERR_UNSUPPORTED with a named reason. */
+typedef struct fhe_compression_params {
+    uint32_t glwe_dimension;      /* k' (4) */
+    uint32_t polynomial_size;     /* N' (256) */
+    uint32_t lwe_per_glwe;        /* L  (256) */
+    uint32_t pks_base_log;        /* 4 */
+    uint32_t pks_level;           /* 4 */
+    uint32_t pks_noise_log2;      /* TUniform bound of the packing key (42) */
+    uint32_t storage_log_modulus; /* 12 */
+} fhe_compression_params;
+int fhe_compression_params_default(fhe_compression_params* out);
+/* CompressionPrivateKeys (client): k' N' binary words s', independent of the GLWE key. */
+typedef struct fhe_compression_private_key fhe_compression_private_key;
+/* CompressionKey + DecompressionKey (server):
+ *   packing KSK  u64[2048][pks_level][k' + 1][N']: row (j, l) is a GLWE encryption under s' of the constant
+ *                polynomial S_j << (64 - pks_base_log (l + 1)), S the big key: masks A_c uniform,
+ *                B = sum_c A_c * s'_c + e + const, e per coefficient from TUniform(2^pks_noise_log2)
+ *   decompression BSK  a CLASSIC (grouping 1) bootstrapping key of LWE dimension k' N' encrypting the
+ *                bits of s' (flat, polynomial-major) under the big GLWE key, in fhe_generate_keys' word
+ *                layout and gadget form -- classic even when the main key is multi-bit.
+ * A seeded form of this key does not exist. */
+typedef struct fhe_compression_key fhe_compression_key;
+/* Draws everything from ck's encryption stream, in this order and before any threaded pass: k' N' secret
+ * words (bit 0 of each), the packing KSK's rows in order (k' N' mask words, then N' noise words, per row),
+ * the BSK's (q, rho) rows in order (2048 mask words, then 2048 noise words):
+ *   k' N' + 2048 pks_level (k' + 1) N' + 8192 k' N' stream words (u64)
+ * whatever the number of host threads, so a serialized client key continues right after them.
+ * params = NULL: the defaults. */
+int fhe_compression_keys_generate(fhe_client_key* ck, const fhe_compression_params* params,
+                                  fhe_compression_private_key** priv, fhe_compression_key** key);
+int fhe_compression_key_params(const fhe_compression_key* key, fhe_params* main, fhe_compression_params* comp);
+int fhe_compression_private_key_params(const fhe_compression_private_key* priv, fhe_params* main,
+                                       fhe_compression_params* comp);
+/* raw key material (tests): sizes in u64 words; either buffer may be NULL with length 0 */
+int fhe_compression_key_export(const fhe_compression_key* key, uint64_t* pksk, size_t pksk_len, uint64_t* bsk,
+                               size_t bsk_len);
+int fhe_compression_private_key_export(const fhe_compression_private_key* priv, uint64_t* sk, size_t len);
+void fhe_compression_private_key_destroy(fhe_compression_private_key* priv);
+void fhe_compression_key_destroy(fhe_compression_key* key);
+/* Wire formats: kinds 7 (private key), 8 (compression key), 9 (compressed list) of the keys' framed,
+ * checksummed format; size-query convention as above.  Every reader checks the parameter ranges and the
+ * exact payload length of the parsed parameters before it allocates, and refuses every other kind.
+ * tfhe-rs' wire format is not reproduced (parity unpinned). */
+int fhe_compression_private_key_serialize(const fhe_compression_private_key* priv, uint8_t* buf, size_t cap,
+                                          size_t* len);
+int fhe_compression_private_key_deserialize(const uint8_t* buf, size_t len, fhe_compression_private_key** priv);
+int fhe_compression_key_serialize(const fhe_compression_key* key, uint8_t* buf, size_t cap, size_t* len);
+int fhe_compression_key_deserialize(const uint8_t* buf, size_t len, fhe_compression_key** key);
+
+/* CompressedCiphertextList holding ONE value.  Host object, needs no context.  Wire (kind 9): main params,
+ * compression params (7 x u32), u32 form (FHE_SEEDED_RADIX / FHE_SEEDED_BIGUINT semantics), u32 count
+ * (num_bits or nlimbs), u32 B (blocks), B degree bytes (each < 16), then per GLWE g = 0.. in order its
+ * 12-bit values packed little-endian bit-contiguously (value i at bits [12 i, 12 i + 12)): k' N' mask
+ * values, polynomial-major, then b_g = min(L, B - g L) bodies; every GLWE starts on a byte boundary:
+ *   32 + 36 + 28 + 12 + B + sum_g ceil(12 (k' N' + b_g) / 8)  bytes. */
+typedef struct fhe_compressed_list fhe_compressed_list;
+/* The packing keyswitch on the host -- the word-for-word definition of the GPU path, and what a server
+ * without a GPU uses: cts = nblocks x 2049 words, degrees = nblocks bytes (< 16), form / count as above
+ * (count / 2, or 16 count, must equal nblocks). */
+int fhe_compress_host(const fhe_compression_key* key, const uint64_t* cts, size_t nblocks, const uint8_t* degrees,
+                      uint32_t form, uint32_t count, fhe_compressed_list** out);
+int fhe_compressed_info(const fhe_compressed_list* x, uint32_t* form, uint32_t* count, size_t* nblocks);
+/* the parameter sets that travel with the list; either output may be NULL */
+int fhe_compressed_params(const fhe_compressed_list* x, fhe_params* main, fhe_compression_params* comp);
+int fhe_compressed_serialize(const fhe_compressed_list* x, uint8_t* buf, size_t cap, size_t* len);
+int fhe_compressed_deserialize(const uint8_t* buf, size_t len, fhe_compressed_list** out);
+void fhe_compressed_destroy(fhe_compressed_list* x);
+/* Client side, no GPU and no context: per block, phase = body_t - sum_c (A_c * s'_c)[t] mod 2^12, value =
+ * round(phase / 2^7) mod 16; assembled as fhe_radix_decrypt does (blocks above degree 3 carry into their
+ * neighbours), mod 2^bits.  nwords >= ceil(bits / 64), bits = num_bits or 32 nlimbs. */
+int fhe_compressed_decrypt(const fhe_compression_private_key* priv, const fhe_compressed_list* x, uint64_t* words,
+                           size_t nwords);
+/* Installs the key for fhe_*_compress / fhe_compressed_expand_* of this context: after fhe_set_server_key,
+ * and dropped by the next server-key install (then FHE_ERR_NO_KEY from those calls).  FHE_ERR_INVALID, with
+ * the differing field named, if the key's main parameters are not the installed server key's. */
+int fhe_set_compression_key(fhe_ctx* ctx, const fhe_compression_key* key);
+/* CompressedCiphertextListBuilder::push(x).build(): flushes what x depends on (no collective: rank-local
+ * under a communicator), then three gfx950 kernels -- digits, int8 matrix-core contraction against the
+ * packing key's byte planes, rotate / modulus switch / pack -- and one download.  Byte-identical to
+ * fhe_compress_host on the exported blocks. */
+int fhe_radix_compress(fhe_ctx* ctx, const fhe_radix* x, fhe_compressed_list** out);
+int fhe_biguint_compress(fhe_ctx* ctx, const fhe_biguint* x, fhe_compressed_list** out);
+/* CompressedCiphertextList::get: fresh block slots (noise 1, degree from the degree byte), stream-ordered
+ * like fhe_seeded_expand_radix: one unpack + sample-extract kernel, then the existing blind rotate under the
+ * decompression key with the identity table. */
+int fhe_compressed_expand_radix(fhe_ctx* ctx, const fhe_compressed_list* x, fhe_radix** out);
+int fhe_compressed_expand_biguint(fhe_ctx* ctx, const fhe_compressed_list* x, fhe_biguint** out);
+/* Test hook: the unpack + sample-extract kernel alone.  rows = nblocks x (k' N' + 1) words (each stored value
+ * << 52), host pointer; synchronous. */
+int fhe_compressed_extract_rows(fhe_ctx* ctx, const fhe_compressed_list* x, uint64_t* rows, size_t nwords);
+
 /* ------------------------------------------------------------------- Schnorr / BIP-340 */
 /* The caller of the hot path (src/schnorr.rs).  32-byte scalars are big-endian.  The plaintext
  * EC / hash steps run on the host; the FHE block s = k + e*d runs on the GPU engine. */
