@@ -1586,3 +1586,77 @@ int fhe_compressed_extract_rows(fhe_ctx* c, const fhe_compressed_list* x, uint64
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------- compact ciphertext lists
+// tfhe-rs' CompactCiphertextList::expand (public_key.h): the device ends of it.  The host ends (key generation,
+// encryption under the public key, the wire kinds, fhe_compact_list_expand_host, fhe_compact_list_decrypt) are
+// in public_key.cpp.
+namespace {
+// the checks of every GPU expansion, before anything is allocated or launched
+int compact_expand_check(fhe_ctx* c, const fhe_compact_list* x) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x) return invalid("null compact list");
+    uint32_t have = 0, want = 0;
+    if (const char* f = params_differ(x->params, c->p, &have, &want))
+        return invalid(std::string("compact list's ") + f + " (" + std::to_string(have) +
+                       ") differs from the context's server key (" + std::to_string(want) + ")");
+    return FHE_OK;
+}
+int compact_value_check(fhe_ctx* c, const fhe_compact_list* x, uint32_t index, uint32_t form) {
+    int rc = compact_expand_check(c, x);
+    if (rc) return rc;
+    if (index >= x->values.size())
+        return invalid("compact list: value index " + std::to_string(index) + " out of range (the list holds " +
+                       std::to_string(x->values.size()) + ")");
+    if (x->values[index].form != form)
+        return invalid("compact list: value " + std::to_string(index) +
+                       (form == FHE_SEEDED_RADIX ? " holds a BigUintFHE, not a radix integer"
+                                                 : " holds a radix integer, not a BigUintFHE"));
+    return FHE_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fhe_compact_list_expand_radix(fhe_ctx* c, const fhe_compact_list* x, uint32_t index, fhe_radix** out) {
+    int rc = compact_value_check(c, x, index, FHE_SEEDED_RADIX);
+    if (rc) return rc;
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        Radix r;
+        r.blocks = c->engine->expand_compact(*x, index);
+        *out = wrap(std::move(r), x->values[index].count);
+        return FHE_OK;
+    });
+}
+
+int fhe_compact_list_expand_biguint(fhe_ctx* c, const fhe_compact_list* x, uint32_t index, fhe_biguint** out) {
+    int rc = compact_value_check(c, x, index, FHE_SEEDED_BIGUINT);
+    if (rc) return rc;
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        const Blocks all = c->engine->expand_compact(*x, index);
+        auto v = std::make_unique<fhe_biguint>();
+        for (size_t at = 0; at < all.size(); at += kLimbBlocks) {
+            Radix d;
+            d.blocks.assign(all.begin() + at, all.begin() + at + kLimbBlocks);
+            v->v.digits.push_back(std::move(d));
+        }
+        *out = v.release();
+        return FHE_OK;
+    });
+}
+
+int fhe_compact_list_extract_rows(fhe_ctx* c, const fhe_compact_list* x, uint64_t* rows, size_t nwords) {
+    int rc = compact_expand_check(c, x);
+    if (rc) return rc;
+    if ((!rows && x->ncoef()) || nwords < x->ncoef() * kBigCt)
+        return invalid("fhe_compact_list_extract_rows: buffer too small (ncoef x 2049 words)");
+    return guarded([&] {
+        c->engine->extract_compact_rows(*x, rows);
+        return FHE_OK;
+    });
+}
+
+}  // extern "C"

@@ -28,6 +28,12 @@ hipError_t launch_expand_ksk(const ChaChaKey& k, uint64_t* ksk, const uint64_t* 
 // that key in memory; npoly = 4 ggsw, bodies holds npoly / 2 polynomials
 hipError_t launch_expand_bsk_fourier(const ChaChaKey& k, const uint64_t* bodies, int npoly, const double2* W,
                                      const double2* psi, double2* out, hipStream_t s);
+// public_key.hip: for i < count, dst[i][0 .. 2048] = the big LWE sample-extracted at coefficient first + i of
+// the staged chunks (ca: 2048 words of C_A per chunk; coefficient g lies in chunk g / 2048 at t = g % 2048):
+// mask word u = ca[t - u] for u <= t, -ca[t - u + 2048] for u > t, body cb[i].  ca, cb and dst are device
+// arrays, every dst[i] a slot of 2049 words; the caller stages every chunk that [first, first + count) touches
+hipError_t launch_compact_extract(const uint64_t* ca, const uint64_t* cb, uint64_t* const* dst, uint32_t first, int count,
+                                  hipStream_t s);
 // ksk holds the KSK stream words ([rows][n + 1], rows = N * levels): bodies computed in place
 hipError_t launch_ksk_bodies(uint64_t* ksk, const uint64_t* lwe_sk, const uint64_t* glwe_sk, int n, int rows,
                              int levels, int base_log, int noise_log2, hipStream_t s);

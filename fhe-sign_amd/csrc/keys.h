@@ -104,6 +104,13 @@ constexpr uint64_t kSeededMaxBlocks = 1ull << 24;
 // a seeded ciphertext's block does, so row r's words are [2048 r, 2048 r + 2048) whatever n is.
 constexpr uint32_t kStreamSeededKsk = 102;
 constexpr uint32_t kStreamSeededBsk = 103;
+// Public-key encryption (public_key.h), the same nonce and counter layout.  kStreamPublicKeyMask is keyed by
+// the key's PUBLIC seed (mask polynomial A = its first 2048 u64 words).  The two others are keyed by a list's
+// SECRET encryption seed: chunk c's binary polynomial R is u64 words [32 c, 32 c + 32) of kStreamCompactBinary,
+// its noise words start at u64 word 4096 c of kStreamCompactNoise (2048 for E1, then one per used coefficient).
+constexpr uint32_t kStreamPublicKeyMask = 104;
+constexpr uint32_t kStreamCompactBinary = 105;
+constexpr uint32_t kStreamCompactNoise = 106;
 
 }  // namespace fhe
 

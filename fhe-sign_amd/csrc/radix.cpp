@@ -1136,6 +1136,75 @@ Blocks Engine::decompress(const fhe_compressed_list& x) {
     return out;
 }
 
+// ------------------------------------------------------------------ compact ciphertext lists (public key)
+Blocks Engine::compact_extract(const fhe_compact_list& x, size_t first, size_t n, const std::vector<uint32_t>& degrees) {
+    engine_check(host_mode_ == kDevice, "expand_compact on a host-only engine");
+    engine_check(first + n <= x.ncoef() && x.ncoef() <= kCompactMaxCoefs && x.ca.size() == (x.ncoef() + kPolySize - 1) / kPolySize * kPolySize,
+                 "compact list: coefficient range outside the list");
+    Blocks out(n);
+    if (n == 0) return out;
+    const size_t c0 = first / kPolySize, c1 = (first + n - 1) / kPolySize + 1;  // the chunks the range touches
+    const size_t ca_words = (c1 - c0) * kPolySize;
+    const size_t words = ca_words + 2 * n;  // C_A of the chunks, the bodies, then the slot pointers
+    if (words > up_cap_) {
+        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
+        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
+        d_up_ = nullptr;
+        up_cap_ = 0;
+        hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc upload");
+        up_cap_ = words;
+    }
+    std::vector<uint64_t*> dst(n);
+    for (size_t i = 0; i < n; ++i) {
+        out[i].slot = pool_->alloc();
+        out[i].degree = degrees[i];
+        out[i].noise = 1;
+        dst[i] = out[i].slot->p;
+    }
+    uint64_t* d_cb = d_up_ + ca_words;
+    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_cb + n);
+    hip_check(hipMemcpyAsync(d_up_, x.ca.data() + c0 * kPolySize, ca_words * 8, hipMemcpyHostToDevice, ctx_->stream),
+              "compact masks");
+    hip_check(hipMemcpyAsync(d_cb, x.cb.data() + first, n * 8, hipMemcpyHostToDevice, ctx_->stream), "compact bodies");
+    hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
+              "compact slots");
+    hip_check(launch_compact_extract(d_up_, d_cb, d_dst, (uint32_t)(first - c0 * kPolySize), (int)n, ctx_->stream),
+              "compact extraction");
+    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
+    return out;
+}
+
+Blocks Engine::expand_compact(const fhe_compact_list& x, size_t value) {
+    engine_check(value < x.values.size(), "compact list: value index out of range");
+    const fhe_compact_list::Value& v = x.values[value];
+    std::vector<uint32_t> degrees(v.ncoef);
+    for (size_t q = 0; q < v.ncoef; ++q) degrees[q] = compact_degree(x, v, v.first + q);
+    Blocks coefs = compact_extract(x, v.first, v.ncoef, degrees);
+    if (!x.packed) return coefs;
+    // one level: block 2 q = x_q & 3, block 2 q + 1 = x_q >> 2
+    const uint32_t mc = ctx_->p.msg_carry();
+    std::vector<uint32_t> lo(mc), hi(mc);
+    for (uint32_t m = 0; m < mc; ++m) {
+        lo[m] = m & 3;
+        hi[m] = m >> 2;
+    }
+    std::vector<PbsItem> items(v.nblocks);
+    for (size_t k = 0; k < v.nblocks; ++k) {
+        items[k].terms = {{coefs[k / 2], 1}};
+        items[k].table = (k & 1) ? hi : lo;
+    }
+    return run(items);
+}
+
+void Engine::extract_compact_rows(const fhe_compact_list& x, uint64_t* rows) {
+    const size_t n = x.ncoef();
+    if (n == 0) return;
+    const Blocks all = compact_extract(x, 0, n, std::vector<uint32_t>(n, 3));
+    std::vector<const Block*> ptrs(n);
+    for (size_t i = 0; i < n; ++i) ptrs[i] = &all[i];
+    download_many(ptrs, rows);
+}
+
 Blocks Engine::upload_deferred(size_t n, uint32_t degree, std::function<std::vector<uint64_t>()> fill) {
     run_before_launch();  // an earlier deferred upload first (one at a time)
     Blocks out(n);

@@ -22,6 +22,7 @@
 
 #include "context.h"
 #include "kernels.h"
+#include "public_key.h"
 
 namespace fhe {
 
@@ -203,6 +204,17 @@ public:
     Blocks decompress(const fhe_compressed_list& x);
     // the unpack + sample-extract kernel alone: n x (k' N' + 1) words to the host (tests)
     void extract_rows(const fhe_compressed_list& x, uint64_t* rows);
+    // A compact ciphertext list's value (public_key.h) expanded on the device, modelled on expand_seeded: fresh
+    // slots, the touched chunks' C_A (16 KB each), the bodies and the slot pointers staged through the upload
+    // buffer, public_key.hip's sample extraction into the slots -- word for word expand_compact_host's rows.
+    // Stream-ordered like an upload: no flush, no collective (under a communicator every rank expands the same
+    // bytes).  Unpacked: the extracted blocks are the result (degree 3, noise 1).  Packed: a coefficient holds
+    // m_2i + 4 m_(2i+1) at degree 15, noise 1, and goes through run() as two items, x & 3 and x >> 2 -- recorded
+    // in the deferred graph, where they share levels with whatever else is pending; a lone last block (degree 3)
+    // folds to an alias by run()'s identity rule.  Device engines only.
+    Blocks expand_compact(const fhe_compact_list& x, size_t value);
+    // the extraction kernel alone over every coefficient of the list: ncoef x 2049 words to the host (tests)
+    void extract_compact_rows(const fhe_compact_list& x, uint64_t* rows);
     void download(const Block& b, uint64_t* ct);
     // the slot blocks' ciphertexts -> host, contiguous (one gather + one copy + one wait instead of a
     // round trip per block: the decryption of a 256-bit result is 128-144 blocks)
@@ -289,6 +301,8 @@ private:
         }
     }
     PbsDesc* stage_desc(size_t n, PbsDesc** dev);
+    // coefficients [first, first + n) of x sample-extracted into fresh slots (degrees as given, noise 1)
+    Blocks compact_extract(const fhe_compact_list& x, size_t first, size_t n, const std::vector<uint32_t>& degrees);
 };
 
 void engine_check(bool ok, const char* what);

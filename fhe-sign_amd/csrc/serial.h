@@ -21,6 +21,10 @@
 //           words; 8: the packing KSK u64[2048][pks_level][k' + 1][N'], the decompression BSK u64[k' N'][2][2][2048];
 //           9: u32 form | u32 count | u32 B | B degree bytes | per GLWE the 12-bit stream of k' N' + b_g values,
 //           each GLWE from a byte boundary -- 108 + B + sum_g ceil(12 (k' N' + b_g) / 8) bytes in all.
+//   kind 10 (public key, public_key.cpp): params | 32 seed bytes | 2048 u64 body words -- 16,484 bytes in all.
+//   kind 11 (compact ciphertext list, public_key.cpp): params | u32 packed (0 / 1) | u32 nvalues | per value
+//           u32 form, u32 count | per chunk 2048 u64 C_A words | ncoef u64 C_B words -- 76 + 8 nvalues +
+//           8 (2048 nchunks + ncoef) bytes in all; ncoef and nchunks follow from the value table.
 // Readers check magic, version, kind, length, checksum, parameter ranges and every count before
 // touching memory, and refuse block metadata (degree, noise) outside the radix layer's budget, so a
 // corrupted or hostile buffer fails with FHE_ERR_INVALID instead of poisoning the scheduler.
@@ -36,7 +40,8 @@
 namespace fhe::ser {
 
 enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4, kSeeded = 5, kSeededServerKey = 6,
-                       kCompressionPrivateKey = 7, kCompressionKey = 8, kCompressedList = 9 };
+                       kCompressionPrivateKey = 7, kCompressionKey = 8, kCompressedList = 9,
+                       kPublicKey = 10, kCompactList = 11 };
 constexpr uint32_t kVersion = 2;  // 2: params carry the blind-rotation grouping (9th word); 1 still read
 constexpr size_t kHeaderBytes = 32;
 
@@ -60,7 +65,7 @@ struct Reader {
     uint32_t version = kVersion;  // of the frame (unframe sets it)
     bool take(void* dst, size_t k) {
         if (!ok || n - off < k) return ok = false;
-        memcpy(dst, p + off, k);
+        if (k) memcpy(dst, p + off, k);  // an empty vector's data() may be null
         off += k;
         return true;
     }

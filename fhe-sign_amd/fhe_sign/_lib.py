@@ -249,6 +249,31 @@ _SIGNATURES = [
     ("fhe_compressed_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_compressed_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_compressed_extract_rows", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_public_key_generate", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("fhe_public_key_params", C.c_int, [C.c_void_p, C.POINTER(FheParams)]),
+    ("fhe_public_key_export", C.c_int, [C.c_void_p, u8p, u64p, C.c_size_t]),
+    ("fhe_public_key_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_public_key_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_public_key_destroy", None, [C.c_void_p]),
+    ("fhe_compact_builder_new", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_compact_builder_push_radix", C.c_int, [C.c_void_p, u64p, C.c_uint32]),
+    ("fhe_compact_builder_push_biguint", C.c_int, [C.c_void_p, u32p, C.c_size_t]),
+    ("fhe_compact_builder_build", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("fhe_compact_builder_destroy", None, [C.c_void_p]),
+    ("fhe_compact_list_info", C.c_int,
+     [C.c_void_p, C.POINTER(C.c_int), u32p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("fhe_compact_list_value_info", C.c_int,
+     [C.c_void_p, C.c_uint32, u32p, u32p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("fhe_compact_list_params", C.c_int, [C.c_void_p, C.POINTER(FheParams)]),
+    ("fhe_compact_list_export", C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t]),
+    ("fhe_compact_list_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_compact_list_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_compact_list_destroy", None, [C.c_void_p]),
+    ("fhe_compact_list_expand_host", C.c_int, [C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_compact_list_decrypt", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u64p, C.c_size_t]),
+    ("fhe_compact_list_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("fhe_compact_list_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("fhe_compact_list_extract_rows", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t]),
     ("fhe_schnorr_public_key", C.c_int, [u8p, u8p]),
     ("fhe_schnorr_compute_nonce", C.c_int, [u8p, u8p, C.c_size_t, u8p, u8p]),
     ("fhe_schnorr_sign_with_k0", C.c_int, [u8p, C.c_size_t, u8p, u8p, u8p]),

@@ -164,6 +164,55 @@ class CompressedServerKey:
         return ServerKey(h, self.params)
 
 
+class CompactPublicKey:
+    """tfhe-rs' CompactPublicKey: a public 32-byte mask seed and the body polynomial B = A S + E under the
+    client's big key (include/fhe_rocm.h "public-key encryption").  A host object, about 16.5 KB serialized;
+    whoever holds it encrypts with CompactCiphertextList.builder(pk), no secret involved."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self.params = FheParams()
+        check(load().fhe_public_key_params(handle, C.byref(self.params)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_public_key_destroy(self._h)
+            self._h = None
+
+    @classmethod
+    def new(cls, client_key: "ClientKey", seed=None) -> "CompactPublicKey":
+        """advances client_key's encryption stream by exactly 2048 words; `seed` (32 bytes, PUBLIC) is for
+        tests, None draws it from the OS"""
+        if seed is not None:
+            seed = bytes(seed)
+            if len(seed) != 32:
+                raise ValueError("a mask seed is 32 bytes")
+        h = C.c_void_p()
+        check(load().fhe_public_key_generate(client_key.handle, seed, C.byref(h)))
+        return cls(h)
+
+    def export(self):
+        """(the 32 seed bytes, the 2048 body words)"""
+        seed = (C.c_uint8 * 32)()
+        body = np.zeros(2048, np.uint64)
+        check(load().fhe_public_key_export(self._h, seed, ptr(body), body.size))
+        return bytes(seed), body
+
+    def serialize(self) -> bytes:
+        """16,484 bytes: frame, params, seed, 2048 body words"""
+        return serialize_with(load().fhe_public_key_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes) -> "CompactPublicKey":
+        h = C.c_void_p()
+        check(load().fhe_public_key_deserialize(data, len(data), C.byref(h)))
+        return cls(h)
+
+
 def default_compression_params() -> CompressionParams:
     p = CompressionParams()
     check(load().fhe_compression_params_default(C.byref(p)))

@@ -638,6 +638,153 @@ FheUint.compress = _compress_radix
 BigUintFHE.compress = _compress_biguint
 
 
+class CompactCiphertextListBuilder:
+    """CompactCiphertextList::builder(&pk): push values, then build() or build_packed().  Needs the public
+    key only -- no client key, no context."""
+
+    def __init__(self, public_key):
+        self._h = C.c_void_p()
+        check(load().fhe_compact_builder_new(public_key.handle, C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_compact_builder_destroy(self._h)
+            self._h = None
+
+    def push(self, value: int, bits: int):
+        """a radix integer of `bits` bits (FheUint)"""
+        w = _words(value, bits) if bits > 0 else np.zeros(1, np.uint64)
+        check(load().fhe_compact_builder_push_radix(self._h, ptr(w), bits))
+        return self
+
+    def push_biguint(self, value: int):
+        """a BigUintFHE: 16 blocks per u32 limb, no leading zero limb (0 is the empty vector)"""
+        limbs = np.array(to_u32_digits(value), dtype=np.uint32)
+        check(load().fhe_compact_builder_push_biguint(self._h, ptr(limbs, C.c_uint32), limbs.size))
+        return self
+
+    def _build(self, packed, seed):
+        h = C.c_void_p()
+        check(load().fhe_compact_builder_build(self._h, packed, _mask_seed(seed), C.byref(h)))
+        return CompactCiphertextList(h)
+
+    def build(self, seed=None):
+        """one block per coefficient.  `seed` is the SECRET encryption seed: tests only; None draws it from
+        the OS, and it is kept nowhere"""
+        return self._build(0, seed)
+
+    def build_packed(self, seed=None):
+        """two blocks per coefficient; expand() splits them with one bootstrap level.  `seed` as in build()"""
+        return self._build(1, seed)
+
+
+class CompactCiphertextList:
+    """tfhe-rs' CompactCiphertextList: values encrypted under a CompactPublicKey, one GLWE (C_A, C_B) per
+    2048 coefficients (include/fhe_rocm.h "public-key encryption").  A host object: serialize / deserialize /
+    expand_host / decrypt(client_key) need no context; expand() brings the values onto this thread's GPU."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_compact_list_destroy(self._h)
+            self._h = None
+
+    @staticmethod
+    def builder(public_key) -> CompactCiphertextListBuilder:
+        return CompactCiphertextListBuilder(public_key)
+
+    def _info(self):
+        packed, nv, nc, nch = C.c_int(), C.c_uint32(), C.c_size_t(), C.c_size_t()
+        check(load().fhe_compact_list_info(self._h, C.byref(packed), C.byref(nv), C.byref(nc), C.byref(nch)))
+        return bool(packed.value), int(nv.value), int(nc.value), int(nch.value)
+
+    @property
+    def packed(self) -> bool:
+        return self._info()[0]
+
+    def __len__(self):
+        return self._info()[1]
+
+    @property
+    def ncoef(self) -> int:
+        return self._info()[2]
+
+    @property
+    def nchunks(self) -> int:
+        return self._info()[3]
+
+    def value_info(self, i: int):
+        """(form, count, nblocks, first coefficient, coefficients) of value i"""
+        form, count, nb, first, nc = C.c_uint32(), C.c_uint32(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(load().fhe_compact_list_value_info(self._h, i, C.byref(form), C.byref(count), C.byref(nb), C.byref(first),
+                                                 C.byref(nc)))
+        return int(form.value), int(count.value), int(nb.value), int(first.value), int(nc.value)
+
+    def export(self):
+        """(C_A as (nchunks, 2048), C_B as (ncoef,))"""
+        _, _, nc, nch = self._info()
+        ca, cb = np.zeros((nch, 2048), np.uint64), np.zeros(nc, np.uint64)
+        check(load().fhe_compact_list_export(self._h, ptr(ca), ca.size, ptr(cb), cb.size))
+        return ca, cb
+
+    def serialize(self) -> bytes:
+        """76 + 8 nvalues + 8 (2048 nchunks + ncoef) bytes"""
+        return serialize_with(load().fhe_compact_list_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes):
+        h = C.c_void_p()
+        check(load().fhe_compact_list_deserialize(data, len(data), C.byref(h)))
+        return cls(h)
+
+    def expand_host(self) -> np.ndarray:
+        """the sample-extracted big LWEs, (ncoef, 2049): the definition of what expand() puts on the GPU"""
+        out = np.zeros((self.ncoef, 2049), np.uint64)
+        check(load().fhe_compact_list_expand_host(self._h, ptr(out), out.size))
+        return out
+
+    def decrypt_value(self, client_key, i: int) -> int:
+        form, count, _, _, _ = self.value_info(i)
+        bits = count if form == SEEDED_RADIX else 32 * count
+        n = max(1, (bits + 63) // 64)
+        w = np.zeros(n, np.uint64)
+        check(load().fhe_compact_list_decrypt(client_key.handle, self._h, i, ptr(w), n))
+        return sum(int(w[k]) << (64 * k) for k in range(n))
+
+    def decrypt(self, client_key) -> list:
+        """every value, on the client (no GPU): phase, round, unpack"""
+        return [self.decrypt_value(client_key, i) for i in range(len(self))]
+
+    def expand_value(self, i: int, ctx=None):
+        """value i as FheUint or BigUintFHE on ctx (default: this thread's context)"""
+        ctx = ctx or _ctx()
+        form, count = self.value_info(i)[:2]
+        h = C.c_void_p()
+        if form == SEEDED_BIGUINT:
+            check(load().fhe_compact_list_expand_biguint(ctx.handle, self._h, i, C.byref(h)))
+            return BigUintFHE(h)
+        check(load().fhe_compact_list_expand_radix(ctx.handle, self._h, i, C.byref(h)))
+        return FheUint._wrap(h, count)
+
+    def expand(self, ctx=None) -> list:
+        """CompactCiphertextList::expand: the values in push order.  A packed list records its unpacking
+        bootstraps (one level) in the context's deferred graph"""
+        return [self.expand_value(i, ctx) for i in range(len(self))]
+
+    def extract_rows(self, ctx=None) -> np.ndarray:
+        """test hook: the extraction kernel's rows, (ncoef, 2049)"""
+        ctx = ctx or _ctx()
+        out = np.zeros((self.ncoef, 2049), np.uint64)
+        check(load().fhe_compact_list_extract_rows(ctx.handle, self._h, ptr(out), out.size))
+        return out
+
+
 LEVEL_SPLIT = 1 << 31  # FHE_LEVEL_SPLIT: the level was fanned out over the ranks
 
 

@@ -679,6 +679,92 @@ int fhe_compressed_expand_biguint(fhe_ctx* ctx, const fhe_compressed_list* x, fh
  * << 52), host pointer; synchronous. */
 int fhe_compressed_extract_rows(fhe_ctx* ctx, const fhe_compressed_list* x, uint64_t* rows, size_t nwords);
 
+/* ------------------------------------------------- public-key encryption (compact lists) */
+/* Encryption by a party that does not hold the secret key: tfhe-rs' CompactPublicKey::new(&client_key),
+ * CompactCiphertextList::builder(&pk).push(..).build_packed() and .expand().  The default parameters encrypt
+ * under the big key of dimension k N = 2048, a power of two, so the compact scheme applies as it is (no
+ * dedicated parameters, no casting keyswitch).  Polynomials live in Z_2^64[X] / (X^2048 + 1); S is the
+ * client's big key as a polynomial (coefficient order = the big LWE key's).
+ *   key     a PUBLIC 32-byte mask seed and a body polynomial: A = the first 2048 u64 words of the ChaCha20
+ *           stream whose key is the seed and whose nonce is {104, "ROCM", 0}; B = A S + E, E_j from the j-th of
+ *           the next 2048 words of the client key's encryption stream (tuniform at glwe_noise_log2): the key
+ *           advances by exactly 2048 words, so a serialized client key continues correctly.  16,484 bytes.
+ *   list    nvalues values, each a radix of num_bits or a BigUintFHE of nlimbs x 16 blocks.  A value's 2-bit
+ *           blocks become coefficients in order: one block per coefficient (build), or m_2i + 4 m_(2i+1)
+ *           (build_packed: an odd last block stands alone, every value starts on a fresh coefficient).
+ *           Coefficients fill chunks of 2048.  Chunk c takes, from ChaCha20 streams keyed by the ENCRYPTION
+ *           SEED: R (bit i = bit i & 63 of u64 word 32 c + (i >> 6), nonce {105, "ROCM", 0}), E1 (2048 words
+ *           from u64 word 4096 c, nonce {106, "ROCM", 0}) and E2 (the words after E1, one per used
+ *           coefficient), and holds C_A = A R + E1 and C_B[j] = (B R)[j] + E2[j] + delta m_j.  A packed 256-bit
+ *           value is 2048 x 8 + 64 x 8 = 16,896 payload bytes, against 2.1 MB in the full form.
+ *   expand  coefficient t of a chunk is the big LWE with mask word u = C_A[t - u] (u <= t), -C_A[t - u + 2048]
+ *           (u > t) and body C_B[t]; its phase error E R + E2 - E1 S is below 2^30 in absolute value.
+ * THE ENCRYPTION SEED IS SECRET: IT GIVES AWAY R, AND WITH R EVERY MESSAGE OF THE LIST.  IT IS NEVER STORED IN
+ * THE LIST AND MUST NEVER BE USED TWICE.  Pass encryption_seed = NULL (32 bytes from getrandom()) outside
+ * tests; a given seed is for tests only.  The key's mask seed is public, but one seed serves one key only
+ * (mask_seed = NULL: getrandom()).  A list holds at most 2^16 values and 2^24 coefficients.  tfhe-rs' bytes
+ * are not reproduced (parity unpinned), zero-knowledge proofs of encryption are out of scope. */
+typedef struct fhe_public_key fhe_public_key;
+typedef struct fhe_compact_builder fhe_compact_builder;
+typedef struct fhe_compact_list fhe_compact_list;
+/* CompactPublicKey::new */
+int fhe_public_key_generate(fhe_client_key* ck, const uint8_t mask_seed[32] /* NULL: OS entropy */,
+                            fhe_public_key** out);
+int fhe_public_key_params(const fhe_public_key* pk, fhe_params* params);
+/* the seed (32 bytes) and the body polynomial (nwords >= 2048); either output may be NULL */
+int fhe_public_key_export(const fhe_public_key* pk, uint8_t seed[32], uint64_t* body, size_t nwords);
+/* Wire format (kind 10 of the framed, checksummed format): params, 32 seed bytes, 2048 u64 bodies.  The
+ * reader checks magic, version, kind, length, checksum, parameter ranges and the payload length before it
+ * allocates. */
+int fhe_public_key_serialize(const fhe_public_key* pk, uint8_t* buf, size_t cap, size_t* len);
+int fhe_public_key_deserialize(const uint8_t* buf, size_t len, fhe_public_key** out);
+void fhe_public_key_destroy(fhe_public_key* pk);
+/* CompactCiphertextList::builder(&pk): takes a copy of the key; no client key, no context.  push: words and
+ * num_bits as fhe_radix_encrypt, limbs as fhe_biguint_encrypt (nlimbs 0 is the empty vector, no coefficient). */
+int fhe_compact_builder_new(const fhe_public_key* pk, fhe_compact_builder** out);
+int fhe_compact_builder_push_radix(fhe_compact_builder* b, const uint64_t* words, uint32_t num_bits);
+int fhe_compact_builder_push_biguint(fhe_compact_builder* b, const uint32_t* limbs, size_t nlimbs);
+/* .build() (packed = 0) / .build_packed() (packed = 1); the builder may build again (use a fresh seed) */
+int fhe_compact_builder_build(const fhe_compact_builder* b, int packed,
+                              const uint8_t encryption_seed[32] /* SECRET; NULL: OS entropy */, fhe_compact_list** out);
+void fhe_compact_builder_destroy(fhe_compact_builder* b);
+/* any output may be NULL */
+int fhe_compact_list_info(const fhe_compact_list* x, int* packed, uint32_t* nvalues, size_t* ncoef, size_t* nchunks);
+/* value `index`: form (FHE_SEEDED_*), count (num_bits or nlimbs), its blocks, first coefficient and coefficients */
+int fhe_compact_list_value_info(const fhe_compact_list* x, uint32_t index, uint32_t* form, uint32_t* count,
+                                size_t* nblocks, size_t* first_coef, size_t* ncoef);
+int fhe_compact_list_params(const fhe_compact_list* x, fhe_params* params);
+/* C_A (2048 nchunks words) and C_B (ncoef words); either may be NULL */
+int fhe_compact_list_export(const fhe_compact_list* x, uint64_t* ca, size_t ca_words, uint64_t* cb, size_t cb_words);
+/* Wire format (kind 11): params, u32 packed, u32 nvalues, per value u32 form + u32 count, C_A, C_B --
+ * 76 + 8 nvalues + 8 (2048 nchunks + ncoef) bytes.  The reader checks magic, version, kind, length, checksum,
+ * parameter ranges, the flag, every form and count, and that the value table matches the payload length, all
+ * before it allocates anything of the list's size. */
+int fhe_compact_list_serialize(const fhe_compact_list* x, uint8_t* buf, size_t cap, size_t* len);
+int fhe_compact_list_deserialize(const uint8_t* buf, size_t len, fhe_compact_list** out);
+void fhe_compact_list_destroy(fhe_compact_list* x);
+/* The sample extraction on the host: rows = ncoef x 2049 words.  The word-for-word definition of the GPU
+ * kernel's output. */
+int fhe_compact_list_expand_host(const fhe_compact_list* x, uint64_t* rows, size_t nwords);
+/* Client side, no GPU: value `index` from its coefficients' phases (round, unpack), little-endian words
+ * (BigUintFHE: limb i at bits 32 i); nwords >= ceil(bits / 64).  FHE_ERR_INVALID with the field named if the
+ * list's parameters differ from the client key's. */
+int fhe_compact_list_decrypt(const fhe_client_key* ck, const fhe_compact_list* x, uint32_t index, uint64_t* words,
+                             size_t nwords);
+/* CompactCiphertextList::expand of value `index` on the GPU of ctx: fresh block slots filled by a gfx950
+ * sample-extraction kernel from the staged C_A / C_B (stream-ordered like fhe_seeded_expand_radix: no flush, no
+ * collective -- under the multi-GPU fan-out every rank must expand the same bytes).  An unpacked list's
+ * extracted blocks are the result (degree 3, noise 1).  A packed list's coefficients (degree 15, noise 1) are
+ * split by two lookups each, x & 3 and x >> 2, recorded in the deferred bootstrap graph: one level, shared with
+ * whatever else is pending.  FHE_ERR_NO_KEY without an installed server key; FHE_ERR_INVALID for an index out
+ * of range, the other form, and parameters that differ from the installed key's (the message names the
+ * field), before anything is launched. */
+int fhe_compact_list_expand_radix(fhe_ctx* ctx, const fhe_compact_list* x, uint32_t index, fhe_radix** out);
+int fhe_compact_list_expand_biguint(fhe_ctx* ctx, const fhe_compact_list* x, uint32_t index, fhe_biguint** out);
+/* Test hook: the extraction kernel alone over every coefficient.  rows = ncoef x 2049 words, host pointer;
+ * flushes and waits like a download. */
+int fhe_compact_list_extract_rows(fhe_ctx* ctx, const fhe_compact_list* x, uint64_t* rows, size_t nwords);
+
 /* ------------------------------------------------------------------- Schnorr / BIP-340 */
 /* The caller of the hot path (src/schnorr.rs).  32-byte scalars are big-endian.  The plaintext
  * EC / hash steps run on the host; the FHE block s = k + e*d runs on the GPU engine. */
