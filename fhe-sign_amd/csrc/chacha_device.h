@@ -1,6 +1,7 @@
 // chacha_device.h -- the ChaCha20 block function (RFC 8439) on the device, shared by the key
-// generation stream kernel (keygen.hip), the seeded-ciphertext expansion (seeded.hip) and the seeded
-// server key's install (seeded_key.hip); the latter two also share the quad exchange for coalesced stores.
+// generation stream kernel (keygen.hip), the seeded-ciphertext expansion (seeded.hip), the seeded server
+// key's install (seeded_key.hip) and the seeded compression key's (seeded_compression.hip); seeded.hip and
+// seeded_key.hip also share the quad exchange for coalesced stores.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

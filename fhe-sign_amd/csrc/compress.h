@@ -45,6 +45,10 @@ struct CompParams {
     }
     // words of the client key's encryption stream fhe_compression_keys_generate consumes
     size_t stream_words() const { return (size_t)lwe_dim() + pksk_words() + bsk_words(); }
+    // the seeded form (fhe_seeded_compression_key): body words, and the stream words its generation consumes
+    size_t pksk_body_words() const { return (size_t)kBigDim * ell * N; }
+    size_t bsk_body_words() const { return (size_t)lwe_dim() * 2 * kPolySize; }
+    size_t seeded_stream_words() const { return (size_t)lwe_dim() + pksk_body_words() + bsk_body_words(); }
     bool operator==(const CompParams& o) const {
         return k == o.k && N == o.N && L == o.L && beta == o.beta && ell == o.ell &&
                pks_noise_log2 == o.pks_noise_log2 && storage_log_modulus == o.storage_log_modulus;
@@ -84,6 +88,26 @@ struct fhe_compression_key {
     std::vector<uint64_t> bsk;   // [k' N'][row][poly][2048], standard domain, classic
 };
 
+// A seeded (compressed) compression key: tfhe-rs' CompressedCompressionKey + CompressedDecompressionKey
+// (DESIGN.md 6e).  Host only.  Of the full key only the bodies are kept; every mask word is regenerated from
+// the PUBLIC seed, one row per 256 ChaCha blocks (2048 u64 words; k' N' <= 2048):
+//   packing KSK row r = j ell + l (stream kStreamSeededPksk): coefficient m of mask polynomial c < k' = u64 word
+//       2048 r + c N' + m; pksk_bodies[r N' ..] = B = sum_c A_c * s'_c + e, then B[0] += S_j << (64 - beta (l + 1))
+//   BSK GGSW q < k' N', row rho (stream kStreamSeededCbsk): mask polynomial A = u64 words [2048 (2 q + rho),
+//       + 2048); bsk_bodies[(2 q + rho) 2048 ..] = B = A * S + e, then row 1: B[0] += g s'_q; row 0: B[t] -=
+//       g s'_q S_t for every t (g = 1 << (64 - pbs_base_log)): the body form of row 0's gadget, as in
+//       fhe_seeded_server_key (keys.h) -- the expanded key's words differ from generate_compression_keys' for
+//       the same secrets, its phases do not.
+// One seed, one object: a seed is never reused for a second key, or for a seeded ciphertext, under the same
+// client key.
+struct fhe_seeded_compression_key {
+    fhe::Params params;
+    fhe::CompParams cp;
+    uint8_t seed[32] = {};
+    std::vector<uint64_t> pksk_bodies;  // [2048][ell][N']
+    std::vector<uint64_t> bsk_bodies;   // [k' N'][2][2048]
+};
+
 struct fhe_compressed_list {
     fhe::Params params;
     fhe::CompParams cp;
@@ -95,6 +119,15 @@ struct fhe_compressed_list {
 namespace fhe {
 void generate_compression_keys(fhe_client_key* ck, const CompParams& cp, fhe_compression_private_key* priv,
                                fhe_compression_key* key);
+// The seeded key of ck under the public `seed`.  Everything is drawn from ck->enc_rng before any threaded pass:
+// k' N' secret words (bit 0 of each: the s' generate_compression_keys draws from the same stream state), then
+// N' noise words per packing-key row in row order, then 2048 noise words per BSK row in (q, rho) order --
+// exactly CompParams::seeded_stream_words() words, whatever the number of host threads.
+void generate_seeded_compression_keys(fhe_client_key* ck, const CompParams& cp, const uint8_t seed[32],
+                                      fhe_compression_private_key* priv, fhe_seeded_compression_key* out);
+// The full key of a seeded one: masks regenerated, bodies in place.  The word-for-word definition of the
+// device install (seeded_compression.hip, seeded_key.hip).
+void expand_seeded_compression_key_host(const fhe_seeded_compression_key& sck, fhe_compression_key* key);
 // The definition of the device path (compress.hip), word for word: packed = CompParams::packed_bytes(B)
 // bytes.  Threaded over the blocks of a GLWE; the result does not depend on the thread count (every
 // T_i is computed alone, and the sum is taken mod 2^64).

@@ -166,6 +166,82 @@ void generate_compression_keys(fhe_client_key* ck, const CompParams& cp, fhe_com
     });
 }
 
+// ------------------------------------------------------------------------- seeded compression key
+namespace {
+// the seeded server key's row stride (keys.cpp): row r's mask words start at u64 word 2048 r of its stream
+constexpr uint64_t kRowWords = 2048;
+// fn(row, masks) for row < rows on the pool, `masks` seeked to the row's first word
+template <class F>
+void seeded_rows(const KeyWords& key, uint32_t stream, size_t rows, F&& fn) {
+    parallel_rows(rows, [&](size_t r) {
+        ChaChaStream masks(key, stream);
+        masks.seek((uint64_t)r * kRowWords * 2);  // in 32-bit stream words
+        fn(r, masks);
+    });
+}
+}  // namespace
+
+void generate_seeded_compression_keys(fhe_client_key* ck, const CompParams& cp, const uint8_t seed[32],
+                                      fhe_compression_private_key* priv, fhe_seeded_compression_key* out) {
+    const Params& p = ck->params;
+    const uint32_t kN = cp.lwe_dim(), Np = cp.N, N = kPolySize;
+    priv->params = out->params = p;
+    priv->cp = out->cp = cp;
+    std::memcpy(out->seed, seed, 32);
+    // every stream word first, in the documented order: secret, packing-KSK noise, BSK noise
+    priv->sk.resize(kN);
+    out->pksk_bodies.resize(cp.pksk_body_words());
+    out->bsk_bodies.resize(cp.bsk_body_words());
+    ck->enc_rng.fill_u64(priv->sk.data(), kN);
+    ck->enc_rng.fill_u64(out->pksk_bodies.data(), out->pksk_bodies.size());
+    ck->enc_rng.fill_u64(out->bsk_bodies.data(), out->bsk_bodies.size());
+    for (auto& v : priv->sk) v &= 1ull;
+    const KeyWords key = bytes_key(seed);
+    const uint64_t *sp = priv->sk.data(), *S = ck->glwe_sk.data();
+    seeded_rows(key, kStreamSeededPksk, (size_t)kBigDim * cp.ell, [&](size_t r, ChaChaStream& masks) {
+        std::vector<uint64_t> A(kN);
+        masks.fill_u64(A.data(), kN);
+        uint64_t* B = out->pksk_bodies.data() + r * Np;
+        for (uint32_t m = 0; m < Np; ++m) B[m] = (uint64_t)tuniform_of(B[m], cp.pks_noise_log2);
+        for (uint32_t c = 0; c < cp.k; ++c)
+            negacyclic_binary_mac_n(B, A.data() + (size_t)c * Np, sp + (size_t)c * Np, Np);
+        const uint32_t j = (uint32_t)(r / cp.ell), l = (uint32_t)(r % cp.ell);
+        B[0] += S[j] << (64 - cp.beta * (l + 1));
+    });
+    seeded_rows(key, kStreamSeededCbsk, (size_t)kN * 2, [&](size_t r, ChaChaStream& masks) {
+        std::vector<uint64_t> A(N);
+        masks.fill_u64(A.data(), N);
+        uint64_t* B = out->bsk_bodies.data() + r * N;
+        for (uint32_t m = 0; m < N; ++m) B[m] = (uint64_t)tuniform_of(B[m], p.glwe_noise_log2);
+        negacyclic_binary_mac_n(B, A.data(), S, N);
+        const uint64_t g = sp[r / 2] << (64 - p.pbs_base_log);
+        if (r % 2)
+            B[0] += g;
+        else  // row 0's gadget in body form: a regenerated mask cannot hold it (compress.h)
+            for (uint32_t t = 0; t < N; ++t) B[t] -= g * S[t];
+    });
+}
+
+void expand_seeded_compression_key_host(const fhe_seeded_compression_key& sck, fhe_compression_key* key) {
+    const CompParams& cp = sck.cp;
+    const uint32_t kN = cp.lwe_dim(), Np = cp.N, cols = cp.cols(), N = kPolySize;
+    key->params = sck.params;
+    key->cp = cp;
+    key->pksk.assign(cp.pksk_words(), 0);
+    key->bsk.assign(cp.bsk_words(), 0);
+    const KeyWords k = bytes_key(sck.seed);
+    seeded_rows(k, kStreamSeededPksk, (size_t)kBigDim * cp.ell, [&](size_t r, ChaChaStream& masks) {
+        uint64_t* row = key->pksk.data() + r * cols;
+        masks.fill_u64(row, kN);
+        std::memcpy(row + kN, sck.pksk_bodies.data() + r * Np, (size_t)Np * 8);
+    });
+    seeded_rows(k, kStreamSeededCbsk, (size_t)kN * 2, [&](size_t r, ChaChaStream& masks) {
+        uint64_t* A = key->bsk.data() + r * 2 * N;
+        masks.fill_u64(A, N);
+        std::memcpy(A + N, sck.bsk_bodies.data() + r * N, (size_t)N * 8);
+    });
+}
+
 void pack_keyswitch_host(const fhe_compression_key& key, const uint64_t* cts, size_t B, uint8_t* packed) {
     const CompParams& cp = key.cp;
     const uint32_t Np = cp.N, cols = cp.cols(), kN = cp.lwe_dim(), beta = cp.beta, ell = cp.ell;
@@ -393,6 +469,99 @@ int fhe_compression_key_deserialize(const uint8_t* buf, size_t len, fhe_compress
         return FHE_OK;
     });
 }
+
+// tfhe-rs' CompressedCompressionKey + CompressedDecompressionKey (compress.h fhe_seeded_compression_key).
+// Payload of kSeededCompressionKey: params, compression params, 32 seed bytes, the packing-key bodies, the BSK
+// body polynomials; no counts -- the parameters fix them.
+int fhe_compression_keys_generate_seeded(fhe_client_key* ck, const fhe_compression_params* params,
+                                         const uint8_t* mask_seed, fhe_compression_private_key** priv,
+                                         fhe_seeded_compression_key** sck) {
+    if (!ck || !priv || !sck) return invalid("null argument");
+    CompParams cp;
+    const char* why = nullptr;
+    if (params && !CompParams::from_c(*params, &cp, &why)) {
+        set_error(why);
+        return FHE_ERR_UNSUPPORTED;
+    }
+    uint8_t seed[32];
+    if (mask_seed) {
+        std::memcpy(seed, mask_seed, 32);
+    } else if (!os_entropy32(seed)) {
+        set_error("getrandom failed: no mask seed");
+        return FHE_ERR_UNSUPPORTED;
+    }
+    return guarded([&] {
+        auto a = std::make_unique<fhe_compression_private_key>();
+        auto b = std::make_unique<fhe_seeded_compression_key>();
+        generate_seeded_compression_keys(ck, cp, seed, a.get(), b.get());
+        *priv = a.release();
+        *sck = b.release();
+        return FHE_OK;
+    });
+}
+
+int fhe_seeded_compression_key_params(const fhe_seeded_compression_key* sck, fhe_params* main,
+                                      fhe_compression_params* comp) {
+    if (!sck) return FHE_ERR_INVALID;
+    if (main) *main = sck->params.to_c();
+    if (comp) *comp = sck->cp.to_c();
+    return FHE_OK;
+}
+
+int fhe_seeded_compression_key_serialize(const fhe_seeded_compression_key* sck, uint8_t* buf, size_t cap,
+                                         size_t* len) {
+    if (!sck || !len) return FHE_ERR_INVALID;
+    return guarded([&] {
+        ser::Writer w;
+        w.b.reserve(112 + (sck->pksk_bodies.size() + sck->bsk_bodies.size()) * 8);
+        w.params(sck->params);
+        write_cp(w, sck->cp);
+        w.raw(sck->seed, 32);
+        w.words(sck->pksk_bodies.data(), sck->pksk_bodies.size());
+        w.words(sck->bsk_bodies.data(), sck->bsk_bodies.size());
+        return ser::emit(ser::frame(ser::kSeededCompressionKey, w.b), buf, cap, len);
+    });
+}
+
+int fhe_seeded_compression_key_deserialize(const uint8_t* buf, size_t len, fhe_seeded_compression_key** out) {
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        ser::Reader r;
+        std::string why;
+        Params p;
+        CompParams cp;
+        if (!ser::unframe(buf, len, ser::kSeededCompressionKey, &r, &why) || !r.params(&p, &why) ||
+            !read_cp(r, &cp, &why))
+            return invalid(why);
+        // the length first: nothing is allocated unless the payload is exactly what the parameters need
+        if (r.n - r.off != 32 + (cp.pksk_body_words() + cp.bsk_body_words()) * 8)
+            return invalid("seeded compression key: payload length differs from what its parameters need");
+        auto k = std::make_unique<fhe_seeded_compression_key>();
+        k->params = p;
+        k->cp = cp;
+        k->pksk_bodies.resize(cp.pksk_body_words());
+        k->bsk_bodies.resize(cp.bsk_body_words());
+        if (!r.take(k->seed, 32) || !r.words(k->pksk_bodies.data(), k->pksk_bodies.size()) ||
+            !r.words(k->bsk_bodies.data(), k->bsk_bodies.size()) || !r.done())
+            return invalid("malformed seeded compression key");
+        *out = k.release();
+        return FHE_OK;
+    });
+}
+
+int fhe_seeded_compression_key_expand_host(const fhe_seeded_compression_key* sck, fhe_compression_key** out) {
+    if (!sck || !out) return invalid("null argument");
+    if (sck->pksk_bodies.size() != sck->cp.pksk_body_words() || sck->bsk_bodies.size() != sck->cp.bsk_body_words())
+        return invalid("seeded compression key: body counts differ from what its parameters need");
+    return guarded([&] {
+        auto k = std::make_unique<fhe_compression_key>();
+        expand_seeded_compression_key_host(*sck, k.get());
+        *out = k.release();
+        return FHE_OK;
+    });
+}
+
+void fhe_seeded_compression_key_destroy(fhe_seeded_compression_key* sck) { delete sck; }
 
 int fhe_compress_host(const fhe_compression_key* key, const uint64_t* cts, size_t nblocks, const uint8_t* degrees,
                       uint32_t form, uint32_t count, fhe_compressed_list** out) {

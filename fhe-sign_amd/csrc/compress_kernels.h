@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "keygen.h"
+
 namespace fhe {
 
 int pk_col_tiles(int cols);
@@ -13,6 +15,11 @@ size_t pk_digits_bytes(int count, int ell);
 int pk_out_stride(int k, int Np);
 // pksk u64 [2048][ell][cols] -> int8 [8][column tiles][32 ell][64][16] (once, at fhe_set_compression_key)
 hipError_t launch_pksk_to_planes(const uint64_t* pksk, int ell, int cols, int8_t* planes, hipStream_t s);
+// seeded_compression.hip: the same planes, byte for byte, of the packing key whose row r has u64 words
+// [2048 r, 2048 r + k Np) of the stream as its masks and bodies[r Np .. + Np) as its body, without that key
+// in memory; bodies is a device array of 2048 ell Np words
+hipError_t launch_expand_pksk_planes(const ChaChaKey& key, const uint64_t* bodies, int ell, int k, int Np,
+                                     int8_t* planes, hipStream_t s);
 // src[i] (device array of `count` slot pointers, 2049 words each) -> out[g * pk_out_stride + ..]: GLWE g's
 // k' N' mask values, then L body slots (the unused ones zero), 12 bits each.  digits: pk_digits_bytes(count,
 // ell); body: count words; P: count x (k' + 1) N' words.

@@ -763,6 +763,89 @@ int fhe_set_compression_key(fhe_ctx* c, const fhe_compression_key* key) {
     return FHE_OK;
 }
 
+// The seeded install: the bodies are the only upload.  seeded_compression.hip writes the packing key's byte
+// planes from seed + bodies (the u64 packing key is never allocated), seeded_key.hip's k_expand_bsk_fourier
+// generates the BSK mask polynomials inside the Fourier conversion.  Same device state as
+// fhe_set_compression_key of the host-expanded key.
+int fhe_set_compression_key_seeded(fhe_ctx* c, const fhe_seeded_compression_key* sck) {
+    if (!c || !sck) {
+        set_error("null argument to fhe_set_compression_key_seeded");
+        return FHE_ERR_INVALID;
+    }
+    if (!c->has_key || !c->engine) {
+        set_error("no server key installed: fhe_set_compression_key_seeded comes after fhe_set_server_key");
+        return FHE_ERR_NO_KEY;
+    }
+    uint32_t have = 0, want = 0;
+    if (const char* f = params_differ(sck->params, c->p, &have, &want)) {
+        set_error(std::string("seeded compression key's ") + f + " (" + std::to_string(have) +
+                  ") differs from the context's server key (" + std::to_string(want) + ")");
+        return FHE_ERR_INVALID;
+    }
+    CompParams cp;
+    const char* why = nullptr;
+    if (!CompParams::from_c(sck->cp.to_c(), &cp, &why) || sck->pksk_bodies.size() != cp.pksk_body_words() ||
+        sck->bsk_bodies.size() != cp.bsk_body_words()) {
+        set_error(why ? why : "seeded compression key: body counts differ from what its parameters need");
+        return FHE_ERR_UNSUPPORTED;
+    }
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    int rc = c->release_compression();
+    if (rc) return rc;
+    c->cp = cp;
+    const KeyWords key = bytes_key(sck->seed);
+    uint64_t *d_pb = nullptr, *d_bb = nullptr;
+    FHE_HIP_CHECK(hipMalloc(&d_pb, sck->pksk_bodies.size() * 8));
+    std::unique_ptr<void, DeviceFree> pb_guard(d_pb);  // both freed behind the wait below
+    FHE_HIP_CHECK(hipMalloc(&d_bb, sck->bsk_bodies.size() * 8));
+    std::unique_ptr<void, DeviceFree> bb_guard(d_bb);
+    auto body = [&]() -> int {
+        FHE_HIP_CHECK(hipMalloc(&c->d_pk_planes, fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
+        FHE_HIP_CHECK(hipMemcpyAsync(d_pb, sck->pksk_bodies.data(), sck->pksk_bodies.size() * 8, hipMemcpyHostToDevice,
+                                     c->stream));
+        FHE_HIP_CHECK(launch_expand_pksk_planes(chacha_stream_key(key.data(), kStreamSeededPksk), d_pb, (int)cp.ell,
+                                                (int)cp.k, (int)cp.N, c->d_pk_planes, c->stream));
+        const int npoly = (int)(cp.lwe_dim() * 4);
+        FHE_HIP_CHECK(hipMalloc(&c->d_cbsk, (size_t)npoly * 1024 * sizeof(double2)));
+        FHE_HIP_CHECK(hipMalloc(&c->d_cbsk_e, (size_t)npoly * 1024 * sizeof(double2)));
+        FHE_HIP_CHECK(hipMemcpyAsync(d_bb, sck->bsk_bodies.data(), sck->bsk_bodies.size() * 8, hipMemcpyHostToDevice,
+                                     c->stream));
+        FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededCbsk), d_bb, npoly, c->d_W,
+                                                c->d_psi, c->d_cbsk, c->stream));
+        FHE_HIP_CHECK(launch_bsk_to_e(c->d_cbsk, npoly, c->d_cbsk_e, c->stream));
+        FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+        return FHE_OK;
+    };
+    rc = body();
+    if (rc) {
+        (void)c->release_compression();
+        return rc;
+    }
+    c->has_comp = true;
+    return FHE_OK;
+}
+
+int fhe_ctx_export_compression_state(fhe_ctx* c, int8_t* planes, size_t planes_bytes, double* bsk, size_t bsk_doubles,
+                                     double* bsk_e, size_t bsk_e_doubles) {
+    if (!c) return FHE_ERR_INVALID;
+    if (!c->has_comp) {
+        set_error("no compression key installed");
+        return FHE_ERR_NO_KEY;
+    }
+    const size_t pb = fhe::pk_planes_bytes((int)c->cp.ell, (int)c->cp.cols());
+    const size_t nd = (size_t)c->cp.lwe_dim() * 4 * 1024 * 2;
+    if ((planes && planes_bytes < pb) || (bsk && bsk_doubles < nd) || (bsk_e && bsk_e_doubles < nd)) {
+        set_error("fhe_ctx_export_compression_state: buffer too small");
+        return FHE_ERR_INVALID;
+    }
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (planes) FHE_HIP_CHECK(hipMemcpy(planes, c->d_pk_planes, pb, hipMemcpyDeviceToHost));
+    if (bsk) FHE_HIP_CHECK(hipMemcpy(bsk, c->d_cbsk, nd * 8, hipMemcpyDeviceToHost));
+    if (bsk_e) FHE_HIP_CHECK(hipMemcpy(bsk_e, c->d_cbsk_e, nd * 8, hipMemcpyDeviceToHost));
+    return FHE_OK;
+}
+
 int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
     if (!c || !sk) return FHE_ERR_INVALID;
     FHE_HIP_CHECK(hipSetDevice(c->device));

@@ -111,6 +111,11 @@ constexpr uint32_t kStreamSeededBsk = 103;
 constexpr uint32_t kStreamPublicKeyMask = 104;
 constexpr uint32_t kStreamCompactBinary = 105;
 constexpr uint32_t kStreamCompactNoise = 106;
+// Mask streams of a seeded compression key (compress.h fhe_seeded_compression_key), keyed by its PUBLIC seed,
+// with the seeded server key's row stride: packing-KSK row r's k' N' mask words are u64 words [2048 r, ..),
+// the decompression BSK's mask polynomial of GGSW q, row rho is u64 words [2048 (2 q + rho), + 2048).
+constexpr uint32_t kStreamSeededPksk = 107;
+constexpr uint32_t kStreamSeededCbsk = 108;
 
 }  // namespace fhe
 

@@ -25,6 +25,10 @@
 //   kind 11 (compact ciphertext list, public_key.cpp): params | u32 packed (0 / 1) | u32 nvalues | per value
 //           u32 form, u32 count | per chunk 2048 u64 C_A words | ncoef u64 C_B words -- 76 + 8 nvalues +
 //           8 (2048 nchunks + ncoef) bytes in all; ncoef and nchunks follow from the value table.
+//   kind 12 (seeded compression key, compress_host.cpp): params | 7 x u32 compression params | 32 seed bytes |
+//           2048 pks_level N' u64 packing-key bodies | k' N' 2 2048 u64 BSK body polynomials -- 128 +
+//           8 (2048 pks_level N' + 4096 k' N') bytes in all.  The masks are not stored: streams 107 (packing
+//           KSK) and 108 (decompression BSK) under the seed, one row per 256 ChaCha blocks (compress.h).
 // Readers check magic, version, kind, length, checksum, parameter ranges and every count before
 // touching memory, and refuse block metadata (degree, noise) outside the radix layer's budget, so a
 // corrupted or hostile buffer fails with FHE_ERR_INVALID instead of poisoning the scheduler.
@@ -41,7 +45,7 @@ namespace fhe::ser {
 
 enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4, kSeeded = 5, kSeededServerKey = 6,
                        kCompressionPrivateKey = 7, kCompressionKey = 8, kCompressedList = 9,
-                       kPublicKey = 10, kCompactList = 11 };
+                       kPublicKey = 10, kCompactList = 11, kSeededCompressionKey = 12 };
 constexpr uint32_t kVersion = 2;  // 2: params carry the blind-rotation grouping (9th word); 1 still read
 constexpr size_t kHeaderBytes = 32;
 

@@ -9,13 +9,15 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
                                       installs it on the GPU from its bodies)
   CompressionKeys / CompressedCiphertextList   tfhe's compression of computed ciphertexts: x.compress() on
                                       the GPU, .serialize(), .decrypt(private) on the client, .decompress()
+  CompressedCompressionKey            tfhe's seeded compression key (CompressionKeys.generate_compressed /
+                                      decompress; Context.set_compression_key installs it from its bodies)
   CompactPublicKey / CompactCiphertextList   tfhe's public-key encryption: builder(pk).push(..).build_packed()
                                       without any secret, .expand() on the GPU
   Schnorr.sign_fhe_with_k0 / sign_fhe src/schnorr.rs:154-290
 All ciphertext arithmetic runs on the GPU through lib/libfhe_rocm.so; this package only marshals.
 """
 from ._lib import CompressionParams, FheError, FheParams, load  # noqa: F401
-from .core import (ClientKey, CompactPublicKey, CompressedServerKey, CompressionKey, CompressionKeys, CompressionPrivateKey, Context, ServerKey, comm_unique_id, default_params,  # noqa: F401
+from .core import (ClientKey, CompactPublicKey, CompressedCompressionKey, CompressedServerKey, CompressionKey, CompressionKeys, CompressionPrivateKey, Context, ServerKey, comm_unique_id, default_params,  # noqa: F401
                    default_compression_params, generate_keys, multi_bit_params, tuning)
 from .integer import (  # noqa: F401,E402
     COMPAT, FAST, PUBLIC, BigUintFHE, FheBool, FheUint, FheUint8, FheUint32, FheUint64, FheUint128, FheUint256, set_server_key,

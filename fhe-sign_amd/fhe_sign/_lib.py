@@ -249,6 +249,16 @@ _SIGNATURES = [
     ("fhe_compressed_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_compressed_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_compressed_extract_rows", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_compression_keys_generate_seeded", C.c_int,
+     [C.c_void_p, C.POINTER(CompressionParams), C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_compression_key_params", C.c_int, [C.c_void_p, C.POINTER(FheParams), C.POINTER(CompressionParams)]),
+    ("fhe_seeded_compression_key_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_seeded_compression_key_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_compression_key_expand_host", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_seeded_compression_key_destroy", None, [C.c_void_p]),
+    ("fhe_set_compression_key_seeded", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fhe_ctx_export_compression_state", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     ("fhe_public_key_generate", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     ("fhe_public_key_params", C.c_int, [C.c_void_p, C.POINTER(FheParams)]),
     ("fhe_public_key_export", C.c_int, [C.c_void_p, u8p, u64p, C.c_size_t]),

@@ -287,7 +287,57 @@ class CompressionKey:
         return cls(h)
 
 
+class CompressedCompressionKey:
+    """tfhe-rs' CompressedCompressionKey + CompressedDecompressionKey: a public 32-byte seed and the bodies of
+    the compression key (3.0x smaller on the wire; include/fhe_rocm.h "seeded (compressed) compression key").
+    Context.set_compression_key(it) regenerates the masks on the GPU; decompress() does it on the host."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self.main_params, self.params = FheParams(), CompressionParams()
+        check(load().fhe_seeded_compression_key_params(handle, C.byref(self.main_params), C.byref(self.params)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_seeded_compression_key_destroy(self._h)
+            self._h = None
+
+    def serialize(self) -> bytes:
+        """128 + 8 (2048 level N' + 4096 k' N') bytes: frame, both parameter sets, seed, bodies"""
+        return serialize_with(load().fhe_seeded_compression_key_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes) -> "CompressedCompressionKey":
+        h = C.c_void_p()
+        check(load().fhe_seeded_compression_key_deserialize(data, len(data), C.byref(h)))
+        return cls(h)
+
+    def decompress(self) -> CompressionKey:
+        """the full key on the host: the word-for-word definition of the GPU install"""
+        h = C.c_void_p()
+        check(load().fhe_seeded_compression_key_expand_host(self._h, C.byref(h)))
+        return CompressionKey(h)
+
+
 class CompressionKeys:
+    @staticmethod
+    def generate_compressed(client_key: ClientKey, params: CompressionParams | None = None, seed: bytes | None = None):
+        """(CompressionPrivateKey, CompressedCompressionKey) of client_key; advances its encryption stream by
+        k' N' + 2048 level N' + 4096 k' N' words.  seed=None (the default) draws the public mask seed from the
+        OS; a given 32-byte seed is for tests.  One seed, one object: never reuse it under the same client key."""
+        if seed is not None:
+            seed = bytes(seed)
+            if len(seed) != 32:
+                raise ValueError("the mask seed is 32 bytes")
+        a, b = C.c_void_p(), C.c_void_p()
+        check(load().fhe_compression_keys_generate_seeded(
+            client_key.handle, C.byref(params) if params is not None else None, seed, C.byref(a), C.byref(b)))
+        return CompressionPrivateKey(a), CompressedCompressionKey(b)
+
     @staticmethod
     def generate(client_key: ClientKey, params: CompressionParams | None = None):
         """(CompressionPrivateKey, CompressionKey) of client_key; advances its encryption stream by
@@ -340,6 +390,7 @@ class Context:
         check(load().fhe_ctx_create(device, C.byref(h)))
         self._h = h
         self.params = None
+        self._comp_params = None  # of the key set_compression_key installed last
 
     @property
     def handle(self):
@@ -361,9 +412,30 @@ class Context:
             check(load().fhe_set_server_key(self._h, sk.handle))
         self.params = sk.params
 
-    def set_compression_key(self, key: "CompressionKey") -> None:
-        """after set_server_key; the next set_server_key drops it"""
-        check(load().fhe_set_compression_key(self._h, key.handle))
+    def set_compression_key(self, key: "CompressionKey | CompressedCompressionKey") -> None:
+        """after set_server_key; the next set_server_key drops it.  A CompressedCompressionKey is installed
+        from its bodies: the masks are regenerated on the GPU"""
+        if isinstance(key, CompressedCompressionKey):
+            check(load().fhe_set_compression_key_seeded(self._h, key.handle))
+        else:
+            check(load().fhe_set_compression_key(self._h, key.handle))
+        self._comp_params = key.params
+
+    def export_compression_state(self):
+        """(byte planes int8, Fourier BSK float64, its E layout float64) of the installed compression key
+        (test hook: fhe_ctx_export_compression_state)"""
+        lib = load()
+        check(lib.fhe_ctx_export_compression_state(self._h, None, 0, None, 0, None, 0))  # FHE_ERR_NO_KEY first
+        c = self._comp_params
+        if c is None:
+            raise RuntimeError("export_compression_state: the key was not installed through set_compression_key")
+        cols = (c.glwe_dimension + 1) * c.polynomial_size
+        planes = np.zeros(8 * ((cols + 15) // 16) * 32 * c.pks_level * 1024, np.int8)
+        bsk = np.zeros(c.lwe_dim() * 4 * 1024 * 2, np.float64)
+        bsk_e = np.zeros_like(bsk)
+        check(lib.fhe_ctx_export_compression_state(self._h, planes.ctypes.data, planes.size, bsk.ctypes.data, bsk.size,
+                                                   bsk_e.ctypes.data, bsk_e.size))
+        return planes, bsk, bsk_e
 
     def export_fourier_bsk(self) -> np.ndarray:
         out = np.zeros(self.params.ggsw_count() * 4 * 1024 * 2, np.float64)

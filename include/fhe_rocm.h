@@ -608,7 +608,8 @@ typedef struct fhe_compression_private_key fhe_compression_private_key;
  *   decompression BSK  a CLASSIC (grouping 1) bootstrapping key of LWE dimension k' N' encrypting the
  *                bits of s' (flat, polynomial-major) under the big GLWE key, in fhe_generate_keys' word
  *                layout and gadget form -- classic even when the main key is multi-bit.
- * A seeded form of this key does not exist. */
+ * 150,994,944 payload bytes at the defaults; its seeded form (fhe_seeded_compression_key below) is 3.0x
+ * smaller on the wire. */
 typedef struct fhe_compression_key fhe_compression_key;
 /* Draws everything from ck's encryption stream, in this order and before any threaded pass: k' N' secret
  * words (bit 0 of each), the packing KSK's rows in order (k' N' mask words, then N' noise words, per row),
@@ -678,6 +679,71 @@ int fhe_compressed_expand_biguint(fhe_ctx* ctx, const fhe_compressed_list* x, fh
 /* Test hook: the unpack + sample-extract kernel alone.  rows = nblocks x (k' N' + 1) words (each stored value
  * << 52), host pointer; synchronous. */
 int fhe_compressed_extract_rows(fhe_ctx* ctx, const fhe_compressed_list* x, uint64_t* rows, size_t nwords);
+
+/* ------------------------------------------------- seeded (compressed) compression key */
+/* The compression key is the largest object left for a client to send: 150,994,944 payload bytes at the
+ * defaults (packing KSK 83,886,080 + decompression BSK 67,108,864), of which k' of every k' + 1 packing-key
+ * polynomials and every second BSK polynomial are public random masks.  The seeded key keeps a PUBLIC
+ * 32-byte seed and the bodies: 50,331,776 bytes serialized (3.0x smaller).  tfhe-rs' CompressedCompressionKey
+ * / CompressedDecompressionKey.  The handle lives on the host and needs no context.
+ *   masks   ChaCha20 keyed by the 32 seed bytes (little-endian words), nonce {id, "ROCM", 0}; every row
+ *           starts on a stride of 256 ChaCha blocks (2048 u64 words; k' N' <= 2048):
+ *           packing KSK (id 107) row r = j pks_level + l: coefficient m of mask polynomial c < k' = u64 word
+ *           2048 r + c N' + m;
+ *           BSK (id 108) GGSW q < k' N', row rho in {0, 1}: mask coefficient m = u64 word 2048 (2 q + rho) + m
+ *   noise   everything from the client key's encryption stream, before any threaded pass: k' N' secret words
+ *           (bit 0 of each -- the s' fhe_compression_keys_generate draws from the same stream state), then N'
+ *           noise words per packing-key row in row order, then 2048 noise words per BSK row in (q, rho) order:
+ *             k' N' + 2048 pks_level N' + 4096 k' N'  stream words (u64), 6,292,480 at the defaults,
+ *           whatever the number of host threads: a serialized client key continues correctly afterwards
+ *   bodies  packing KSK: B = sum_c A_c * s'_c + e, e from TUniform(2^pks_noise_log2), then B[0] += S_j <<
+ *           (64 - pks_base_log (l + 1)).  BSK, with g = 1 << (64 - pbs_base_log) and message s'_q (classic,
+ *           whatever the main grouping): B = A * S + e, e from TUniform(2^glwe_noise_log2), then row 1:
+ *           B[0] += g s'_q, row 0: B[t] -= g s'_q S_t for every t.  (fhe_compression_keys_generate puts row 0's
+ *           gadget into the mask; a mask that is regenerated from a seed cannot hold it.  The phases are the
+ *           same, so the expanded key is consumed by every kernel unchanged -- but its words differ from
+ *           fhe_compression_keys_generate's for the same secrets.)
+ * THE SEED IS PUBLIC.  ONE SEED, ONE OBJECT: never reuse a seed for a second compression key, a server key
+ * or a seeded ciphertext under the same client key (the stream ids differ from 101 / 102 / 103, so a reuse
+ * is not the catastrophic case of equal masks; the rule stands all the same).  Pass mask_seed = NULL
+ * (32 bytes from getrandom()) outside tests. */
+typedef struct fhe_seeded_compression_key fhe_seeded_compression_key;
+int fhe_compression_keys_generate_seeded(fhe_client_key* ck, const fhe_compression_params* params /* NULL: defaults */,
+                                         const uint8_t mask_seed[32] /* NULL: OS entropy */,
+                                         fhe_compression_private_key** priv, fhe_seeded_compression_key** sck);
+/* either output may be NULL */
+int fhe_seeded_compression_key_params(const fhe_seeded_compression_key* sck, fhe_params* main,
+                                      fhe_compression_params* comp);
+/* Wire format (kind 12 of the keys' framed, checksummed format; size-query convention as above): main params,
+ * compression params (7 x u32), 32 seed bytes, packing-key bodies u64[2048][pks_level][N'], BSK bodies
+ * u64[k' N'][2][2048] -- 128 + 8 (2048 pks_level N' + 4096 k' N') bytes.  The reader checks magic, version,
+ * kind, checksum, both parameter ranges and that the payload length is exactly that of the parsed parameters,
+ * all before it allocates.  A full key's bytes (kind 8) are refused here, and these by
+ * fhe_compression_key_deserialize.  tfhe-rs' wire format is not reproduced (parity unpinned). */
+int fhe_seeded_compression_key_serialize(const fhe_seeded_compression_key* sck, uint8_t* buf, size_t cap,
+                                         size_t* len);
+int fhe_seeded_compression_key_deserialize(const uint8_t* buf, size_t len, fhe_seeded_compression_key** sck);
+/* decompress on the host: an ordinary compression key (masks regenerated, bodies in place; serializes as
+ * kind 8, installs through fhe_set_compression_key).  The word-for-word definition of the GPU install. */
+int fhe_seeded_compression_key_expand_host(const fhe_seeded_compression_key* sck, fhe_compression_key** key);
+void fhe_seeded_compression_key_destroy(fhe_seeded_compression_key* sck);
+/* Leaves ctx in exactly the device state of fhe_set_compression_key(ctx, expand_host(sck)) -- the packing
+ * key's byte planes, both Fourier layouts of the decompression BSK, the compression parameters -- but uploads
+ * only the bodies: a gfx950 kernel writes the byte planes from seed + bodies (the u64 packing key never
+ * exists on the device), and the BSK mask polynomials are generated inside the Fourier conversion.  No
+ * secret is needed and no collective is issued.  Errors as fhe_set_compression_key: FHE_ERR_INVALID for a
+ * NULL argument, FHE_ERR_NO_KEY without a server key, FHE_ERR_INVALID with the differing field named if the
+ * main parameters are not the installed server key's, FHE_ERR_UNSUPPORTED if the body counts do not match
+ * the parameters -- all before anything is launched, a previously installed compression key stays in place.
+ * FHE_ERR_HIP for a device failure: then the context has no compression key.  Dropped by the next server-key
+ * install. */
+int fhe_set_compression_key_seeded(fhe_ctx* ctx, const fhe_seeded_compression_key* sck);
+/* Test hook: the installed compression key's device state.  planes = the packing key's int8 byte planes
+ * [8][ceil((k' + 1) N' / 16)][32 pks_level][64][16], bsk / bsk_e = the decompression BSK's two Fourier layouts,
+ * k' N' x 4 x 1024 complex doubles each (sizes in doubles).  Each pair may be NULL / 0.  Waits for the
+ * stream.  FHE_ERR_NO_KEY without a compression key. */
+int fhe_ctx_export_compression_state(fhe_ctx* ctx, int8_t* planes, size_t planes_bytes, double* bsk,
+                                     size_t bsk_doubles, double* bsk_e, size_t bsk_e_doubles);
 
 /* ------------------------------------------------- public-key encryption (compact lists) */
 /* Encryption by a party that does not hold the secret key: tfhe-rs' CompactPublicKey::new(&client_key),
