@@ -738,8 +738,10 @@ static void mac_own_first(const double* D0, const double* D1, const double* kr, 
  * product is added without rounding to an integer first (acc = tor_red(acc + y), the untwist
  * product fused in: fho_fourier_add_to_poly).  The extra error is the rounding of acc + y at the
  * magnitude of y (~2^90 typical, <= 2^97), i.e. the same order as
- * the f64 transform's own error -- 2^-25 of the torus per CMUX against a blind-rotation noise of
- * ~2^-15 (bootstrapping-key noise x digits); decryption is unaffected.  The GLWE is returned as u64
+ * the f64 transform's own error -- measured against exact integer arithmetic (tests/test_exact_pbs.py,
+ * DESIGN.md 3): 2^38.5 rms per coefficient and update (2^-25.5 of the torus), which is 2^43.2 in phase
+ * (a phase sums N/2 + 1 coefficients), against a blind-rotation noise of ~2^44 per update in phase
+ * (bootstrapping-key noise x digits); decryption is unaffected.  The GLWE is returned as u64
  * (fho_f64_to_torus, round half even) for sample extraction. */
 void fho_blind_rotate(const fho_keys* k, const uint64_t* ct_small, const uint64_t* lut,
                       uint64_t* glwe) {
@@ -771,11 +773,19 @@ void fho_blind_rotate(const fho_keys* k, const uint64_t* ct_small, const uint64_
      * worst case, 2^37 typical); the next X^a acc - acc (|.| <= 2^98) rounds once more (<= 2^45) and
      * its digit is exact for the value it holds (rint is exact; the digit's own rounding <= 2^40 is
      * the gadget's).  So the f64 representative drifts from the exact torus value by <= 2^46 per
-     * CMUX in the worst case (2^-18 of the torus), ~2^38 typically, random in sign: after n = 834
-     * CMUXes <= 2^50.8 at worst against the decode half-step 2^58 and the modulus-switch noise
-     * sigma ~ 2^54.6, ~2^43 typically (tests/test_oracle.py::test_unreduced_accumulator_error_bound
-     * checks these bounds on worst-case magnitudes; the 2^20-bootstrap decode test,
-     * tests/test_noise_gpu.py, checks the end result). */
+     * CMUX in the worst case (2^-18 of the torus; tests/test_oracle.py::
+     * test_unreduced_accumulator_error_bound checks that bound on worst-case magnitudes).
+     * Measured against exact integer arithmetic (tests/test_exact_pbs.py; DESIGN.md 3 has the table),
+     * per COEFFICIENT and update: rms 2^38.1-2^38.5 classic, 2^39.0-2^39.3 for a multi-bit group,
+     * largest seen 2^40.9 / 2^42.0.  In PHASE, which sums N/2 + 1 coefficients: 2^43.2 / 2^44.2 per
+     * update of a random accumulator (32 x the coefficient figure: the error is white), random in
+     * sign, so ~2^48.0 after 834 CMUXes and ~2^48.6 after 417 groups, against an exact-arithmetic
+     * noise of 2^49.5 there, the modulus-switch noise sigma ~ 2^54.6 and the decode half-step 2^58.
+     * The FIRST update is the exception: acc = X^-b LUT has digits constant over boxes of 128
+     * coefficients, the error of that update is smooth instead of white, and the binary key (mean
+     * 1/2) sums it coherently: 2^45.4 in phase classic, 2^47.6 multi-bit, once, whatever n -- 2.7
+     * times the exact noise at n = 2, 5 % of the variance at 834 multi-bit.  (The 2^20-bootstrap
+     * decode test, tests/test_noise_gpu.py, checks the end result.) */
     uint32_t upd = 0;
 
     if (k->p.grouping == 2) {
