@@ -1660,3 +1660,98 @@ int fhe_compact_list_extract_rows(fhe_ctx* c, const fhe_compact_list* x, uint64_
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------- re-randomization
+// tfhe-rs' re_randomize under the CompactPublicKey (public_key.h): the device ends of it.  The host definition
+// (fhe_rerandomize_host), the install (fhe_set_public_key) and the seed helper are in rerandomize.cpp and
+// schnorr.cpp.
+namespace {
+// the checks of every re-randomization, before anything is flushed or launched; seed32 = the call's seed
+int rerandomize_check(fhe_ctx* c, const uint8_t* seed, uint8_t seed32[32]) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!c->has_pk) {
+        set_error("no public key installed (fhe_set_public_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    if (seed) {
+        std::memcpy(seed32, seed, 32);
+        return FHE_OK;
+    }
+    if (c->attached() && c->nranks > 1)
+        return invalid("re-randomization under a communicator needs a seed: with seed = NULL every rank would draw its own "
+                       "and the ranks' ciphertexts would diverge");
+    if (!os_entropy32(seed32)) {
+        set_error("getrandom failed: no re-randomization seed");
+        return FHE_ERR_UNSUPPORTED;
+    }
+    return FHE_OK;
+}
+void wipe32(uint8_t seed32[32]) {
+    volatile uint8_t* w = seed32;
+    for (int i = 0; i < 32; ++i) w[i] = 0;
+}
+}  // namespace
+
+extern "C" {
+
+int fhe_radix_rerandomize(fhe_ctx* c, const fhe_radix* x, const uint8_t* seed, fhe_radix** out) {
+    if (!x || !out) return invalid("null argument to fhe_radix_rerandomize");
+    uint8_t seed32[32];
+    int rc = rerandomize_check(c, seed, seed32);
+    if (rc) return rc;
+    rc = guarded([&] {
+        std::vector<const Block*> blocks;
+        for (const Block& b : x->r.blocks) blocks.push_back(&b);
+        Radix r;
+        r.blocks = c->engine->rerandomize(blocks, seed32);
+        *out = wrap(std::move(r), x->bits);
+        return FHE_OK;
+    });
+    wipe32(seed32);  // used for this call, kept nowhere
+    return rc;
+}
+
+int fhe_biguint_rerandomize(fhe_ctx* c, const fhe_biguint* x, const uint8_t* seed, fhe_biguint** out) {
+    if (!x || !out) return invalid("null argument to fhe_biguint_rerandomize");
+    uint8_t seed32[32];
+    int rc = rerandomize_check(c, seed, seed32);
+    if (rc) return rc;
+    rc = guarded([&] {
+        std::vector<const Block*> blocks;
+        for (const Radix& d : x->v.digits) {
+            engine_check(d.nblocks() == kLimbBlocks, "fhe_biguint_rerandomize: a limb is not a 32-bit radix");
+            for (const Block& b : d.blocks) blocks.push_back(&b);
+        }
+        const Blocks all = c->engine->rerandomize(blocks, seed32);
+        auto v = std::make_unique<fhe_biguint>();
+        for (size_t at = 0; at < all.size(); at += kLimbBlocks) {
+            Radix d;
+            d.blocks.assign(all.begin() + at, all.begin() + at + kLimbBlocks);
+            v->v.digits.push_back(std::move(d));
+        }
+        *out = v.release();
+        return FHE_OK;
+    });
+    wipe32(seed32);
+    return rc;
+}
+
+int fhe_rerandomize_rows(fhe_ctx* c, const uint8_t* seed, const uint64_t* rows, size_t nblocks, uint64_t* out) {
+    if (!seed || ((!rows || !out) && nblocks)) return invalid("null argument to fhe_rerandomize_rows");
+    if (nblocks > kCompactMaxCoefs) return invalid("fhe_rerandomize_rows: more than 2^24 blocks");
+    uint8_t seed32[32];
+    int rc = rerandomize_check(c, seed, seed32);
+    if (rc || !nblocks) return rc;
+    return guarded([&] {
+        const Blocks in = c->engine->upload_many(rows, nblocks, kMsgMod - 1);
+        std::vector<const Block*> blocks;
+        for (const Block& b : in) blocks.push_back(&b);
+        const Blocks res = c->engine->rerandomize(blocks, seed32);
+        for (size_t i = 0; i < nblocks; ++i) blocks[i] = &res[i];
+        c->engine->download_many(blocks, out);
+        return FHE_OK;
+    });
+}
+
+}  // extern "C"

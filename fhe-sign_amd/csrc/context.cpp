@@ -153,6 +153,10 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
         const int rc = release_compression();
         if (rc) return rc;
     }
+    if (has_pk) {  // nor does a public key
+        const int rc = release_public_key();
+        if (rc) return rc;
+    }
     if (d_ms) {
         FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read it
         FHE_HIP_CHECK(hipFree(d_ms));
@@ -653,6 +657,7 @@ void fhe_ctx_destroy(fhe_ctx* c) {
     delete c->engine;
     c->engine = nullptr;
     (void)c->release_compression();
+    (void)c->release_public_key();
     c->release_comm();
     void* ptrs[] = {c->d_ksk, c->d_ksk_planes, c->d_ks_digits, c->d_ks_body, c->d_bsk, c->d_W, c->d_psi, c->d_tw_wide, c->d_psi_wide, c->d_tw_quad,
                     c->d_psi_quad, c->d_zeta_wide, c->d_mono, c->d_bsk_e, c->d_zeta_full, c->d_flags, c->d_luts, c->d_ms, c->d_stage_in, c->d_stage_out, c->d_stage_lut, c->d_gather, c->d_clock};
@@ -675,6 +680,10 @@ struct DeviceFree {
 int release_key(fhe_ctx* c) {
     if (c->has_comp) {  // a compression key belongs to the server key it was installed after
         const int rc = c->release_compression();
+        if (rc) return rc;
+    }
+    if (c->has_pk) {  // so does a public key
+        const int rc = c->release_public_key();
         if (rc) return rc;
     }
     if (!c->has_key) return FHE_OK;

@@ -206,4 +206,13 @@ struct fhe_ctx {
     int ensure_pk(size_t count);
     int ensure_cms(size_t count);
     int release_compression();  // waits for the stream, frees all of the above
+
+    // Public key of the re-randomization (fhe_set_public_key; dropped by every server-key install): A then B,
+    // 2048 words each, and the zero encryptions' scratch, `rr_cap` chunks of Z_A then Z_B (rerandomize.hip).
+    bool has_pk = false;
+    uint64_t* d_pk_ab = nullptr;
+    uint64_t* d_rr_z = nullptr;
+    size_t rr_cap = 0;
+    int ensure_rr(size_t chunks);
+    int release_public_key();  // waits for the stream, frees all of the above
 };

@@ -34,6 +34,16 @@ hipError_t launch_expand_bsk_fourier(const ChaChaKey& k, const uint64_t* bodies,
 // arrays, every dst[i] a slot of 2049 words; the caller stages every chunk that [first, first + count) touches
 hipError_t launch_compact_extract(const uint64_t* ca, const uint64_t* cb, uint64_t* const* dst, uint32_t first, int count,
                                   hipStream_t s);
+// rerandomize.hip: the zero encryptions of nblocks blocks (public_key.h "re-randomization").  ab = the public
+// key's A then B (2048 words each); z = ceil(nblocks / 2048) chunks of Z_A then Z_B (2048 words each), Z_B's
+// noise on the used coefficients only; kbin / knoise = the re-randomization seed's two streams.  nblocks <= 2^24
+hipError_t launch_rerand_zero(const ChaChaKey& kbin, const ChaChaKey& knoise, const uint64_t* ab, uint64_t* z, uint32_t nblocks,
+                              uint32_t noise_log2, hipStream_t s);
+// rerandomize.hip: for i < nblocks, dst[i][0 .. 2048] = the source block + the sample extraction of z at
+// coefficient i; the source is the slot src[i], or for src[i] == null the trivial ciphertext (0, tbody[i]).
+// src, tbody and dst are device arrays, every slot 2049 words
+hipError_t launch_rerand_add(const uint64_t* z, const uint64_t* const* src, const uint64_t* tbody, uint64_t* const* dst,
+                             uint32_t nblocks, hipStream_t s);
 // ksk holds the KSK stream words ([rows][n + 1], rows = N * levels): bodies computed in place
 hipError_t launch_ksk_bodies(uint64_t* ksk, const uint64_t* lwe_sk, const uint64_t* glwe_sk, int n, int rows,
                              int levels, int base_log, int noise_log2, hipStream_t s);

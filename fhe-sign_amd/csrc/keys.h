@@ -116,6 +116,12 @@ constexpr uint32_t kStreamCompactNoise = 106;
 // the decompression BSK's mask polynomial of GGSW q, row rho is u64 words [2048 (2 q + rho), + 2048).
 constexpr uint32_t kStreamSeededPksk = 107;
 constexpr uint32_t kStreamSeededCbsk = 108;
+// Re-randomization under the public key (public_key.h), keyed by a call's re-randomization seed
+// with the compact list's positions: chunk c's R is u64 words [32 c, 32 c + 32) of kStreamRerandBinary, its
+// noise words start at u64 word 4096 c of kStreamRerandNoise.  Ids of their own: a seed shared by mistake with
+// a compact list's encryption seed (105 / 106) does not make related ciphertexts.
+constexpr uint32_t kStreamRerandBinary = 109;
+constexpr uint32_t kStreamRerandNoise = 110;
 
 }  // namespace fhe
 

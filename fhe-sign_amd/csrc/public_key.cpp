@@ -19,39 +19,12 @@ namespace fhe {
 namespace {
 constexpr uint32_t N = kPolySize;
 
-// r += a * s mod (X^N + 1) for the binary polynomial whose coefficient j is bit(j)
-template <class Bit>
-void negacyclic_binary_mac(uint64_t* r, const uint64_t* a, Bit&& bit) {
-    for (uint32_t j = 0; j < N; ++j) {
-        if (!bit(j)) continue;
-        for (uint32_t m = j; m < N; ++m) r[m] += a[m - j];
-        for (uint32_t m = 0; m < j; ++m) r[m] -= a[m + N - j];
-    }
-}
+}  // namespace
 
 void public_key_mask(const uint8_t seed[32], uint64_t* A) {
     ChaChaStream masks(bytes_key(seed), kStreamPublicKeyMask);
     masks.fill_u64(A, N);
 }
-
-// fn(c) for c < chunks on up to 16 host threads: every chunk seeks its own streams, so the split only
-// divides the work
-template <class F>
-void parallel_chunks(size_t chunks, F&& fn) {
-    const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-    const size_t T = std::min<size_t>(std::min<size_t>(hw, 16), chunks);
-    if (T <= 1) {
-        for (size_t c = 0; c < chunks; ++c) fn(c);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < T; ++t)
-        th.emplace_back([&, t] {
-            for (size_t c = t; c < chunks; c += T) fn(c);
-        });
-    for (auto& x : th) x.join();
-}
-}  // namespace
 
 void generate_public_key(fhe_client_key* ck, const uint8_t seed[32], fhe_public_key* pk) {
     pk->params = ck->params;

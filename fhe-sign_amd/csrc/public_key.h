@@ -16,9 +16,19 @@
 //   expand  coefficient t of a chunk -> the big LWE with mask word u = C_A[t - u] (u <= t), -C_A[t - u + N]
 //           (u > t), body C_B[t]: the sample extraction of compress.hip's k_pk_unpack and of the oracle
 // The phase error of a coefficient is E R + E2 - E1 S: |.| <= 2048 2^17 + 2^17 + 2048 2^17 < 2^30 (R, S binary).
+//
+// Re-randomization (tfhe-rs' re_randomize under the CompactPublicKey): blocks 0 .. n-1 of a value
+// get a fresh public-key encryption of ZERO added.  From a 32-byte re-randomization seed, chunk c draws R and
+// the noise at the list's positions under stream ids of its own (kStreamRerandBinary / kStreamRerandNoise):
+//   Z_A = A R + E1, Z_B[j] = (B R)[j] + E2[j] for the used j (no message term)
+//   block i (t = i mod N of chunk i / N): mask word u += Z_A[t - u] (u <= t), -= Z_A[t - u + N] (u > t),
+//   body += Z_B[t] -- the sample extraction above, added to the input instead of written.
+// The added phase error is again E R + E2 - E1 S, below 2^30 in magnitude.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "keys.h"
@@ -60,6 +70,35 @@ struct fhe_compact_builder {
 };
 
 namespace fhe {
+// r += a * s mod (X^N + 1) for the binary polynomial whose coefficient j is bit(j)
+template <class Bit>
+void negacyclic_binary_mac(uint64_t* r, const uint64_t* a, Bit&& bit) {
+    constexpr uint32_t N = kPolySize;
+    for (uint32_t j = 0; j < N; ++j) {
+        if (!bit(j)) continue;
+        for (uint32_t m = j; m < N; ++m) r[m] += a[m - j];
+        for (uint32_t m = 0; m < j; ++m) r[m] -= a[m + N - j];
+    }
+}
+// fn(c) for c < chunks on up to 16 host threads: every chunk seeks its own streams, so the split only
+// divides the work
+template <class F>
+void parallel_chunks(size_t chunks, F&& fn) {
+    const size_t hw = std::max(1u, std::thread::hardware_concurrency());
+    const size_t T = std::min<size_t>(std::min<size_t>(hw, 16), chunks);
+    if (T <= 1) {
+        for (size_t c = 0; c < chunks; ++c) fn(c);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < T; ++t)
+        th.emplace_back([&, t] {
+            for (size_t c = t; c < chunks; c += T) fn(c);
+        });
+    for (auto& x : th) x.join();
+}
+// A = the first N words of the key's mask stream
+void public_key_mask(const uint8_t seed[32], uint64_t* A);
 // pk of ck under the PUBLIC mask seed: advances ck->enc_rng by exactly N words, drawn before the threaded pass
 void generate_public_key(fhe_client_key* ck, const uint8_t seed[32], fhe_public_key* pk);
 // fills first / ncoef / nblocks of every value; false (with the offending field named) on a malformed table
@@ -72,4 +111,9 @@ void encrypt_compact(const fhe_public_key& pk, const uint8_t enc_seed[32], bool 
 void expand_compact_host(const fhe_compact_list& x, size_t first, size_t n, uint64_t* rows);
 // the degree of coefficient g's plaintext: 3, or 15 where two blocks share it
 uint32_t compact_degree(const fhe_compact_list& x, const fhe_compact_list::Value& v, size_t g);
+// rerandomize.cpp: the zero encryptions of n blocks under the re-randomization seed: za = Z_A of every chunk
+// (ceil(n / N) x N words), zb = Z_B of the used coefficients (n words).  n <= kCompactMaxCoefs.
+void rerandomize_zero_host(const fhe_public_key& pk, const uint8_t seed[32], size_t n, uint64_t* za, uint64_t* zb);
+// cts: n rows of 2049 words, re-randomized in place.  The word-for-word definition of rerandomize.hip.
+void rerandomize_host(const fhe_public_key& pk, const uint8_t seed[32], uint64_t* cts, size_t n);
 }  // namespace fhe

@@ -1205,6 +1205,73 @@ void Engine::extract_compact_rows(const fhe_compact_list& x, uint64_t* rows) {
     download_many(ptrs, rows);
 }
 
+// ------------------------------------------------------------------ re-randomization (public key)
+Blocks Engine::rerandomize(const std::vector<const Block*>& blocks, const uint8_t seed[32]) {
+    engine_check(host_mode_ == kDevice, "rerandomize on a host-only engine");
+    if (!ctx_->has_pk) throw EngineError(FHE_ERR_NO_KEY, "no public key installed (fhe_set_public_key)");
+    const size_t n = blocks.size();
+    engine_check(n <= kCompactMaxCoefs, "rerandomize of more than 2^24 blocks");
+    Blocks out(n);
+    if (n == 0) return out;
+    // lazy blocks first: their combination into slots of their own (lincomb flushes)
+    Blocks real(n);
+    std::vector<const Block*> in(n);
+    for (size_t i = 0; i < n; ++i) {
+        in[i] = blocks[i];
+        if (!blocks[i]->lazy()) continue;
+        engine_check(blocks[i]->lin_cst >= 0, "rerandomize of a lazy block below zero");
+        const uint32_t degree = blocks[i]->degree;
+        real[i] = lincomb(*blocks[i]->lin, (uint32_t)blocks[i]->lin_cst);
+        real[i].degree = degree;
+        in[i] = &real[i];
+    }
+    flush_for(in);
+    const size_t chunks = (n + kPolySize - 1) / kPolySize;
+    engine_check(ctx_->ensure_rr(chunks) == FHE_OK, "re-randomization workspace");
+    const size_t words = 3 * n;  // the source slots, the trivial bodies, then the fresh slots
+    if (words > up_cap_) {
+        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
+        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
+        d_up_ = nullptr;
+        up_cap_ = 0;
+        hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc upload");
+        up_cap_ = words;
+    }
+    std::vector<const uint64_t*> src(n);
+    std::vector<uint64_t> tbody(n, 0);
+    std::vector<uint64_t*> dst(n);
+    for (size_t i = 0; i < n; ++i) {
+        const Block& b = *in[i];
+        src[i] = b.ptr();
+        if (b.trivial()) {
+            engine_check(!b.half_neg, "rerandomize of a half-step block");
+            tbody[i] = (uint64_t)b.value * ctx_->p.delta();
+        }
+        // a real ciphertext from here on: slot set, no value, no combination, no half step
+        out[i].slot = pool_->alloc();
+        out[i].degree = b.trivial() ? std::max<uint32_t>(b.degree, kMsgMod - 1) : b.degree;
+        out[i].noise = b.noise;
+        dst[i] = out[i].slot->p;
+    }
+    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up_);
+    uint64_t* d_tbody = d_up_ + n;
+    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up_ + 2 * n);
+    hip_check(hipMemcpyAsync(d_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "rerandomize slots");
+    hip_check(hipMemcpyAsync(d_tbody, tbody.data(), n * 8, hipMemcpyHostToDevice, ctx_->stream), "rerandomize bodies");
+    hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "rerandomize slots");
+    KeyWords key = bytes_key(seed);
+    ChaChaKey kbin = chacha_stream_key(key.data(), kStreamRerandBinary), knoise = chacha_stream_key(key.data(), kStreamRerandNoise);
+    const hipError_t zrc = launch_rerand_zero(kbin, knoise, ctx_->d_pk_ab, ctx_->d_rr_z, (uint32_t)n, ctx_->p.glwe_noise_log2, ctx_->stream);
+    // the launch has copied its arguments: the seed gives away R, no copy of it stays on the host
+    for (volatile uint32_t& w : key) w = 0;
+    for (ChaChaKey* k : {&kbin, &knoise})
+        for (volatile uint32_t& w : k->key) w = 0;
+    hip_check(zrc, "zero encryptions");
+    hip_check(launch_rerand_add(ctx_->d_rr_z, d_src, d_tbody, d_dst, (uint32_t)n, ctx_->stream), "re-randomization");
+    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
+    return out;
+}
+
 Blocks Engine::upload_deferred(size_t n, uint32_t degree, std::function<std::vector<uint64_t>()> fill) {
     run_before_launch();  // an earlier deferred upload first (one at a time)
     Blocks out(n);

@@ -215,6 +215,18 @@ public:
     Blocks expand_compact(const fhe_compact_list& x, size_t value);
     // the extraction kernel alone over every coefficient of the list: ncoef x 2049 words to the host (tests)
     void extract_compact_rows(const fhe_compact_list& x, uint64_t* rows);
+    // Re-randomization under the installed public key (public_key.h, fhe_set_public_key), modelled on
+    // compact_extract: block i of the result = block i of `blocks` + the sample extraction, at coefficient i, of
+    // the zero encryptions the 32-byte seed defines -- word for word rerandomize_host of the blocks' exported
+    // rows.  Out of place: fresh slots, the sources untouched.  Pending producers of the blocks are launched
+    // first (flush_for; under a communicator that is the plain flush a decryption makes), a lazy block is made
+    // real by lincomb, a trivial block enters as the ciphertext (0, delta value).  Only the seed and the slot
+    // pointers (24 B per block) are staged; rerandomize.hip makes the zero encryptions and adds them.
+    // Stream-ordered, no collective of its own: under a communicator every rank passes the same seed and
+    // computes the same words.  Degree and noise label of a block are unchanged (the added error is below
+    // 2^30, against 2^49.7 of a bootstrap's output); a trivial block becomes a slot block of degree
+    // max(value, 3) with no known-value shortcut left.  Device engines with a public key only.
+    Blocks rerandomize(const std::vector<const Block*>& blocks, const uint8_t seed[32]);
     void download(const Block& b, uint64_t* ct);
     // the slot blocks' ciphertexts -> host, contiguous (one gather + one copy + one wait instead of a
     // round trip per block: the decryption of a 256-bit result is 128-144 blocks)

@@ -402,6 +402,30 @@ using namespace fhe;
 
 extern "C" {
 
+// SHA-256(T || T || u64le(domain_len) || domain || data), T = SHA-256("fhe-rocm/rerandomize"): tagged_hash's
+// construction, the domain's length ahead of it so that (domain, data) splits one way only
+int fhe_rerandomize_seed(const uint8_t* domain, size_t domain_len, const uint8_t* data, size_t data_len, uint8_t out[32]) {
+    if (!out || (domain_len && !domain) || (data_len && !data)) {
+        set_error("null argument to fhe_rerandomize_seed");
+        return FHE_ERR_INVALID;
+    }
+    static const char tag[] = "fhe-rocm/rerandomize";
+    Sha256 t;
+    t.update((const uint8_t*)tag, sizeof tag - 1);
+    const auto th = t.final();
+    Sha256 s;
+    s.update(th.data(), 32);
+    s.update(th.data(), 32);
+    uint8_t L[8];
+    for (int i = 0; i < 8; ++i) L[i] = (uint8_t)((uint64_t)domain_len >> (8 * i));
+    s.update(L, 8);
+    if (domain_len) s.update(domain, domain_len);
+    if (data_len) s.update(data, data_len);
+    const auto h = s.final();
+    std::memcpy(out, h.data(), 32);
+    return FHE_OK;
+}
+
 int fhe_schnorr_public_key(const uint8_t privkey[32], uint8_t pubkey_x[32]) {
     if (!privkey || !pubkey_x) return FHE_ERR_INVALID;
     Pt p = pubkey_even_y(nmod(U256::from_be(privkey)));

@@ -13,6 +13,8 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
                                       decompress; Context.set_compression_key installs it from its bodies)
   CompactPublicKey / CompactCiphertextList   tfhe's public-key encryption: builder(pk).push(..).build_packed()
                                       without any secret, .expand() on the GPU
+  Context.set_public_key / x.re_randomize(seed)   tfhe's re_randomize: a fresh public-key encryption of zero added
+                                      to every block on the GPU (rerandomize_host: the host definition)
   Schnorr.sign_fhe_with_k0 / sign_fhe src/schnorr.rs:154-290
 All ciphertext arithmetic runs on the GPU through lib/libfhe_rocm.so; this package only marshals.
 """
@@ -24,5 +26,6 @@ from .integer import (  # noqa: F401,E402
     LEVEL_SPLIT, level_log, rank_pbs, stats, to_u32_digits,
     CompressedBigUintFHE, CompressedFheUint, CompressedFheUint8, CompressedFheUint32, CompressedFheUint64,
     CompressedFheUint128, CompressedFheUint256, CompressedCiphertextList,
-    CompactCiphertextList, CompactCiphertextListBuilder)
+    CompactCiphertextList, CompactCiphertextListBuilder,
+    rerandomization_seed, rerandomize_host, rerandomize_rows, rerandomize_zero_host)
 from .schnorr import Schnorr, compute_nonce, public_key_x  # noqa: F401,E402

@@ -284,6 +284,14 @@ _SIGNATURES = [
     ("fhe_compact_list_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("fhe_compact_list_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("fhe_compact_list_extract_rows", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_rerandomize_host", C.c_int, [C.c_void_p, C.c_char_p, u64p, C.c_size_t]),
+    ("fhe_rerandomize_zero_host", C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t]),
+    ("fhe_set_public_key", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fhe_radix_rerandomize", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("fhe_biguint_rerandomize", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("fhe_rerandomize_rows", C.c_int, [C.c_void_p, C.c_char_p, u64p, C.c_size_t, u64p]),
+    ("fhe_ctx_time_rerand_zero", C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_float)]),
+    ("fhe_rerandomize_seed", C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, u8p]),
     ("fhe_schnorr_public_key", C.c_int, [u8p, u8p]),
     ("fhe_schnorr_compute_nonce", C.c_int, [u8p, u8p, C.c_size_t, u8p, u8p]),
     ("fhe_schnorr_sign_with_k0", C.c_int, [u8p, C.c_size_t, u8p, u8p, u8p]),

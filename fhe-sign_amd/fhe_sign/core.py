@@ -421,6 +421,10 @@ class Context:
             check(load().fhe_set_compression_key(self._h, key.handle))
         self._comp_params = key.params
 
+    def set_public_key(self, pk: "CompactPublicKey") -> None:
+        """after set_server_key; the next set_server_key drops it.  Uploads A and B (32 KB) for re_randomize"""
+        check(load().fhe_set_public_key(self._h, pk.handle))
+
     def export_compression_state(self):
         """(byte planes int8, Fourier BSK float64, its E layout float64) of the installed compression key
         (test hook: fhe_ctx_export_compression_state)"""

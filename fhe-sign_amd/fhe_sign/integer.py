@@ -117,6 +117,15 @@ class FheUint:
         check(load().fhe_radix_export(_ctx().handle, self._h, ptr(out), out.size))
         return out.reshape(nb, 2049)
 
+    def re_randomize(self, seed=None):
+        """tfhe-rs' re_randomize under the CompactPublicKey (Context.set_public_key): a new FheUint, every
+        block this one's plus a fresh public-key encryption of zero (fhe_radix_rerandomize); self is untouched.
+        seed: 32 bytes used for this call only (rerandomization_seed), or None for OS entropy -- refused under a
+        communicator of more than one rank, where every rank passes the same seed."""
+        h = C.c_void_p()
+        check(load().fhe_radix_rerandomize(_ctx().handle, self._h, _rerand_seed(seed), C.byref(h)))
+        return self._wrap(h, self.bits)
+
     # ---- helpers
     def _bin(self, fn, other):
         h = C.c_void_p()
@@ -397,8 +406,57 @@ class BigUintFHE:
             lib.fhe_columns_destroy(h)
         return sum(int(x) << (64 * i) for i, x in enumerate(w))
 
+    def re_randomize(self, seed=None):
+        """FheUint.re_randomize over the digits in order, 16 blocks each (fhe_biguint_rerandomize); the empty
+        vector gives the empty vector"""
+        h = C.c_void_p()
+        check(load().fhe_biguint_rerandomize(_ctx().handle, self._h, _rerand_seed(seed), C.byref(h)))
+        return BigUintFHE(h)
+
     __add__ = add
     __mul__ = mul
+
+
+def _rerand_seed(seed):
+    if seed is None:
+        return None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a re-randomization seed is 32 bytes")
+    return seed
+
+
+def rerandomize_host(public_key, seed, rows) -> np.ndarray:
+    """the host definition of re_randomize (fhe_rerandomize_host): a re-randomized copy of `rows` (n x 2049
+    words, e.g. FheUint.export()) under the CompactPublicKey and the 32-byte seed; no context, no GPU"""
+    out = np.array(rows, dtype=np.uint64, order="C").reshape(-1, 2049)
+    check(load().fhe_rerandomize_host(public_key.handle, _rerand_seed(seed), ptr(out), out.shape[0]))
+    return out
+
+
+def rerandomize_zero_host(public_key, seed, nblocks):
+    """test hook (fhe_rerandomize_zero_host): (Z_A (nchunks, 2048), Z_B (nblocks,)) of the zero encryptions"""
+    chunks = (nblocks + 2047) // 2048
+    za, zb = np.zeros((chunks, 2048), np.uint64), np.zeros(nblocks, np.uint64)
+    check(load().fhe_rerandomize_zero_host(public_key.handle, _rerand_seed(seed), nblocks, ptr(za), za.size, ptr(zb), zb.size))
+    return za, zb
+
+
+def rerandomize_rows(seed, rows, ctx=None) -> np.ndarray:
+    """test hook (fhe_rerandomize_rows): the GPU path over n x 2049 host words, any n up to 2^24"""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2049)
+    out = np.zeros_like(rows)
+    check(load().fhe_rerandomize_rows((ctx or _ctx()).handle, _rerand_seed(seed), ptr(rows), rows.shape[0], ptr(out)))
+    return out
+
+
+def rerandomization_seed(domain: bytes, data: bytes) -> bytes:
+    """fhe_rerandomize_seed: the tagged SHA-256 replicas and ranks derive one call's seed from (a request id, a
+    message hash).  A seed an adversary can predict before choosing the ciphertext protects nothing."""
+    domain, data = bytes(domain), bytes(data)
+    out = (C.c_uint8 * 32)()
+    check(load().fhe_rerandomize_seed(domain, len(domain), data, len(data), out))
+    return bytes(out)
 
 
 SEEDED_RADIX, SEEDED_BIGUINT = 0, 1  # FHE_SEEDED_*

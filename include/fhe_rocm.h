@@ -831,6 +831,56 @@ int fhe_compact_list_expand_biguint(fhe_ctx* ctx, const fhe_compact_list* x, uin
  * flushes and waits like a download. */
 int fhe_compact_list_extract_rows(fhe_ctx* ctx, const fhe_compact_list* x, uint64_t* rows, size_t nwords);
 
+/* ------------------------------------------------- re-randomization under the public key */
+/* tfhe-rs' re_randomize under the CompactPublicKey: a fresh public-key encryption of ZERO is added to every
+ * block of a value, so the ciphertext that enters a circuit has never been seen before -- the answer to the
+ * IND-CPA-D setting of an engine whose decryptions become public (a signature is one).  Notation as above.
+ * Blocks 0 .. n-1 of the value form chunks of 2048; from the 32-byte RE-RANDOMIZATION SEED, chunk c takes R
+ * (bit i = bit i & 63 of u64 word 32 c + (i >> 6), nonce {109, "ROCM", 0}), E1 (2048 words from u64 word
+ * 4096 c, nonce {110, "ROCM", 0}) and E2 (the words after E1, one per used block), the compact list's
+ * positions under stream ids of their own, and forms Z_A = A R + E1, Z_B[j] = (B R)[j] + E2[j].  Block i
+ * (t = i mod 2048 of chunk i / 2048): mask word u += Z_A[t - u] (u <= t), -= Z_A[t - u + 2048] (u > t), body +=
+ * Z_B[t].  A trivial block enters as mask 0, body delta value.  At most 2^24 blocks.  The added phase error
+ * E R + E2 - E1 S is below 2^30 in absolute value, against about 2^49.7 of a bootstrap's output: degree and
+ * noise label of a block are unchanged.  No bootstrap.  tfhe-rs' bytes are not reproduced (parity unpinned).
+ * SEED POLICY.  A seed is used for ONE call and then thrown away.  A seed that an adversary can predict before
+ * choosing the ciphertext protects nothing: derive it from something fixed only after the ciphertext is (or
+ * pass NULL).  seed = NULL draws 32 bytes from getrandom() and wipes them after the launch.  Under a
+ * communicator of more than one rank NULL is refused (the ranks would diverge): every rank passes the same
+ * seed, e.g. fhe_rerandomize_seed of a request id all ranks know. */
+/* In place on nblocks rows of 2049 words; no context, no GPU.  The word-for-word definition of the device
+ * path.  FHE_ERR_INVALID for a NULL argument or more than 2^24 blocks. */
+int fhe_rerandomize_host(const fhe_public_key* pk, const uint8_t seed[32], uint64_t* cts, size_t nblocks);
+/* Test hook: the zero encryptions alone.  za = Z_A of every chunk (2048 ceil(nblocks / 2048) words), zb = Z_B
+ * of the used coefficients (nblocks words). */
+int fhe_rerandomize_zero_host(const fhe_public_key* pk, const uint8_t seed[32], size_t nblocks, uint64_t* za,
+                              size_t za_words, uint64_t* zb, size_t zb_words);
+/* Uploads A and B (32 KB) once; after fhe_set_server_key, dropped by the next server-key install.  Rank-local:
+ * under a communicator every rank installs the same key (the broadcast of a server key drops it on receivers).
+ * FHE_ERR_NO_KEY without a server key; FHE_ERR_INVALID, the field named, if the key's parameters differ from
+ * the installed server key's. */
+int fhe_set_public_key(fhe_ctx* ctx, const fhe_public_key* pk);
+/* Out of place: fresh slots; x and everyone who shares its slots are untouched.  Pending bootstraps x depends
+ * on are launched first; then two gfx950 kernels (the zero encryptions; the extraction added to the source),
+ * stream-ordered, no collective.  Only the seed and the slot pointers cross the bus.  The result's blocks are
+ * real ciphertexts (a trivial block of x too).  BigUintFHE: the digits in order, 16 blocks each; the empty
+ * vector gives the empty vector.  FHE_ERR_NO_KEY without an installed public key. */
+int fhe_radix_rerandomize(fhe_ctx* ctx, const fhe_radix* x, const uint8_t seed[32] /* NULL: OS entropy */,
+                          fhe_radix** out);
+int fhe_biguint_rerandomize(fhe_ctx* ctx, const fhe_biguint* x, const uint8_t seed[32] /* NULL: OS entropy */,
+                            fhe_biguint** out);
+/* Test hook: the device path over nblocks host rows of 2049 words (any count up to 2^24, where a radix integer
+ * stops at 2048 blocks): upload into slots, re-randomize, download into out; flushes and waits like a download. */
+int fhe_rerandomize_rows(fhe_ctx* ctx, const uint8_t seed[32], const uint64_t* rows, size_t nblocks, uint64_t* out);
+/* Measurement hook: the zero-encryption kernel alone, `reps` launches for nblocks blocks between two HIP events
+ * on the context's stream; *ms = the mean per launch.  FHE_ERR_NO_KEY without an installed public key. */
+int fhe_ctx_time_rerand_zero(fhe_ctx* ctx, const uint8_t seed[32], size_t nblocks, uint32_t reps, float* ms);
+/* out = SHA-256(T || T || u64le(domain_len) || domain || data), T = SHA-256("fhe-rocm/rerandomize"): the
+ * signer's tagged hash.  Replicas and ranks derive the same seed from public context (a request id, a message
+ * hash); see the seed policy above for what that context must be. */
+int fhe_rerandomize_seed(const uint8_t* domain, size_t domain_len, const uint8_t* data, size_t data_len,
+                         uint8_t out[32]);
+
 /* ------------------------------------------------------------------- Schnorr / BIP-340 */
 /* The caller of the hot path (src/schnorr.rs).  32-byte scalars are big-endian.  The plaintext
  * EC / hash steps run on the host; the FHE block s = k + e*d runs on the GPU engine. */
