@@ -861,8 +861,9 @@ __global__ __launch_bounds__(256 * H, H == 1 ? 2 : 1) void k_blind_rotate_qy2(co
 // f64 operation sequence per ciphertext are qy2's: identical bits.  Forward stages 0-3 have wave-uniform
 // zetas (block indices of register bits only); stages 4-7 read 1 + 1 + 2 + 4 per-lane zetas from an LDS
 // table by (b9..b6), the inverse B stages 1 + 1 + 2 + 4 twiddles by (b1 b0), the inverse A stages
-// 1 + 1 + 2 + 4 from W in global memory (loop-invariant per lane); sibling blocks differ by exactly i
-// (fft_tables / zeta_table build them so).
+// 1 + 1 + 2 + 4 from a lane-ordered LDS copy of the W entries the lane needs (loop-invariant per lane: the
+// prologue fetches them once, not every step); sibling blocks differ by exactly i (fft_tables / zeta_table
+// build them so).
 namespace {
 // layout parameters (tools/lds_layout_qz.py): additive weights of b0..b9, index bits on lane bits 5..0.
 // Every ds_read_b128 / ds_write_b128 of A, B and E is conflict-free, and ZA keeps each quad of lanes
@@ -899,6 +900,10 @@ FHE_DEV constexpr int idx_zB(int L, int r) {  // r = (b5 b4 b3 b2)
 //                                        Z[128 + 8 U4 + 2 j] (j < 4)
 //   inverse twiddles by m2 = (b1 b0):    W[128 m2], W[64 m2], W[32 m2 + 128 j] (j < 2), W[16 m2 + 64 j] (j < 4)
 constexpr int ZZ_SZ = 16 * 9, ZT_SZ = 4 * 9;
+// LDS table of the inverse A twiddles, 8 rows of 64 in lane order (entry 64 k + L: every ds_read_b128 is
+// conflict-free), v = idx_zA(L, 0): W[8 v], W[4 v], W[2 v + 128 j] (j < 2), W[v + 64 j] (j < 4).  With it the
+// kernel's LDS is 81,280 bytes: two workgroups still fit a CU (tests/test_qz_tables.py)
+constexpr int ZW_SZ = 8 * 64;
 
 template <int K, class F>
 FHE_DEV void dit_pairs16(cplx (&x)[16], F&& tw) {
@@ -925,9 +930,11 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_qz(const uint64_t* __re
         clk_r0 = __builtin_amdgcn_s_memrealtime();
     }
     constexpr int ZL_Z = NC * 2 * ZR_SZ, ZL_T = ZL_Z + ZZ_SZ;
-    __shared__ __attribute__((aligned(16))) cplx s_lds[ZL_T + ZT_SZ];
+    constexpr int ZL_W = ZL_T + ZT_SZ;
+    __shared__ __attribute__((aligned(16))) cplx s_lds[ZL_W + ZW_SZ];
     cplx* s_z = s_lds + ZL_Z;
     cplx* s_t = s_lds + ZL_T;
+    cplx* s_w = s_lds + ZL_W;
     if (threadIdx.x < 128) {
         const int U4 = threadIdx.x >> 3, k = threadIdx.x & 7;
         const int zi = k == 0 ? 16 + U4 : k == 1 ? 32 + 2 * U4 : k < 4 ? 64 + 4 * U4 + 2 * (k - 2) : 128 + 8 * U4 + 2 * (k - 4);
@@ -948,6 +955,9 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_qz(const uint64_t* __re
     cplx* reg = s_lds + w * ZR_SZ;  // region 2 c + p
     const int v = idx_zA(L, 0);     // A layout: idx = 64 r + v (v = b5 .. b0)
     const int iB = idx_zB(L, 0);
+#pragma unroll
+    for (int k = 2 * w; k < 2 * w + 2; ++k)  // wave w fills rows 2 w and 2 w + 1 of the inverse A twiddles
+        s_w[64 * k + L] = W[k == 0 ? 8 * v : k == 1 ? 4 * v : k < 4 ? 2 * v + 128 * (k - 2) : v + 64 * (k - 4)];
     const int bA = zq(v), bB = zq(iB);
     const int bE = zq(idx_E(w, L, 0));
     const cplx* zt = s_z + 9 * (iB >> 6);  // (b9 .. b6) in B
@@ -991,7 +1001,7 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_qz(const uint64_t* __re
 #pragma unroll
     for (int c = 0; c < NC; ++c) e0n[c] = cmul(lane_factor(a_next[c]), pair_factor(a_next[c]));
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t bsk_rs = table_rsrc(bsk), ps_rs = table_rsrc(ps), w_rs = table_rsrc(W);
+    const __amdgpu_buffer_rsrc_t bsk_rs = table_rsrc(bsk), ps_rs = table_rsrc(ps);
     const cplx* Zu = Z;  // uniform zetas of stages 0-3: Z[1], Z[2], Z[4], Z[6], Z[8], Z[10], Z[12], Z[14]
     uint32_t upd = 0;
     bool red_in = false;
@@ -1035,20 +1045,24 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_qz(const uint64_t* __re
 #pragma unroll
         for (int r = 0; r < 16; ++r) reg[bA + zq(idx_zA(0, r))] = x[r];
         wave_sync();
+        // the zetas before the data, and the data in the first stage's pair order (r, r + 8): LDS reads return
+        // in issue order, so the first butterflies wait on the tables and a few data reads, not on 17 of 20
+        const cplx z4 = zt[0], z5 = zt[1];
+        const cplx z6[2] = {zt[2], zt[3]};
+        const cplx z7[4] = {zt[4], zt[5], zt[6], zt[7]};
 #pragma unroll
-        for (int r = 0; r < 16; ++r) x[r] = reg[bB + zq(idx_zB(0, r))];
+        for (int r = 0; r < 8; ++r) {
+            x[r] = reg[bB + zq(idx_zB(0, r))];
+            x[r + 8] = reg[bB + zq(idx_zB(0, r + 8))];
+        }
         // ---- phase B: stages 4-7 (register bits 3..0 = b5..b2)
         {
-            const cplx z4 = zt[0];
             dit_pairs16<3>(x, [&](int) { return z4; });
-            const cplx z5 = zt[1];
             dit_pairs16<2>(x, [&](int r) { return (r >> 3) ? mul_i(z5) : z5; });
-            const cplx z6[2] = {zt[2], zt[3]};
             dit_pairs16<1>(x, [&](int r) {
                 const cplx base = z6[r >> 3];
                 return (r >> 2 & 1) ? mul_i(base) : base;
             });
-            const cplx z7[4] = {zt[4], zt[5], zt[6], zt[7]};
             dit_pairs16<0>(x, [&](int r) {
                 const cplx base = z7[r >> 2];
                 return (r >> 1 & 1) ? mul_i(base) : base;
@@ -1109,22 +1123,21 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_qz(const uint64_t* __re
         }
         __builtin_amdgcn_s_setprio(0);
         __syncthreads();
-        // ---- B (inverse): b2 (register bit 0), b3, b4, b5 (bit 3)
+        // ---- B (inverse): b2 (register bit 0), b3, b4, b5 (bit 3); the twiddles before the data, as in phase B
+        const cplx w2 = conj_(tt[0]), w3 = tt[1];
+        const cplx w4[2] = {tt[2], tt[3]};
+        const cplx w5[4] = {tt[4], tt[5], tt[6], tt[7]};
 #pragma unroll
         for (int r = 0; r < 16; ++r) x[r] = reg[bB + zq(idx_zB(0, r))];
 #pragma unroll
         for (int c = 0; c < NC; ++c) e0n[c] = cmul(Ebn[c], Fn[c]);  // loaded before the first barrier
         {
-            const cplx w2 = conj_(tt[0]);
             dit_pairs16<0>(x, [&](int) { return w2; });
-            const cplx w3 = tt[1];
             dit_pairs16<1>(x, [&](int r) { return conj_((r & 1) ? mul_i(w3) : w3); });
-            const cplx w4[2] = {tt[2], tt[3]};
             dit_pairs16<2>(x, [&](int r) {
                 const cplx base = w4[r & 1];
                 return conj_((r & 2) ? mul_i(base) : base);
             });
-            const cplx w5[4] = {tt[4], tt[5], tt[6], tt[7]};
             dit_pairs16<3>(x, [&](int r) {
                 const cplx base = w5[r & 3];
                 return conj_((r & 4) ? mul_i(base) : base);
@@ -1134,12 +1147,11 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_qz(const uint64_t* __re
 #pragma unroll
         for (int r = 0; r < 16; ++r) reg[bB + zq(idx_zB(0, r))] = x[r];
         wave_sync();
-        // inverse twiddles of phase A: W[8 v], W[4 v], W[2 v + 128 j], W[v + 64 j] (loop-invariant per lane)
-        const bptr W8{w_rs, 128u * (uint32_t)v, 0u}, W4{w_rs, 64u * (uint32_t)v, 0u};
-        const bptr W2{w_rs, 32u * (uint32_t)v, 0u}, W1{w_rs, 16u * (uint32_t)v, 0u};
-        const cplx w6 = conj_(W8[0]), w7 = W4[0];
-        const cplx w8[2] = {W2[0], W2[128]};
-        const cplx w9[4] = {W1[0], W1[64], W1[128], W1[192]};
+        // inverse twiddles of phase A: W[8 v], W[4 v], W[2 v + 128 j], W[v + 64 j], rows 0-7 of s_w
+        const cplx* wl = s_w + L;
+        const cplx w6 = conj_(wl[0]), w7 = wl[64];
+        const cplx w8[2] = {wl[128], wl[192]};
+        const cplx w9[4] = {wl[256], wl[320], wl[384], wl[448]};
         cplx pst[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r)
@@ -1153,8 +1165,8 @@ __global__ __launch_bounds__(256, 2) void k_blind_rotate_qz(const uint64_t* __re
             const cplx base = w8[r & 1];
             return conj_((r & 2) ? mul_i(base) : base);
         });
-        // pairs 4-7's factors only now (w6 .. w8 are dead): all 16 at once with x, acc and the twiddles do
-        // not fit 256 registers
+        // pairs 4-7's factors only now (w6 .. w8 are dead): all 16 in flight across these stages take 255
+        // registers and measured no faster, nor did issuing this half a stage or two earlier
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < 16; ++r)

@@ -2,9 +2,9 @@
 """CPU emulation of k_blind_rotate_qz's data movement (br_qy.hip; no GPU): the forward transform
 phases A -> B -> E and the inverse E -> B -> A of one workgroup (two ciphertexts, one wave per
 polynomial in A and B), transcribed from the kernel -- registers, the LDS map zq, both exchanges, the
-LDS zeta / twiddle tables and the per-lane W indices -- and checked against the oracle's transforms
-(oracle/tfhe_oracle.c forward_twisted, fho_fft_inverse, restated in tools/qy_emulate.py) in numpy
-complex128.  The constants below are the kernel's; tests/test_qz_layout.py pins both.
+LDS zeta / twiddle tables and the lane-ordered table of the inverse-A twiddles -- and checked against
+the oracle's transforms (oracle/tfhe_oracle.c forward_twisted, fho_fft_inverse, restated in
+tools/qy_emulate.py) in numpy complex128.  The constants below are the kernel's; tests/test_qz_layout.py pins both.
 usage: python3 tools/qz_emulate.py"""
 import os
 import sys
@@ -22,6 +22,11 @@ ZR_SZ = sum(ZW) + 1
 REGION_BOUND = 1100                            # two workgroups per CU: 2 x (4 regions + tables) <= 160 KiB
 NC = 2
 Lv = np.arange(64)
+ZZ_SZ, ZT_SZ = 16 * 9, 4 * 9                   # the stride-9 tables s_z, s_t
+WT_ROWS = 8                                    # rows of the lane-ordered inverse-A twiddle table s_w
+ZW_SZ = WT_ROWS * 64
+ZL_W = 2 * NC * ZR_SZ + ZZ_SZ + ZT_SZ          # s_w's offset in complex entries: behind the regions, s_z and s_t
+LDS_BYTES = 16 * (ZL_W + ZW_SZ)                # the kernel's whole static LDS
 
 
 def zq(idx):
@@ -61,6 +66,28 @@ def tables():
         wi = 128 * m if k == 0 else 64 * m if k == 1 else 32 * m + 128 * (k - 2) if k < 4 else 16 * m + 64 * (k - 4)
         s_t[9 * m + k] = W[wi]
     return s_z, s_t
+
+
+def w_index(k, v):
+    """the W index row k of s_w holds for the lane whose A index is v: what the CMUX loop loaded from global
+    memory every step before the table existed (W[8 v], W[4 v], W[2 v + 128 j], W[v + 64 j])"""
+    return 8 * v if k == 0 else 4 * v if k == 1 else 2 * v + 128 * (k - 2) if k < 4 else v + 64 * (k - 4)
+
+
+def lane_twiddle_indices():
+    """the prologue's fill of s_w as W indices: thread t = 64 w + L writes entries 64 k + L of rows
+    k = 2 w, 2 w + 1 with v = idx_zA(L, 0); -1 where nothing was written"""
+    idx = np.full(ZW_SZ, -1)
+    for t in range(256):
+        w, L = t >> 6, t & 63
+        for k in (2 * w, 2 * w + 1):
+            idx[64 * k + L] = w_index(k, idx_zA(L, 0))
+    return idx
+
+
+def lane_twiddle_read(k, L):
+    """the entry of s_w the CMUX loop reads for row k in lane L"""
+    return 64 * k + L
 
 
 def pairs16(X, K, tw):
@@ -143,10 +170,11 @@ def inverse_BA(lds, w):
     pairs16(X, 3, lambda r: np.conj(sel_i(tt[4 + (r & 3)], r & 4)))
     store(lds, w, idx_zB, X)
     X = load(lds, w, idx_zA)
-    v = np.array([idx_zA(L, 0) for L in range(64)])
-    w6, w7 = W[8 * v], W[4 * v]
-    w8 = [W[2 * v], W[2 * v + 128]]
-    w9 = [W[v + 64 * j] for j in range(4)]
+    s_w = W[lane_twiddle_indices()]
+    wl = [s_w[lane_twiddle_read(k, Lv)] for k in range(WT_ROWS)]
+    w6, w7 = wl[0], wl[1]
+    w8 = [wl[2], wl[3]]
+    w9 = [wl[4 + j] for j in range(4)]
     pairs16(X, 0, lambda r: np.conj(w6))
     pairs16(X, 1, lambda r: np.conj(sel_i(w7, r & 1)))
     pairs16(X, 2, lambda r: np.conj(sel_i(w8[r & 1], r & 2)))
@@ -211,6 +239,15 @@ def conflict_score():
     return out, sum(a + b for a, b in out.values()) / 3.0
 
 
+def twiddle_table_conflicts():
+    """extra LDS-array cycles of the eight ds_read_b128 of s_w (0: conflict-free), over the four 16-lane groups"""
+    extra = 0
+    for k in range(WT_ROWS):
+        pos = np.array([ZL_W + lane_twiddle_read(k, L) for L in range(64)])
+        extra += sum(int(np.bincount(pos[g] % 16, minlength=16).max()) - 1 for g in RG)
+    return extra
+
+
 def main():
     ferr, ierr = run()
     print(f"forward: max |kernel layout - oracle forward_twisted| = {ferr:.3e}")
@@ -218,6 +255,8 @@ def main():
     assert ferr < 1e-9 and ierr < 1e-6
     per, mean = conflict_score()
     print(f"LDS array cycles per instruction (read, write; 4 / 8 conflict-free): {per}; mean read + write {mean:.2f}")
+    assert twiddle_table_conflicts() == 0 and 2 * LDS_BYTES <= 160 * 1024
+    print(f"inverse-A twiddle table: {ZW_SZ} entries at {ZL_W}, conflict-free; LDS {LDS_BYTES} B a workgroup")
     print("qz layouts OK")
 
 
