@@ -354,13 +354,18 @@ int fhe_ctx::ensure_ks(size_t count) {
 }
 
 hipError_t fhe_ctx::keyswitch(const uint64_t* in, const fhe::PbsDesc* desc, size_t count) {
+    hipError_t e;
     if (ks_kernel == FHE_KS_MFMA) {
         if (ensure_ks(count) != FHE_OK) return hipErrorOutOfMemory;
-        return launch_keyswitch_mfma(in, desc, (int)count, d_ksk_planes, d_ks_digits, d_ks_body, d_ms, ms_stride,
-                                     (int)p.n, stream);
+        e = launch_keyswitch_mfma(in, desc, (int)count, d_ksk_planes, d_ks_digits, d_ks_body, d_ms, ms_stride, (int)p.n,
+                                  stream);
+    } else if (desc) {
+        e = launch_keyswitch_desc(desc, (int)count, d_ksk, d_ms, ms_stride, (int)p.n, stream);
+    } else {
+        e = launch_keyswitch(in, (int)count, d_ksk, d_ms, ms_stride, (int)p.n, stream);
     }
-    if (desc) return launch_keyswitch_desc(desc, (int)count, d_ksk, d_ms, ms_stride, (int)p.n, stream);
-    return launch_keyswitch(in, (int)count, d_ksk, d_ms, ms_stride, (int)p.n, stream);
+    if (e != hipSuccess || ms_mode != FHE_MS_CENTERED) return e;
+    return launch_ms_center(d_ms, count, p.n, (size_t)ms_stride, stream);
 }
 
 hipError_t fhe_ctx::blind_rotate(const fhe::PbsDesc* desc, const uint32_t* lut_idx, uint64_t* out, size_t count) {

@@ -60,6 +60,9 @@ struct fhe_ctx {
     double2* d_mono = nullptr;      // monomial table E[4096] of the multi-bit blind rotation (mono_table)
     int8_t* d_ksk_planes = nullptr; // KSK as balanced signed-byte planes (ks_mfma.hip)
     int ks_kernel = FHE_KS_MFMA;
+    // fhe_ctx_set_modulus_switch: FHE_MS_CENTERED makes keyswitch() follow its kernel with k_ms_center on
+    // d_ms (ms_center.hip), so every level launched from then on hands the blind rotation centered rows
+    int ms_mode = FHE_MS_STANDARD;
     // classic throughput kernel (fhe_ctx_set_br_kernel): FHE_BR_AUTO = qz (two ciphertexts per workgroup,
     // one wave per polynomial; it replaced qy2 here, same quantisation) where its rounds of 1024 (256 CUs x
     // 2 workgroups x 2) fill well -- from kQy2Min bootstraps on, and above 960 when the last round is more
@@ -157,7 +160,8 @@ struct fhe_ctx {
     // and makes `np` the context's parameters.
     int adopt_key_params(const fhe::Params& np, bool had_key);
     int ensure_ks(size_t count);
-    // keyswitch of `count` inputs (contiguous big LWE in `in`, or descriptors) into d_ms
+    // keyswitch of `count` inputs (contiguous big LWE in `in`, or descriptors) into d_ms; in centered mode
+    // the rows' bodies are then corrected in place (k_ms_center), behind the keyswitch on the stream
     hipError_t keyswitch(const uint64_t* in, const fhe::PbsDesc* desc, size_t count);
     int ensure_stage(size_t count);
     int sync_luts();

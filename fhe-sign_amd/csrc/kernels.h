@@ -1,4 +1,4 @@
-// kernels.h -- host launchers for the gfx950 kernels (pbs_kernels.hip, ks_mfma.hip, br_wide.hip, br_qy.hip).
+// kernels.h -- host launchers for the gfx950 kernels (pbs_kernels.hip, ks_mfma.hip, ms_center.hip, br_wide.hip, br_qy.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,6 +56,10 @@ hipError_t launch_keyswitch(const uint64_t* in, int count, const uint64_t* ksk, 
 // descriptor-driven keyswitch (radix layer): fused linear prologue
 hipError_t launch_keyswitch_desc(const PbsDesc* desc, int count, const uint64_t* ksk, uint64_t* small,
                                  int ks_stride, int n, hipStream_t s);
+// centered modulus switch (ms_center.hip), in place on `count` rows of `stride` words: word n of every row
+// -= (sum over the n mask words of their signed rounding residues to the 2^52 grid) >> 1; reads words
+// 0 .. n, writes word n
+hipError_t launch_ms_center(uint64_t* rows, size_t count, uint32_t n, size_t stride, hipStream_t s);
 // latency kernel: one ciphertext per 512-thread workgroup (br_wide.hip); desc or lut_idx/out mode
 // grouping 1 (classic) or 2 (multi-bit: bsk holds 3 GGSWs per pair of key bits, mono = E[4096])
 hipError_t launch_blind_rotate_wide(const uint64_t* ms, int ms_stride, const PbsDesc* desc, const uint32_t* lut_idx,

@@ -15,12 +15,15 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
                                       without any secret, .expand() on the GPU
   Context.set_public_key / x.re_randomize(seed)   tfhe's re_randomize: a fresh public-key encryption of zero added
                                       to every block on the GPU (rerandomize_host: the host definition)
+  Context.set_modulus_switch("centered")   tfhe's centered mean noise reduction: the public half of the modulus
+                                      switch's rounding error leaves the body on the GPU before every blind
+                                      rotation (ms_center_host: the host definition)
   Schnorr.sign_fhe_with_k0 / sign_fhe src/schnorr.rs:154-290
 All ciphertext arithmetic runs on the GPU through lib/libfhe_rocm.so; this package only marshals.
 """
 from ._lib import CompressionParams, FheError, FheParams, load  # noqa: F401
 from .core import (ClientKey, CompactPublicKey, CompressedCompressionKey, CompressedServerKey, CompressionKey, CompressionKeys, CompressionPrivateKey, Context, ServerKey, comm_unique_id, default_params,  # noqa: F401
-                   default_compression_params, generate_keys, multi_bit_params, tuning)
+                   default_compression_params, generate_keys, ms_center_host, ms_stride, multi_bit_params, tuning)
 from .integer import (  # noqa: F401,E402
     COMPAT, FAST, PUBLIC, BigUintFHE, FheBool, FheUint, FheUint8, FheUint32, FheUint64, FheUint128, FheUint256, set_server_key,
     LEVEL_SPLIT, level_log, rank_pbs, stats, to_u32_digits,

@@ -102,6 +102,11 @@ _SIGNATURES = [
     ("fhe_ctx_set_wide_threshold", C.c_int, [C.c_void_p, C.c_int]),
     ("fhe_ctx_set_br_kernel", C.c_int, [C.c_void_p, C.c_int]),
     ("fhe_ctx_set_ks_kernel", C.c_int, [C.c_void_p, C.c_int]),
+    ("fhe_ctx_set_modulus_switch", C.c_int, [C.c_void_p, C.c_int]),
+    ("fhe_ctx_get_modulus_switch", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("fhe_ms_center_host", C.c_int, [u64p, C.c_size_t, C.c_uint32, C.c_size_t]),
+    ("fhe_ms_center_rows", C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_uint32, C.c_size_t]),
+    ("fhe_ctx_time_ms_center", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32, C.POINTER(C.c_float)]),
     ("fhe_keyswitch_batch", C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
     ("fhe_pbs_lincomb_batch", C.c_int, [C.c_void_p, u64p, C.c_size_t, u32p, u32p, C.POINTER(C.c_int64), u64p, u32p,
                                         C.c_size_t, u64p, u64p]),

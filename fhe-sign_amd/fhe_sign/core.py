@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CompressionParams, FheParams, check, load, ptr, serialize_with
+from ._lib import CompressionParams, FheError, FheParams, check, load, ptr, serialize_with
 
 BIG_CT = 2049  # big LWE ciphertext words
 
@@ -382,6 +382,45 @@ def generate_keys(params: FheParams | None = None, seed: int | None = None, devi
     return ClientKey(ck, p), ServerKey(sk, p)
 
 
+# fhe_ctx_set_modulus_switch: FHE_MS_STANDARD, FHE_MS_CENTERED
+MODULUS_SWITCH_NAMES = ("standard", "centered")
+MS_PAD_WORD = 0xA5A55A5AC3C33C3C  # what ms_center_host / Context.ms_center_rows put into a row's padding
+
+
+def modulus_switch_mode(name: str) -> int:
+    """the FHE_MS_* value of a mode name; an unknown one is refused here as the library refuses an unknown value"""
+    if name not in MODULUS_SWITCH_NAMES:
+        raise FheError(f"fhe error -1: unknown modulus switch mode {name!r} (one of {MODULUS_SWITCH_NAMES})", -1)
+    return MODULUS_SWITCH_NAMES.index(name)
+
+
+def ms_stride(n: int) -> int:
+    """words per row of the bootstrap workspace: n + 1 rounded up to 8 (64-byte rows)"""
+    return (n + 1 + 7) // 8 * 8
+
+
+def _ms_center_layout(rows, stride):
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rows.ndim != 2 or rows.shape[1] < 2:
+        raise ValueError("rows must be (count, n + 1) words")
+    n = rows.shape[1] - 1
+    stride = n + 1 if stride is None else int(stride)
+    if stride < n + 1:
+        raise ValueError("stride must be at least n + 1")
+    buf = np.full((rows.shape[0], stride), MS_PAD_WORD, np.uint64)
+    buf[:, :n + 1] = rows
+    return buf, n
+
+
+def ms_center_host(rows, stride=None) -> np.ndarray:
+    """the host definition of the centered modulus switch (fhe_ms_center_host) over (count, n + 1) rows:
+    body -= (sum of the mask words' signed rounding residues to the 2^52 grid) >> 1.  Laid out and returned as
+    Context.ms_center_rows does: (count, stride) words, padding included.  No GPU."""
+    buf, n = _ms_center_layout(rows, stride)
+    check(load().fhe_ms_center_host(ptr(buf), buf.shape[0], n, buf.shape[1]))
+    return buf
+
+
 class Context:
     """One GPU + installed server key (tfhe::set_server_key, src/schnorr.rs:443)."""
 
@@ -524,6 +563,33 @@ class Context:
     def set_ks_kernel(self, kind: int) -> None:
         """0 = 64-bit VALU keyswitch, 1 = int8 matrix-core keyswitch (default); identical results"""
         check(load().fhe_ctx_set_ks_kernel(self._h, int(kind)))
+
+    def set_modulus_switch(self, mode: str) -> None:
+        """"standard" (default) or "centered" (fhe_ctx_set_modulus_switch): in centered mode every keyswitch this
+        context launches from now on is followed by k_ms_center, which takes the public half of the modulus
+        switch's rounding error out of the body (sigma 5.9 -> 4.2 grid steps at n = 834).  Launches nothing itself;
+        under a communicator every rank sets the same mode."""
+        check(load().fhe_ctx_set_modulus_switch(self._h, modulus_switch_mode(mode)))
+
+    @property
+    def modulus_switch(self) -> str:
+        m = C.c_int(-1)
+        check(load().fhe_ctx_get_modulus_switch(self._h, C.byref(m)))
+        return MODULUS_SWITCH_NAMES[m.value]
+
+    def ms_center_rows(self, rows: np.ndarray, stride=None) -> np.ndarray:
+        """test hook (fhe_ms_center_rows): k_ms_center over (count, n + 1) host rows, laid out with `stride` words
+        per row (default n + 1; ms_stride(n) is the bootstrap workspace's), the padding filled with MS_PAD_WORD.
+        Returns all (count, stride) words as they come back, padding included.  Needs no server key."""
+        buf, n = _ms_center_layout(rows, stride)
+        check(load().fhe_ms_center_rows(self._h, ptr(buf), buf.shape[0], n, buf.shape[1]))
+        return buf
+
+    def time_ms_center(self, count: int, n: int, stride: int, reps: int = 30) -> float:
+        """measurement hook (fhe_ctx_time_ms_center): mean ms of one k_ms_center launch over count rows"""
+        ms = C.c_float()
+        check(load().fhe_ctx_time_ms_center(self._h, int(count), int(n), int(stride), int(reps), C.byref(ms)))
+        return float(ms.value)
 
     def set_wide_threshold(self, threshold: int) -> None:
         check(load().fhe_ctx_set_wide_threshold(self._h, int(threshold)))

@@ -180,6 +180,40 @@ int fhe_ctx_set_wide_threshold(fhe_ctx* ctx, int threshold);
 #define FHE_BR_QZ 9 /* br_qy.hip k_blind_rotate_qz: classic, two ciphertexts per workgroup, one wave per polynomial in the transforms (no lane transposes); 8 is not a kind */
 int fhe_ctx_set_br_kernel(fhe_ctx* ctx, int kind);
 
+/* Modulus switch of the bootstrap's input.  The blind rotation rounds every word of the keyswitched row to the
+ * 2^52 grid (12 bits kept).  res(x) = (int64)((x + 2^51) & (2^52 - 1)) - 2^51 is the signed distance of x from
+ * the multiple of 2^52 it is rounded to, in [-2^51, 2^51).  The rounding adds sum_i res(a[i]) s[i] to the
+ * phase; for a binary key of weight hw that is a standard deviation of sqrt(hw / 12 + 1 / 12) grid steps
+ * (5.9 at n = 834, of a decode margin of 64): the largest term of a bootstrap's failure probability.
+ * FHE_MS_STANDARD (default) leaves the rows as the keyswitch wrote them.
+ * FHE_MS_CENTERED removes the public half of that sum first (tfhe-rs' centered mean noise reduction): with
+ *   S = sum_{i < n} res(a[i])  (int64; |S| <= n 2^51)      b' = b - (uint64)(S >> 1)  (arithmetic shift, wrapping)
+ * the row (a, b') enters the unchanged modulus switch.  The remaining error sum_i res(a[i]) (s[i] - 1/2) has
+ * standard deviation sqrt(n / 48 + 1 / 12) whatever the key is: 4.2 steps at n = 834.  Mask words are
+ * unchanged; a row whose mask words are multiples of 2^52 is unchanged.  One more gfx950 kernel (k_ms_center,
+ * ms_center.hip) runs on the stream right after every keyswitch kernel the context launches: fhe_pbs_batch
+ * [_device], fhe_keyswitch_batch (the rows as the blind rotation will read them), fhe_pbs_lincomb_batch (its
+ * `small` output included) and every level of the radix layer, fan-out slices included.  The decompression
+ * bootstrap is not touched: its 12-bit stored words have no residue.  Same keys, LUTs, noise labels.
+ * The mode applies to levels launched after the call; the call launches and flushes nothing.  Per context:
+ * under a communicator every rank sets the same mode (as with fhe_ctx_set_br_kernel, nothing is broadcast),
+ * or the ranks' slices of a level differ.  An unknown mode: FHE_ERR_INVALID with a message. */
+#define FHE_MS_STANDARD 0
+#define FHE_MS_CENTERED 1
+int fhe_ctx_set_modulus_switch(fhe_ctx* ctx, int mode);
+int fhe_ctx_get_modulus_switch(fhe_ctx* ctx, int* mode);
+/* The definition on the host, in place on `count` rows of `stride` words (mask words 0 .. n-1, body at n, the
+ * rest padding that is neither read nor written); no context, no GPU.  FHE_ERR_INVALID unless
+ * 1 <= n <= FHE_MS_CENTER_MAX_N (the sum stays inside int64) and stride >= n + 1. */
+#define FHE_MS_CENTER_MAX_N 2048u
+int fhe_ms_center_host(uint64_t* rows, size_t count, uint32_t n, size_t stride);
+/* Test hook: k_ms_center over host rows -- upload with the given stride, run, download.  Needs no server key,
+ * so any n runs without a key generation.  Same validation; at most 2^31 - 1 rows.  Synchronous. */
+int fhe_ms_center_rows(fhe_ctx* ctx, uint64_t* rows, size_t count, uint32_t n, size_t stride);
+/* Measurement hook: k_ms_center alone, `reps` launches over count x stride scratch words between two HIP
+ * events on the context's stream; *ms = the mean per launch. */
+int fhe_ctx_time_ms_center(fhe_ctx* ctx, size_t count, uint32_t n, size_t stride, uint32_t reps, float* ms);
+
 /* Keyswitch: int8 matrix-core contraction against the KSK's byte planes (FHE_KS_MFMA, default) or
  * the 64-bit VALU kernel (FHE_KS_VALU).  Both are exact: identical small LWE words. */
 #define FHE_KS_VALU 0
