@@ -110,8 +110,8 @@ int tx_bcast_device(fhe_ctx* c, void* dev, size_t bytes, int root) {
 // broadcast `bytes` of host memory from root (in place on every rank), through a device bounce buffer
 int bcast_host(fhe_ctx* c, void* host, size_t bytes, int root) {
     if (c->has_tx) return tx_check(c->tx.bcast(c->tx.user, host, bytes, root), "broadcast");
-    void* d = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&d, bytes));
+    DeviceBuf<uint8_t> d;  // freed on return, behind the waits below
+    FHE_HIP_CHECK(d.grow(bytes));
     ncclComm_t cm = (ncclComm_t)c->comm;
     int rc = hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? FHE_OK : FHE_ERR_HIP;
     if (!rc)
@@ -120,7 +120,6 @@ int bcast_host(fhe_ctx* c, void* host, size_t bytes, int root) {
     if (!rc) rc = hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess ? FHE_OK : FHE_ERR_HIP;
     if (!rc) rc = comm_wait_impl(c, "ncclBroadcast");
     if (c->comm) (void)hipStreamSynchronize(c->stream);  // (after an abort the stream may not drain)
-    (void)hipFree(d);
     return rc;
 }
 
@@ -133,8 +132,8 @@ int agree(fhe_ctx* c, int ok, int* all) {
         return rc;
     }
     int32_t v = ok ? 1 : 0;
-    int32_t* d = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&d, sizeof v));
+    DeviceBuf<int32_t> d;  // freed on return, behind the waits below
+    FHE_HIP_CHECK(d.grow(1));
     ncclComm_t cm = (ncclComm_t)c->comm;
     int rc = hipMemcpyAsync(d, &v, sizeof v, hipMemcpyHostToDevice, c->stream) == hipSuccess ? FHE_OK : FHE_ERR_HIP;
     if (!rc)
@@ -143,7 +142,6 @@ int agree(fhe_ctx* c, int ok, int* all) {
     if (!rc) rc = hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, c->stream) == hipSuccess ? FHE_OK : FHE_ERR_HIP;
     if (!rc) rc = comm_wait_impl(c, "ncclAllReduce");
     if (c->comm) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
     *all = v;
     return rc;
 }
@@ -159,12 +157,10 @@ int comm_wait(fhe_ctx* c, const char* what) { return c->wait_stream(what); }
 }  // namespace
 
 int fhe_ctx::ensure_gather(size_t n) {
-    if (n <= gather_cap) return FHE_OK;
+    if (d_gather.fits(n * 2049)) return FHE_OK;
     FHE_HIP_CHECK(hipSetDevice(device));
     FHE_HIP_CHECK(hipStreamSynchronize(stream));  // a previous level may still read it
-    if (d_gather) FHE_HIP_CHECK(hipFree(d_gather));
-    gather_cap = std::max<size_t>(n, 4096);
-    FHE_HIP_CHECK(hipMalloc(&d_gather, gather_cap * 2049 * 8));
+    FHE_HIP_CHECK(d_gather.grow(std::max<size_t>(n, 4096) * 2049));
     return FHE_OK;
 }
 
@@ -258,11 +254,8 @@ int fhe_ctx::allreduce_min_u8(uint8_t* flags, size_t n) {
         return tx_check(tx.allreduce_min_u8(tx.user, flags, n), "all-reduce (dead nodes)");
     }
     if (!comm) return FHE_OK;
-    if (n > flags_cap) {  // grown rarely (a hipFree synchronises the device)
-        if (d_flags) FHE_HIP_CHECK(hipFree(d_flags));
-        flags_cap = std::max<size_t>(n, 1 << 16);
-        FHE_HIP_CHECK(hipMalloc(&d_flags, flags_cap));
-    }
+    // grown rarely (freeing device memory synchronises the device)
+    if (!d_flags.fits(n)) FHE_HIP_CHECK(d_flags.grow(std::max<size_t>(n, 1 << 16)));
     uint8_t* d = d_flags;
     ncclComm_t cm = (ncclComm_t)comm;
     int rc = hipMemcpyAsync(d, flags, n, hipMemcpyHostToDevice, stream) == hipSuccess ? FHE_OK : FHE_ERR_HIP;
@@ -419,11 +412,11 @@ int bcast_radix_groups(fhe_ctx* c, int root, std::vector<Radix>* groups) {
     }
     const size_t meta_words = (size_t)h.ngroups + 4 * (size_t)h.nblocks;
     const size_t data_words = (size_t)h.nslot * kBigCt;
-    uint32_t* d_meta = nullptr;
-    uint64_t* d_data = nullptr;
+    DeviceBuf<uint32_t> d_meta;
+    DeviceBuf<uint64_t> d_data;
     if (local_ok) {
-        hipError_t he = hipMalloc(&d_meta, std::max<size_t>(meta_words, 1) * 4);
-        if (he == hipSuccess) he = hipMalloc(&d_data, std::max<size_t>(data_words, 1) * 8);
+        hipError_t he = d_meta.grow(std::max<size_t>(meta_words, 1));
+        if (he == hipSuccess) he = d_data.grow(std::max<size_t>(data_words, 1));
         if (he != hipSuccess) {
             local_ok = 0;
             local_why = std::string("broadcast: ") + hipGetErrorString(he);
@@ -431,8 +424,8 @@ int bcast_radix_groups(fhe_ctx* c, int root, std::vector<Radix>* groups) {
     }
     auto release = [&] {
         (void)hipStreamSynchronize(c->stream);
-        if (d_meta) (void)hipFree(d_meta);
-        if (d_data) (void)hipFree(d_data);
+        (void)d_meta.reset();
+        (void)d_data.reset();
     };
     if (is_root && local_ok) {
         try {
@@ -613,24 +606,21 @@ int fhe_ctx_broadcast_server_key(fhe_ctx* c, int root) {
     const size_t bsk_doubles = (size_t)npoly * 1024 * 2;
     // Receivers: the new key lands in fresh buffers; the installed key (if any) stays in place and
     // usable until every collective and conversion has succeeded, then the two are swapped.
-    uint64_t* n_ksk = nullptr;
-    int8_t* n_planes = nullptr;
-    double2 *n_bsk = nullptr, *n_e = nullptr;
+    DeviceBuf<uint64_t> n_ksk;
+    DeviceBuf<int8_t> n_planes;
+    DeviceBuf<double2> n_bsk, n_e;
     auto drop_new = [&] {
         (void)hipStreamSynchronize(c->stream);
-        if (n_ksk) (void)hipFree(n_ksk);
-        if (n_planes) (void)hipFree(n_planes);
-        if (n_bsk) (void)hipFree(n_bsk);
-        if (n_e) (void)hipFree(n_e);
-        n_ksk = nullptr;
-        n_planes = nullptr;
-        n_bsk = n_e = nullptr;
+        (void)n_ksk.reset();
+        (void)n_planes.reset();
+        (void)n_bsk.reset();
+        (void)n_e.reset();
     };
     if (!is_root && local_ok) {
-        hipError_t he = hipMalloc(&n_ksk, ksk_words * 8);
-        if (he == hipSuccess) he = hipMalloc(&n_planes, fhe::ks_planes_bytes((int)p.n));
-        if (he == hipSuccess) he = hipMalloc(&n_bsk, bsk_doubles * 8);
-        if (he == hipSuccess) he = hipMalloc(&n_e, bsk_doubles * 8);
+        hipError_t he = n_ksk.grow(ksk_words);
+        if (he == hipSuccess) he = n_planes.grow(fhe::ks_planes_bytes((int)p.n));
+        if (he == hipSuccess) he = n_bsk.grow(bsk_doubles / 2);
+        if (he == hipSuccess) he = n_e.grow(bsk_doubles / 2);
         if (he != hipSuccess) {
             drop_new();
             local_ok = 0;
@@ -681,10 +671,10 @@ int fhe_ctx_broadcast_server_key(fhe_ctx* c, int root) {
         }
     }
     // commit: swap in the new key, release the old one
-    std::swap(c->d_ksk, n_ksk);
-    std::swap(c->d_ksk_planes, n_planes);
-    std::swap(c->d_bsk, n_bsk);
-    std::swap(c->d_bsk_e, n_e);
+    c->d_ksk.swap(n_ksk);
+    c->d_ksk_planes.swap(n_planes);
+    c->d_bsk.swap(n_bsk);
+    c->d_bsk_e.swap(n_e);
     drop_new();  // frees the previous key's buffers (null when there was none)
     return c->adopt_key_params(p, c->has_key);
 }

@@ -135,15 +135,27 @@ void make_lut_poly(const Params& p, const uint32_t* f, std::vector<uint64_t>* lu
 
 using namespace fhe;
 
+// (fhe_ctx_destroy) what is queued runs to its end, then the engine, the communicator, the events and the
+// stream go; the DeviceBuf members free themselves after this body
+fhe_ctx::~fhe_ctx() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    delete engine;
+    release_comm();
+    for (auto e : ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto e : prog_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
 int fhe_ctx::ensure_ms(size_t count) {
     if (count <= ms_cap) return FHE_OK;
-    if (d_ms) {
-        FHE_HIP_CHECK(hipStreamSynchronize(stream));  // previous levels may still read it
-        FHE_HIP_CHECK(hipFree(d_ms));
-    }
+    if (d_ms) FHE_HIP_CHECK(hipStreamSynchronize(stream));  // previous levels may still read it
+    ms_cap = 0;
     size_t cap = count < 256 ? 256 : count;
     ms_stride = (int)((p.n + 1 + 7) / 8 * 8);
-    FHE_HIP_CHECK(hipMalloc(&d_ms, cap * ms_stride * sizeof(uint64_t)));
+    FHE_HIP_CHECK(d_ms.grow(cap * ms_stride));
     ms_cap = cap;
     return FHE_OK;
 }
@@ -157,12 +169,9 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
         const int rc = release_public_key();
         if (rc) return rc;
     }
-    if (d_ms) {
-        FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read it
-        FHE_HIP_CHECK(hipFree(d_ms));
-        d_ms = nullptr;
-    }
+    if (d_ms) FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read it
     ms_cap = 0;
+    FHE_HIP_CHECK(d_ms.reset());
     ms_stride = 0;
     if (!had_key || !(p.msg_carry() == np.msg_carry() && p.delta() == np.delta())) {
         lut_ids.clear();
@@ -176,19 +185,18 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
 
 int fhe_ctx::release_compression() {
     if (stream) FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    void* ptrs[] = {d_pk_planes, d_cbsk, d_cbsk_e, d_pk_src, d_pk_digits, d_pk_body, d_pk_P, d_pk_out, d_cms, d_cpacked, d_cdesc};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    d_pk_planes = nullptr;
-    d_cbsk = d_cbsk_e = nullptr;
-    d_pk_src = nullptr;
-    d_pk_digits = nullptr;
-    d_pk_body = d_pk_P = nullptr;
-    d_pk_out = nullptr;
-    d_cms = nullptr;
-    d_cpacked = nullptr;
-    d_cdesc = nullptr;
     pk_cap = cms_cap = 0;
+    (void)d_pk_planes.reset();
+    (void)d_cbsk.reset();
+    (void)d_cbsk_e.reset();
+    (void)d_pk_src.reset();
+    (void)d_pk_digits.reset();
+    (void)d_pk_body.reset();
+    (void)d_pk_P.reset();
+    (void)d_pk_out.reset();
+    (void)d_cms.reset();
+    (void)d_cpacked.reset();
+    (void)d_cdesc.reset();
     cms_stride = 0;
     has_comp = false;
     return FHE_OK;
@@ -197,20 +205,13 @@ int fhe_ctx::release_compression() {
 int fhe_ctx::ensure_pk(size_t count) {
     if (count <= pk_cap) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    void* old[] = {d_pk_src, d_pk_digits, d_pk_body, d_pk_P, d_pk_out};
-    for (void* q : old)
-        if (q) FHE_HIP_CHECK(hipFree(q));
-    d_pk_src = nullptr;
-    d_pk_digits = nullptr;
-    d_pk_body = d_pk_P = nullptr;
-    d_pk_out = nullptr;
     pk_cap = 0;
     const size_t cap = std::max<size_t>(count, 256);
-    FHE_HIP_CHECK(hipMalloc(&d_pk_src, cap * sizeof(uint64_t*)));
-    FHE_HIP_CHECK(hipMalloc(&d_pk_digits, fhe::pk_digits_bytes((int)cap, (int)cp.ell)));
-    FHE_HIP_CHECK(hipMalloc(&d_pk_body, cap * 8));
-    FHE_HIP_CHECK(hipMalloc(&d_pk_P, cap * cp.cols() * 8));
-    FHE_HIP_CHECK(hipMalloc(&d_pk_out, cp.glwes(cap) * (size_t)fhe::pk_out_stride((int)cp.k, (int)cp.N)));
+    FHE_HIP_CHECK(d_pk_src.grow(cap));
+    FHE_HIP_CHECK(d_pk_digits.grow(fhe::pk_digits_bytes((int)cap, (int)cp.ell)));
+    FHE_HIP_CHECK(d_pk_body.grow(cap));
+    FHE_HIP_CHECK(d_pk_P.grow(cap * cp.cols()));
+    FHE_HIP_CHECK(d_pk_out.grow(cp.glwes(cap) * (size_t)fhe::pk_out_stride((int)cp.k, (int)cp.N)));
     pk_cap = cap;
     return FHE_OK;
 }
@@ -218,18 +219,12 @@ int fhe_ctx::ensure_pk(size_t count) {
 int fhe_ctx::ensure_cms(size_t count) {
     if (count <= cms_cap) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    void* old[] = {d_cms, d_cpacked, d_cdesc};
-    for (void* q : old)
-        if (q) FHE_HIP_CHECK(hipFree(q));
-    d_cms = nullptr;
-    d_cpacked = nullptr;
-    d_cdesc = nullptr;
     cms_cap = 0;
     const size_t cap = std::max<size_t>(count, 256);
     cms_stride = (int)((cp.lwe_dim() + 1 + 7) / 8 * 8);
-    FHE_HIP_CHECK(hipMalloc(&d_cms, cap * cms_stride * 8));
-    FHE_HIP_CHECK(hipMalloc(&d_cpacked, cp.glwes(cap) * cp.glwe_bytes(cp.L)));
-    FHE_HIP_CHECK(hipMalloc(&d_cdesc, cap * sizeof(fhe::PbsDesc)));
+    FHE_HIP_CHECK(d_cms.grow(cap * cms_stride));
+    FHE_HIP_CHECK(d_cpacked.grow(cp.glwes(cap) * cp.glwe_bytes(cp.L)));
+    FHE_HIP_CHECK(d_cdesc.grow(cap));
     cms_cap = cap;
     return FHE_OK;
 }
@@ -237,13 +232,11 @@ int fhe_ctx::ensure_cms(size_t count) {
 int fhe_ctx::ensure_stage(size_t count) {
     if (count <= stage_cap) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    if (d_stage_in) FHE_HIP_CHECK(hipFree(d_stage_in));
-    if (d_stage_out) FHE_HIP_CHECK(hipFree(d_stage_out));
-    if (d_stage_lut) FHE_HIP_CHECK(hipFree(d_stage_lut));
+    stage_cap = 0;
     size_t cap = count < 256 ? 256 : count;
-    FHE_HIP_CHECK(hipMalloc(&d_stage_in, cap * kBigCt * 8));
-    FHE_HIP_CHECK(hipMalloc(&d_stage_out, cap * kBigCt * 8));
-    FHE_HIP_CHECK(hipMalloc(&d_stage_lut, cap * 4));
+    FHE_HIP_CHECK(d_stage_in.grow(cap * kBigCt));
+    FHE_HIP_CHECK(d_stage_out.grow(cap * kBigCt));
+    FHE_HIP_CHECK(d_stage_lut.grow(cap));
     stage_cap = cap;
     return FHE_OK;
 }
@@ -295,15 +288,11 @@ int fhe_ctx::register_lut_half(const int32_t* half, uint32_t* id) {
 int fhe_ctx::sync_luts() {
     if (!luts_dirty) return FHE_OK;
     const size_t nl = h_luts.size() / kPolySize;
-    if (nl > d_luts_cap) {
+    if (!d_luts.fits(h_luts.size())) {
         // the stream may still read the old table: order the free behind it
-        if (d_luts) {
-            FHE_HIP_CHECK(hipStreamSynchronize(stream));
-            FHE_HIP_CHECK(hipFree(d_luts));
-        }
+        if (d_luts) FHE_HIP_CHECK(hipStreamSynchronize(stream));
         size_t cap = nl < 64 ? 64 : nl * 2;
-        FHE_HIP_CHECK(hipMalloc(&d_luts, cap * kPolySize * 8));
-        d_luts_cap = cap;
+        FHE_HIP_CHECK(d_luts.grow(cap * kPolySize));
     }
     FHE_HIP_CHECK(hipMemcpyAsync(d_luts, h_luts.data(), h_luts.size() * 8, hipMemcpyHostToDevice, stream));
     luts_dirty = false;
@@ -345,11 +334,11 @@ int fhe_ctx::ensure_ks(size_t count) {
     if (count <= ks_cap) return FHE_OK;
     FHE_HIP_CHECK(hipSetDevice(device));
     FHE_HIP_CHECK(hipStreamSynchronize(stream));  // previous levels may still read them
-    if (d_ks_digits) FHE_HIP_CHECK(hipFree(d_ks_digits));
-    if (d_ks_body) FHE_HIP_CHECK(hipFree(d_ks_body));
-    ks_cap = std::max<size_t>(count, 1024);
-    FHE_HIP_CHECK(hipMalloc(&d_ks_digits, fhe::ks_digits_bytes((int)ks_cap)));
-    FHE_HIP_CHECK(hipMalloc(&d_ks_body, ks_cap * 8));
+    ks_cap = 0;
+    const size_t cap = std::max<size_t>(count, 1024);
+    FHE_HIP_CHECK(d_ks_digits.grow(fhe::ks_digits_bytes((int)cap)));
+    FHE_HIP_CHECK(d_ks_body.grow(cap));
+    ks_cap = cap;
     return FHE_OK;
 }
 
@@ -489,11 +478,7 @@ int generate_device(fhe_ctx* c, const fhe_params* params, const KeyWords& seed, 
     }
     FHE_HIP_CHECK(hipSetDevice(c->device));
     const size_t kw = sko->ksk.size(), bw = sko->bsk.size();
-    uint64_t *d_ksk = nullptr, *d_bsk = nullptr, *d_lwe = nullptr, *d_glwe = nullptr, *d_msg = nullptr;
-    auto release = [&] {
-        for (uint64_t* q : {d_ksk, d_bsk, d_lwe, d_glwe, d_msg})
-            if (q) (void)hipFree(q);
-    };
+    DeviceBuf<uint64_t> d_ksk, d_bsk, d_lwe, d_glwe, d_msg;  // freed on return, behind the wait below
     const uint32_t ngg = p.ggsw_count();
     std::vector<uint64_t> msgs(ngg);  // per-GGSW messages (key bits or multi-bit pattern indicators)
     for (uint32_t q = 0; q < ngg; ++q) msgs[q] = p.ggsw_message(cko->lwe_sk.data(), q);
@@ -502,8 +487,8 @@ int generate_device(fhe_ctx* c, const fhe_params* params, const KeyWords& seed, 
         if (e == hipSuccess && r != hipSuccess) e = r;
         return e == hipSuccess;
     };
-    step(hipMalloc(&d_ksk, kw * 8)) && step(hipMalloc(&d_bsk, bw * 8)) && step(hipMalloc(&d_lwe, p.n * 8)) &&
-        step(hipMalloc(&d_glwe, kPolySize * 8)) && step(hipMalloc(&d_msg, ngg * 8)) &&
+    step(d_ksk.grow(kw)) && step(d_bsk.grow(bw)) && step(d_lwe.grow(p.n)) && step(d_glwe.grow(kPolySize)) &&
+        step(d_msg.grow(ngg)) &&
         step(hipMemcpyAsync(d_msg, msgs.data(), ngg * 8, hipMemcpyHostToDevice, c->stream)) &&
         step(hipMemcpyAsync(d_lwe, cko->lwe_sk.data(), p.n * 8, hipMemcpyHostToDevice, c->stream)) &&
         step(hipMemcpyAsync(d_glwe, cko->glwe_sk.data(), kPolySize * 8, hipMemcpyHostToDevice, c->stream)) &&
@@ -521,7 +506,6 @@ int generate_device(fhe_ctx* c, const fhe_params* params, const KeyWords& seed, 
     if (d_glwe) (void)hipMemsetAsync(d_glwe, 0, kPolySize * 8, c->stream);
     if (d_msg) (void)hipMemsetAsync(d_msg, 0, ngg * 8, c->stream);
     step(hipStreamSynchronize(c->stream));
-    release();
     if (e != hipSuccess) {
         set_error(std::string("device keygen: ") + hipGetErrorString(e));
         return FHE_ERR_HIP;
@@ -613,11 +597,10 @@ int fhe_ctx_create(int device, fhe_ctx** out) {
         return FHE_ERR_INVALID;
     }
     FHE_HIP_CHECK(hipSetDevice(device));
-    auto* c = new fhe_ctx();
+    std::unique_ptr<fhe_ctx> c(new fhe_ctx());  // an early return destroys what was created so far
     c->device = device;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
-        delete c;
         set_error(std::string("hipStreamCreate: ") + hipGetErrorString(e));
         return FHE_ERR_HIP;
     }
@@ -627,61 +610,40 @@ int fhe_ctx_create(int device, fhe_ctx** out) {
     zeta_table(&Z);
     std::vector<double2> zw;
     wide_zetas(Z, &zw);
-    FHE_HIP_CHECK(hipMalloc(&c->d_zeta_wide, zw.size() * sizeof(double2)));
+    FHE_HIP_CHECK(c->d_zeta_wide.grow(zw.size()));
     FHE_HIP_CHECK(hipMemcpy(c->d_zeta_wide, zw.data(), zw.size() * sizeof(double2), hipMemcpyHostToDevice));
-    FHE_HIP_CHECK(hipMalloc(&c->d_zeta_full, Z.size() * sizeof(double2)));
+    FHE_HIP_CHECK(c->d_zeta_full.grow(Z.size()));
     FHE_HIP_CHECK(hipMemcpy(c->d_zeta_full, Z.data(), Z.size() * sizeof(double2), hipMemcpyHostToDevice));
     lane_twiddles(W0, &W);
     wide_tables(W0, psi, &tww, &psiw);
     quad_tables(W0, psi, &twq, &psq);
-    FHE_HIP_CHECK(hipMalloc(&c->d_tw_quad, twq.size() * sizeof(double2)));
-    FHE_HIP_CHECK(hipMalloc(&c->d_psi_quad, psq.size() * sizeof(double2)));
+    FHE_HIP_CHECK(c->d_tw_quad.grow(twq.size()));
+    FHE_HIP_CHECK(c->d_psi_quad.grow(psq.size()));
     FHE_HIP_CHECK(hipMemcpy(c->d_tw_quad, twq.data(), twq.size() * sizeof(double2), hipMemcpyHostToDevice));
     FHE_HIP_CHECK(hipMemcpy(c->d_psi_quad, psq.data(), psq.size() * sizeof(double2), hipMemcpyHostToDevice));
-    FHE_HIP_CHECK(hipMalloc(&c->d_tw_wide, tww.size() * sizeof(double2)));
-    FHE_HIP_CHECK(hipMalloc(&c->d_psi_wide, psiw.size() * sizeof(double2)));
+    FHE_HIP_CHECK(c->d_tw_wide.grow(tww.size()));
+    FHE_HIP_CHECK(c->d_psi_wide.grow(psiw.size()));
     FHE_HIP_CHECK(hipMemcpy(c->d_tw_wide, tww.data(), tww.size() * sizeof(double2), hipMemcpyHostToDevice));
     FHE_HIP_CHECK(hipMemcpy(c->d_psi_wide, psiw.data(), psiw.size() * sizeof(double2), hipMemcpyHostToDevice));
     if (const char* e = getenv("FHE_WIDE_THRESHOLD")) c->wide_threshold = atoi(e);
     std::vector<double2> mono;
     mono_table(psi, &mono);
-    FHE_HIP_CHECK(hipMalloc(&c->d_mono, mono.size() * sizeof(double2)));
+    FHE_HIP_CHECK(c->d_mono.grow(mono.size()));
     FHE_HIP_CHECK(hipMemcpy(c->d_mono, mono.data(), mono.size() * sizeof(double2), hipMemcpyHostToDevice));
-    FHE_HIP_CHECK(hipMalloc(&c->d_W, W.size() * sizeof(double2)));
-    FHE_HIP_CHECK(hipMalloc(&c->d_psi, psi.size() * sizeof(double2)));
+    FHE_HIP_CHECK(c->d_W.grow(W.size()));
+    FHE_HIP_CHECK(c->d_psi.grow(psi.size()));
     FHE_HIP_CHECK(hipMemcpy(c->d_W, W.data(), W.size() * sizeof(double2), hipMemcpyHostToDevice));
     FHE_HIP_CHECK(hipMemcpy(c->d_psi, psi.data(), psi.size() * sizeof(double2), hipMemcpyHostToDevice));
-    *out = c;
+    *out = c.release();
     return FHE_OK;
 }
 
-void fhe_ctx_destroy(fhe_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    delete c->engine;
-    c->engine = nullptr;
-    (void)c->release_compression();
-    (void)c->release_public_key();
-    c->release_comm();
-    void* ptrs[] = {c->d_ksk, c->d_ksk_planes, c->d_ks_digits, c->d_ks_body, c->d_bsk, c->d_W, c->d_psi, c->d_tw_wide, c->d_psi_wide, c->d_tw_quad,
-                    c->d_psi_quad, c->d_zeta_wide, c->d_mono, c->d_bsk_e, c->d_zeta_full, c->d_flags, c->d_luts, c->d_ms, c->d_stage_in, c->d_stage_out, c->d_stage_lut, c->d_gather, c->d_clock};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto ev : c->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto ev : c->prog_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void fhe_ctx_destroy(fhe_ctx* c) { delete c; }
 
 namespace {
-struct DeviceFree {
-    void operator()(void* p) const { (void)hipFree(p); }
-};
 // The two ends every key install shares.  release_key: the stream is drained and the previous key's
-// buffers are freed -- from here until install_tail succeeds the context has no key.
+// buffers are freed, also those a failed install left behind -- from here until install_tail succeeds
+// the context has no key.
 int release_key(fhe_ctx* c) {
     if (c->has_comp) {  // a compression key belongs to the server key it was installed after
         const int rc = c->release_compression();
@@ -691,28 +653,29 @@ int release_key(fhe_ctx* c) {
         const int rc = c->release_public_key();
         if (rc) return rc;
     }
-    if (!c->has_key) return FHE_OK;
-    FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
-    FHE_HIP_CHECK(hipFree(c->d_ksk));
-    FHE_HIP_CHECK(hipFree(c->d_bsk));
-    FHE_HIP_CHECK(hipFree(c->d_bsk_e));
-    FHE_HIP_CHECK(hipFree(c->d_ksk_planes));
-    c->d_ksk_planes = nullptr;
-    c->d_ksk = nullptr;
-    c->d_bsk = nullptr;
-    c->d_bsk_e = nullptr;
+    if (c->has_key) FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->has_key = false;
+    FHE_HIP_CHECK(c->d_ksk.reset());
+    FHE_HIP_CHECK(c->d_bsk.reset());
+    FHE_HIP_CHECK(c->d_bsk_e.reset());
+    FHE_HIP_CHECK(c->d_ksk_planes.reset());
     return FHE_OK;
+}
+// Error end of a server-key install: waits for what the install queued, then frees the half-built key
+int drop_key(fhe_ctx* c, int rc) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)release_key(c);
+    return rc;
 }
 // install_tail: d_ksk and the Fourier d_bsk are filled (or being filled on the stream); derive the byte
 // planes and the E layout, wait, adopt the parameters, create the engine.
 int install_tail(fhe_ctx* c, const Params& p, bool had_key) {
     const int npoly = (int)(p.ggsw_count() * 4);
-    FHE_HIP_CHECK(hipMalloc(&c->d_ksk_planes, fhe::ks_planes_bytes((int)p.n)));
+    FHE_HIP_CHECK(c->d_ksk_planes.grow(fhe::ks_planes_bytes((int)p.n)));
     FHE_HIP_CHECK(launch_ksk_to_planes(c->d_ksk, (int)p.n, c->d_ksk_planes, c->stream));
     // two resident layouts: d_bsk for the latency kernel (br_wide.hip), d_bsk_e for the throughput
     // kernel (br_qy.hip); rounds 1-4 also kept br_quad.hip's and ran br_qx.hip (both retired in r5)
-    FHE_HIP_CHECK(hipMalloc(&c->d_bsk_e, (size_t)npoly * 1024 * sizeof(double2)));
+    FHE_HIP_CHECK(c->d_bsk_e.grow((size_t)npoly * 1024));
     FHE_HIP_CHECK(launch_bsk_to_e(c->d_bsk, npoly, c->d_bsk_e, c->stream));
     FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
     // the LUT tables survive a re-key with the same message space and delta (ids stay valid)
@@ -751,17 +714,15 @@ int fhe_set_compression_key(fhe_ctx* c, const fhe_compression_key* key) {
     if (rc) return rc;
     const CompParams& cp = key->cp;
     c->cp = cp;
-    uint64_t* d_std = nullptr;
-    const size_t std_words = std::max(key->pksk.size(), key->bsk.size());
-    FHE_HIP_CHECK(hipMalloc(&d_std, std_words * 8));
-    std::unique_ptr<void, DeviceFree> std_guard(d_std);
+    DeviceBuf<uint64_t> d_std;  // freed on return, behind body's wait
+    FHE_HIP_CHECK(d_std.grow(std::max(key->pksk.size(), key->bsk.size())));
     auto body = [&]() -> int {
-        FHE_HIP_CHECK(hipMalloc(&c->d_pk_planes, fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
+        FHE_HIP_CHECK(c->d_pk_planes.grow(fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
         FHE_HIP_CHECK(hipMemcpyAsync(d_std, key->pksk.data(), key->pksk.size() * 8, hipMemcpyHostToDevice, c->stream));
         FHE_HIP_CHECK(launch_pksk_to_planes(d_std, (int)cp.ell, (int)cp.cols(), c->d_pk_planes, c->stream));
         const int npoly = (int)(cp.lwe_dim() * 4);
-        FHE_HIP_CHECK(hipMalloc(&c->d_cbsk, (size_t)npoly * 1024 * sizeof(double2)));
-        FHE_HIP_CHECK(hipMalloc(&c->d_cbsk_e, (size_t)npoly * 1024 * sizeof(double2)));
+        FHE_HIP_CHECK(c->d_cbsk.grow((size_t)npoly * 1024));
+        FHE_HIP_CHECK(c->d_cbsk_e.grow((size_t)npoly * 1024));
         FHE_HIP_CHECK(hipMemcpyAsync(d_std, key->bsk.data(), key->bsk.size() * 8, hipMemcpyHostToDevice, c->stream));
         FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, npoly, c->d_W, c->d_psi, c->d_cbsk, c->stream));
         FHE_HIP_CHECK(launch_bsk_to_e(c->d_cbsk, npoly, c->d_cbsk_e, c->stream));
@@ -808,20 +769,18 @@ int fhe_set_compression_key_seeded(fhe_ctx* c, const fhe_seeded_compression_key*
     if (rc) return rc;
     c->cp = cp;
     const KeyWords key = bytes_key(sck->seed);
-    uint64_t *d_pb = nullptr, *d_bb = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&d_pb, sck->pksk_bodies.size() * 8));
-    std::unique_ptr<void, DeviceFree> pb_guard(d_pb);  // both freed behind the wait below
-    FHE_HIP_CHECK(hipMalloc(&d_bb, sck->bsk_bodies.size() * 8));
-    std::unique_ptr<void, DeviceFree> bb_guard(d_bb);
+    DeviceBuf<uint64_t> d_pb, d_bb;  // both freed on return, behind body's wait
+    FHE_HIP_CHECK(d_pb.grow(sck->pksk_bodies.size()));
+    FHE_HIP_CHECK(d_bb.grow(sck->bsk_bodies.size()));
     auto body = [&]() -> int {
-        FHE_HIP_CHECK(hipMalloc(&c->d_pk_planes, fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
+        FHE_HIP_CHECK(c->d_pk_planes.grow(fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
         FHE_HIP_CHECK(hipMemcpyAsync(d_pb, sck->pksk_bodies.data(), sck->pksk_bodies.size() * 8, hipMemcpyHostToDevice,
                                      c->stream));
         FHE_HIP_CHECK(launch_expand_pksk_planes(chacha_stream_key(key.data(), kStreamSeededPksk), d_pb, (int)cp.ell,
                                                 (int)cp.k, (int)cp.N, c->d_pk_planes, c->stream));
         const int npoly = (int)(cp.lwe_dim() * 4);
-        FHE_HIP_CHECK(hipMalloc(&c->d_cbsk, (size_t)npoly * 1024 * sizeof(double2)));
-        FHE_HIP_CHECK(hipMalloc(&c->d_cbsk_e, (size_t)npoly * 1024 * sizeof(double2)));
+        FHE_HIP_CHECK(c->d_cbsk.grow((size_t)npoly * 1024));
+        FHE_HIP_CHECK(c->d_cbsk_e.grow((size_t)npoly * 1024));
         FHE_HIP_CHECK(hipMemcpyAsync(d_bb, sck->bsk_bodies.data(), sck->bsk_bodies.size() * 8, hipMemcpyHostToDevice,
                                      c->stream));
         FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededCbsk), d_bb, npoly, c->d_W,
@@ -867,16 +826,19 @@ int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
     const bool had_key = c->has_key;
     int rc = release_key(c);
     if (rc) return rc;
-    FHE_HIP_CHECK(hipMalloc(&c->d_ksk, sk->ksk.size() * 8));
-    FHE_HIP_CHECK(hipMemcpyAsync(c->d_ksk, sk->ksk.data(), sk->ksk.size() * 8, hipMemcpyHostToDevice, c->stream));
-    const int npoly = (int)(p.ggsw_count() * 4);
-    uint64_t* d_std = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&d_std, sk->bsk.size() * 8));
-    std::unique_ptr<void, DeviceFree> std_guard(d_std);  // freed behind install_tail's wait
-    FHE_HIP_CHECK(hipMalloc(&c->d_bsk, (size_t)npoly * 1024 * sizeof(double2)));
-    FHE_HIP_CHECK(hipMemcpyAsync(d_std, sk->bsk.data(), sk->bsk.size() * 8, hipMemcpyHostToDevice, c->stream));
-    FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, npoly, c->d_W, c->d_psi, c->d_bsk, c->stream));
-    return install_tail(c, p, had_key);
+    DeviceBuf<uint64_t> d_std;  // freed on return: behind install_tail's wait, or drop_key's
+    auto body = [&]() -> int {
+        FHE_HIP_CHECK(c->d_ksk.grow(sk->ksk.size()));
+        FHE_HIP_CHECK(hipMemcpyAsync(c->d_ksk, sk->ksk.data(), sk->ksk.size() * 8, hipMemcpyHostToDevice, c->stream));
+        const int npoly = (int)(p.ggsw_count() * 4);
+        FHE_HIP_CHECK(d_std.grow(sk->bsk.size()));
+        FHE_HIP_CHECK(c->d_bsk.grow((size_t)npoly * 1024));
+        FHE_HIP_CHECK(hipMemcpyAsync(d_std, sk->bsk.data(), sk->bsk.size() * 8, hipMemcpyHostToDevice, c->stream));
+        FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, npoly, c->d_W, c->d_psi, c->d_bsk, c->stream));
+        return install_tail(c, p, had_key);
+    };
+    rc = body();
+    return rc ? drop_key(c, rc) : FHE_OK;
 }
 
 // The seeded install: the bodies are the only upload (82 KB + half of the standard-domain BSK, which is
@@ -899,22 +861,24 @@ int fhe_set_server_key_seeded(fhe_ctx* c, const fhe_seeded_server_key* ssk) {
     if (rc) return rc;
     const KeyWords key = bytes_key(ssk->seed);
     const int rows = (int)(kPolySize * p.ks_level), npoly = (int)(p.ggsw_count() * 4);
-    uint64_t *d_kb = nullptr, *d_bb = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&d_kb, ssk->ksk_bodies.size() * 8));
-    std::unique_ptr<void, DeviceFree> kb_guard(d_kb);  // both freed behind install_tail's wait
-    FHE_HIP_CHECK(hipMalloc(&d_bb, ssk->bsk_bodies.size() * 8));
-    std::unique_ptr<void, DeviceFree> bb_guard(d_bb);
-    FHE_HIP_CHECK(hipMalloc(&c->d_ksk, (size_t)rows * (p.n + 1) * 8));
-    FHE_HIP_CHECK(hipMalloc(&c->d_bsk, (size_t)npoly * 1024 * sizeof(double2)));
-    FHE_HIP_CHECK(hipMemcpyAsync(d_kb, ssk->ksk_bodies.data(), ssk->ksk_bodies.size() * 8, hipMemcpyHostToDevice,
-                                 c->stream));
-    FHE_HIP_CHECK(launch_expand_ksk(chacha_stream_key(key.data(), kStreamSeededKsk), c->d_ksk, d_kb, rows, (int)p.n,
-                                    c->stream));
-    FHE_HIP_CHECK(hipMemcpyAsync(d_bb, ssk->bsk_bodies.data(), ssk->bsk_bodies.size() * 8, hipMemcpyHostToDevice,
-                                 c->stream));
-    FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededBsk), d_bb, npoly, c->d_W,
-                                            c->d_psi, c->d_bsk, c->stream));
-    return install_tail(c, p, had_key);
+    DeviceBuf<uint64_t> d_kb, d_bb;  // both freed on return: behind install_tail's wait, or drop_key's
+    auto body = [&]() -> int {
+        FHE_HIP_CHECK(d_kb.grow(ssk->ksk_bodies.size()));
+        FHE_HIP_CHECK(d_bb.grow(ssk->bsk_bodies.size()));
+        FHE_HIP_CHECK(c->d_ksk.grow((size_t)rows * (p.n + 1)));
+        FHE_HIP_CHECK(c->d_bsk.grow((size_t)npoly * 1024));
+        FHE_HIP_CHECK(hipMemcpyAsync(d_kb, ssk->ksk_bodies.data(), ssk->ksk_bodies.size() * 8, hipMemcpyHostToDevice,
+                                     c->stream));
+        FHE_HIP_CHECK(launch_expand_ksk(chacha_stream_key(key.data(), kStreamSeededKsk), c->d_ksk, d_kb, rows,
+                                        (int)p.n, c->stream));
+        FHE_HIP_CHECK(hipMemcpyAsync(d_bb, ssk->bsk_bodies.data(), ssk->bsk_bodies.size() * 8, hipMemcpyHostToDevice,
+                                     c->stream));
+        FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededBsk), d_bb, npoly, c->d_W,
+                                                c->d_psi, c->d_bsk, c->stream));
+        return install_tail(c, p, had_key);
+    };
+    rc = body();
+    return rc ? drop_key(c, rc) : FHE_OK;
 }
 
 int fhe_ctx_export_fourier_bsk(fhe_ctx* c, double* out, size_t len) {
@@ -1087,9 +1051,8 @@ int fhe_pbs_lincomb_batch(fhe_ctx* c, const uint64_t* blocks, size_t nblocks, co
     if (rc) return rc;
     // descriptors, then the wide items' term tables in PbsDesc-sized units (as Engine::flush stages them)
     const size_t ndesc = count + (next * sizeof(TermExt) + sizeof(PbsDesc) - 1) / sizeof(PbsDesc);
-    PbsDesc* dev = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&dev, ndesc * sizeof(PbsDesc)));
-    std::unique_ptr<void, DeviceFree> dev_guard(dev);
+    DeviceBuf<PbsDesc> dev;
+    FHE_HIP_CHECK(dev.grow(ndesc));
     std::vector<PbsDesc> h(ndesc);
     std::memset(h.data(), 0, ndesc * sizeof(PbsDesc));
     TermExt* h_ext = reinterpret_cast<TermExt*>(h.data() + count);
@@ -1129,9 +1092,9 @@ int fhe_pbs_lincomb_batch(fhe_ctx* c, const uint64_t* blocks, size_t nblocks, co
 void* fhe_device_alloc(fhe_ctx* c, size_t bytes) {
     if (!c) return nullptr;
     if (hipSetDevice(c->device) != hipSuccess) return nullptr;
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
-        set_error("hipMalloc failed");
+    void* p = nullptr;  // the caller's to free (fhe_device_free)
+    if (HipDeviceAlloc::alloc(&p, bytes ? bytes : 1) != hipSuccess) {
+        set_error("device allocation failed");
         return nullptr;
     }
     return p;
@@ -1141,7 +1104,7 @@ int fhe_device_free(fhe_ctx* c, void* p) {
     if (!c) return FHE_ERR_INVALID;
     FHE_HIP_CHECK(hipSetDevice(c->device));
     FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
-    FHE_HIP_CHECK(hipFree(p));
+    FHE_HIP_CHECK(HipDeviceAlloc::free(p));
     return FHE_OK;
 }
 
@@ -1197,7 +1160,7 @@ int fhe_ctx_enable_timing(fhe_ctx* c, int enable) {
 int fhe_ctx_enable_clock(fhe_ctx* c, int enable) {
     if (!c) return FHE_ERR_INVALID;
     FHE_HIP_CHECK(hipSetDevice(c->device));
-    if (enable && !c->d_clock) FHE_HIP_CHECK(hipMalloc(&c->d_clock, 4 * sizeof(unsigned long long)));
+    if (enable && !c->d_clock) FHE_HIP_CHECK(c->d_clock.grow(4));
     if (enable) FHE_HIP_CHECK(hipMemsetAsync(c->d_clock, 0, 4 * sizeof(unsigned long long), c->stream));
     c->clock_probe = enable != 0;
     return FHE_OK;

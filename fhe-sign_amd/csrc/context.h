@@ -1,5 +1,7 @@
 // context.h -- per-thread device context: GPU stream, installed server key, LUT registry,
-// PBS workspace.  The analogue of tfhe-rs's thread-local server key (src/schnorr.rs:443).
+// PBS workspace.  The analogue of tfhe-rs's thread-local server key (src/schnorr.rs:443).  Every device
+// buffer is a DeviceBuf (device_buf.h): the context's destructor and the release_* functions wait, then the
+// members free themselves.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +10,7 @@
 #include <vector>
 
 #include "compress.h"
+#include "device_buf.h"
 #include "keys.h"
 #include "kernels.h"
 
@@ -42,23 +45,31 @@ void mono_table(const std::vector<double2>& psi, std::vector<double2>* E);
 }  // namespace fhe
 
 struct fhe_ctx {
+    fhe_ctx() = default;
+    fhe_ctx(const fhe_ctx&) = delete;
+    fhe_ctx& operator=(const fhe_ctx&) = delete;
+    // waits for the stream, deletes the engine, releases the communicator, destroys events and the stream;
+    // the buffers below then free themselves
+    ~fhe_ctx();
     int device = 0;
     hipStream_t stream = nullptr;
     bool has_key = false;
     fhe::Params p;
-    uint64_t* d_ksk = nullptr;
-    double2* d_bsk = nullptr;  // Fourier BSK, blind-rotate layout
-    double2* d_W = nullptr;    // per-lane twiddle table [30][64]
-    double2* d_psi = nullptr;
-    double2* d_tw_wide = nullptr;   // [12][256]
-    double2* d_psi_wide = nullptr;  // [4][256]
-    double2* d_bsk_e = nullptr;     // Fourier BSK in the throughput kernel's E layout (br_qy.hip)
-    double2* d_zeta_full = nullptr; // zeta(s, b) at [2^s + b], 1024 entries (br_qy.hip)
-    double2* d_tw_quad = nullptr;   // W[0..512)
-    double2* d_psi_quad = nullptr;  // [2][8][128]: twist (unused since the twisted forward), untwist
-    double2* d_zeta_wide = nullptr; // [10][256] (context.cpp:wide_zetas)
-    double2* d_mono = nullptr;      // monomial table E[4096] of the multi-bit blind rotation (mono_table)
-    int8_t* d_ksk_planes = nullptr; // KSK as balanced signed-byte planes (ks_mfma.hip)
+    fhe::DeviceBuf<uint64_t> d_ksk;
+    fhe::DeviceBuf<double2> d_bsk;  // Fourier BSK, blind-rotate layout
+    fhe::DeviceBuf<double2> d_W;    // per-lane twiddle table [30][64]
+    fhe::DeviceBuf<double2> d_psi;
+    fhe::DeviceBuf<double2> d_tw_wide;   // [12][256]
+    fhe::DeviceBuf<double2> d_psi_wide;  // [4][256]
+    fhe::DeviceBuf<double2> d_bsk_e;     // Fourier BSK in the throughput kernel's E layout (br_qy.hip)
+    fhe::DeviceBuf<double2> d_zeta_full; // zeta(s, b) at [2^s + b], 1024 entries (br_qy.hip)
+    fhe::DeviceBuf<double2> d_tw_quad;   // W[0..512)
+    // [2][8][128] (quad_tables): the twist psi[128 r + t], which no kernel has read since the twisted
+    // forward, then at [1024] the untwist conj(psi) 2^-51 that br_qy.hip's kernels multiply by
+    fhe::DeviceBuf<double2> d_psi_quad;
+    fhe::DeviceBuf<double2> d_zeta_wide; // [10][256] (context.cpp:wide_zetas)
+    fhe::DeviceBuf<double2> d_mono;      // monomial table E[4096] of the multi-bit blind rotation (mono_table)
+    fhe::DeviceBuf<int8_t> d_ksk_planes; // KSK as balanced signed-byte planes (ks_mfma.hip)
     int ks_kernel = FHE_KS_MFMA;
     // fhe_ctx_set_modulus_switch: FHE_MS_CENTERED makes keyswitch() follow its kernel with k_ms_center on
     // d_ms (ms_center.hip), so every level launched from then on hands the blind rotation centered rows
@@ -74,9 +85,9 @@ struct fhe_ctx {
     static bool qy2_fills(size_t count) {
         return count >= (size_t)kQy2Min || (count > 960 && (count % 1024 == 0 || count % 1024 > 768));
     }
-    int8_t* d_ks_digits = nullptr;  // keyswitch digits workspace
-    uint64_t* d_ks_body = nullptr;
-    size_t ks_cap = 0;              // ciphertexts
+    fhe::DeviceBuf<int8_t> d_ks_digits;  // keyswitch digits workspace
+    fhe::DeviceBuf<uint64_t> d_ks_body;
+    size_t ks_cap = 0;              // ciphertexts; 0 while either of the two is not grown
     // levels with at most this many bootstraps use the latency kernel (one ciphertext per CU at a
     // time -- >128 KB LDS -- so one round over the 256 CUs); the throughput kernel above, which holds
     // 2-3 per CU (profiles/r2/latency_sweep_r2b.txt: from 320 on it is as fast or faster)
@@ -84,23 +95,22 @@ struct fhe_ctx {
     // LUT registry: table contents -> id, device array of accumulator polynomials
     std::map<std::vector<uint32_t>, uint32_t> lut_ids;
     std::vector<uint64_t> h_luts;
-    uint64_t* d_luts = nullptr;
-    size_t d_luts_cap = 0;  // in LUTs
+    fhe::DeviceBuf<uint64_t> d_luts;  // capacity() / kPolySize tables
     bool luts_dirty = false;
     // PBS workspace
-    uint64_t* d_ms = nullptr;  // keyswitched small LWE (u64, stride ms_stride >= n+1)
+    fhe::DeviceBuf<uint64_t> d_ms;  // keyswitched small LWE (u64, stride ms_stride >= n+1)
     size_t ms_cap = 0;  // ciphertexts
     int ms_stride = 0;
-    uint64_t* d_stage_in = nullptr;
-    uint64_t* d_stage_out = nullptr;
-    uint32_t* d_stage_lut = nullptr;
-    size_t stage_cap = 0;
+    fhe::DeviceBuf<uint64_t> d_stage_in;
+    fhe::DeviceBuf<uint64_t> d_stage_out;
+    fhe::DeviceBuf<uint32_t> d_stage_lut;
+    size_t stage_cap = 0;  // ciphertexts; 0 while any of the three is not grown
     // timing
     bool timing = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     float last_ks_ms = 0.f, last_br_ms = 0.f;
     // clock probe of the throughput blind rotate (fhe_ctx_enable_clock / fhe_ctx_read_clock)
-    unsigned long long* d_clock = nullptr;  // {sum of workgroup shader cycles, of 100 MHz ticks, workgroups}
+    fhe::DeviceBuf<unsigned long long> d_clock;  // {sum of workgroup shader cycles, of 100 MHz ticks, workgroups}
     bool clock_probe = false;
     // radix-layer executor (created with the server key)
     fhe::Engine* engine = nullptr;
@@ -113,8 +123,7 @@ struct fhe_ctx {
     uint32_t comm_timeout_ms = FHE_COMM_DEFAULT_TIMEOUT_MS;  // deadline of every collective's enqueue
     int fanout_emulate = 0;     // test hook: split levels over this many virtual ranks on one GPU
     size_t fanout_min = 257;  // above one ciphertext per CU (256 CUs) a level costs 2x the floor
-    uint64_t* d_gather = nullptr;        // [nranks * chunk][2049]
-    size_t gather_cap = 0;               // ciphertexts
+    fhe::DeviceBuf<uint64_t> d_gather;   // [nranks * chunk][2049]
     // test hook (fhe_ctx_attach_test_transport): the collectives through host buffers and callbacks
     fhe_test_transport tx{};
     bool has_tx = false;
@@ -148,8 +157,7 @@ struct fhe_ctx {
     // *flags (one byte per entry) = min over the ranks, in place (one all-reduce; a no-op without a
     // communicator).  The engine's dead-node agreement.
     int allreduce_min_u8(uint8_t* flags, size_t n);
-    uint8_t* d_flags = nullptr;  // device staging of allreduce_min_u8 (grown, freed with the context)
-    size_t flags_cap = 0;
+    fhe::DeviceBuf<uint8_t> d_flags;  // device staging of allreduce_min_u8 (grown, freed with the context)
 
     int ensure_ms(size_t count);
     // Commit point of every key install (fhe_set_server_key, the receivers of
@@ -190,21 +198,21 @@ struct fhe_ctx {
     // byte planes (compress.hip), the decompression BSK in the two Fourier layouts, and the workspaces.
     bool has_comp = false;
     fhe::CompParams cp;
-    int8_t* d_pk_planes = nullptr;
-    double2* d_cbsk = nullptr;    // latency layout
-    double2* d_cbsk_e = nullptr;  // throughput (E) layout
+    fhe::DeviceBuf<int8_t> d_pk_planes;
+    fhe::DeviceBuf<double2> d_cbsk;    // latency layout
+    fhe::DeviceBuf<double2> d_cbsk_e;  // throughput (E) layout
     // compression workspace, `pk_cap` blocks: slot pointers, digits, bodies, contraction output, packed stream
-    const uint64_t** d_pk_src = nullptr;
-    int8_t* d_pk_digits = nullptr;
-    uint64_t* d_pk_body = nullptr;
-    uint64_t* d_pk_P = nullptr;
-    uint8_t* d_pk_out = nullptr;
+    fhe::DeviceBuf<const uint64_t*> d_pk_src;
+    fhe::DeviceBuf<int8_t> d_pk_digits;
+    fhe::DeviceBuf<uint64_t> d_pk_body;
+    fhe::DeviceBuf<uint64_t> d_pk_P;
+    fhe::DeviceBuf<uint8_t> d_pk_out;
     size_t pk_cap = 0;
     // decompression workspace, `cms_cap` blocks: sample-extracted rows (stride cms_stride >= k' N' + 1),
     // the uploaded 12-bit stream, one descriptor (LUT, destination slot) per block
-    uint64_t* d_cms = nullptr;
-    uint8_t* d_cpacked = nullptr;
-    fhe::PbsDesc* d_cdesc = nullptr;
+    fhe::DeviceBuf<uint64_t> d_cms;
+    fhe::DeviceBuf<uint8_t> d_cpacked;
+    fhe::DeviceBuf<fhe::PbsDesc> d_cdesc;
     size_t cms_cap = 0;
     int cms_stride = 0;
     int ensure_pk(size_t count);
@@ -212,11 +220,10 @@ struct fhe_ctx {
     int release_compression();  // waits for the stream, frees all of the above
 
     // Public key of the re-randomization (fhe_set_public_key; dropped by every server-key install): A then B,
-    // 2048 words each, and the zero encryptions' scratch, `rr_cap` chunks of Z_A then Z_B (rerandomize.hip).
+    // 2048 words each, and the zero encryptions' scratch, chunks of Z_A then Z_B (rerandomize.hip).
     bool has_pk = false;
-    uint64_t* d_pk_ab = nullptr;
-    uint64_t* d_rr_z = nullptr;
-    size_t rr_cap = 0;
+    fhe::DeviceBuf<uint64_t> d_pk_ab;
+    fhe::DeviceBuf<uint64_t> d_rr_z;
     int ensure_rr(size_t chunks);
     int release_public_key();  // waits for the stream, frees all of the above
 };

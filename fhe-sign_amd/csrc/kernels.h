@@ -1,4 +1,5 @@
 // kernels.h -- host launchers for the gfx950 kernels (pbs_kernels.hip, ks_mfma.hip, ms_center.hip, br_wide.hip, br_qy.hip).
+// The launchers take plain pointers; the memory behind them is owned through device_buf.h (context.h, radix.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,8 +1,6 @@
 // ms_center.cpp -- host side of the centered modulus switch: the exact-integer definition of
 // ms_center.hip's kernel, its C entry point (no context, no GPU), the per-context mode, and the test and
 // measurement entries that run the kernel over host rows.  fhe_ctx::keyswitch (context.cpp) is the device path.
-#include <memory>
-
 #include "context.h"
 #include "fhe_rocm.h"
 
@@ -31,11 +29,6 @@ int invalid(const std::string& why) {
     set_error(why);
     return FHE_ERR_INVALID;
 }
-struct DeviceFree {
-    void operator()(void* p) const {
-        if (p) (void)hipFree(p);
-    }
-};
 // 1 <= n <= 2048 keeps the sum inside int64; a row holds its n mask words and the body
 int check_shape(const char* who, uint32_t n, size_t stride) {
     if (n < 1 || n > FHE_MS_CENTER_MAX_N) return invalid(std::string(who) + ": n must be 1 .. 2048");
@@ -74,9 +67,8 @@ int fhe_ms_center_rows(fhe_ctx* c, uint64_t* rows, size_t count, uint32_t n, siz
     if (count == 0) return FHE_OK;
     FHE_HIP_CHECK(hipSetDevice(c->device));
     const size_t bytes = count * stride * 8;
-    uint64_t* dev = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&dev, bytes));
-    std::unique_ptr<void, DeviceFree> guard(dev);
+    DeviceBuf<uint64_t> dev;
+    FHE_HIP_CHECK(dev.grow(count * stride));
     FHE_HIP_CHECK(hipMemcpyAsync(dev, rows, bytes, hipMemcpyHostToDevice, c->stream));
     FHE_HIP_CHECK(launch_ms_center(dev, count, n, stride, c->stream));
     FHE_HIP_CHECK(hipMemcpyAsync(rows, dev, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -89,9 +81,8 @@ int fhe_ctx_time_ms_center(fhe_ctx* c, size_t count, uint32_t n, size_t stride, 
     if (const int rc = check_shape("fhe_ctx_time_ms_center", n, stride)) return rc;
     if (count > (size_t)0x7fffffff) return invalid("fhe_ctx_time_ms_center: batch too large");
     FHE_HIP_CHECK(hipSetDevice(c->device));
-    uint64_t* dev = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&dev, count * stride * 8));
-    std::unique_ptr<void, DeviceFree> guard(dev);
+    DeviceBuf<uint64_t> dev;
+    FHE_HIP_CHECK(dev.grow(count * stride));
     hipEvent_t ev[2] = {nullptr, nullptr};
     auto body = [&]() -> int {
         FHE_HIP_CHECK(hipMemsetAsync(dev, 0x5A, count * stride * 8, c->stream));

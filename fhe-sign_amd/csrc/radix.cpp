@@ -72,8 +72,7 @@ Slot::~Slot() {
 
 BlockPool::~BlockPool() {
     if (dry_ || chunks_.empty()) return;  // a host-only engine never touches the HIP runtime
-    (void)hipSetDevice(device_);
-    for (void* c : chunks_) (void)hipFree(c);
+    (void)hipSetDevice(device_);            // the chunks free themselves
 }
 
 // pool growth (FHE_TRACE_LEVELS prints it with the host time of run())
@@ -89,13 +88,14 @@ std::shared_ptr<Slot> BlockPool::alloc() {
     }
     if (free_.empty()) {
         const size_t per = 1024;  // 16 MiB chunks
-        void* c = nullptr;
+        DeviceBuf<uint64_t> chunk;
         const auto t0 = std::chrono::steady_clock::now();
-        hip_check(hipMalloc(&c, per * kBigCt * 8), "block pool hipMalloc");
+        hip_check(chunk.grow(per * kBigCt), "block pool allocation");
         g_pool_grow_ns += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count();
         ++g_pool_grows;
-        chunks_.push_back(c);
-        for (size_t i = 0; i < per; ++i) free_.push_back((uint64_t*)c + (per - 1 - i) * kBigCt);
+        uint64_t* const c = chunk;
+        chunks_.push_back(std::move(chunk));
+        for (size_t i = 0; i < per; ++i) free_.push_back(c + (per - 1 - i) * kBigCt);
         total_ += per;
     }
     auto s = std::make_shared<Slot>();
@@ -159,31 +159,32 @@ Engine::~Engine() {
     if (host_mode_ != kDevice) return;
     (void)hipSetDevice(ctx_->device);
     (void)hipStreamSynchronize(ctx_->stream);
-    for (auto* h : h_desc_)
-        if (h) (void)hipHostFree(h);
     for (auto ev : desc_ev_)
         if (ev) (void)hipEventDestroy(ev);
-    if (d_desc_) (void)hipFree(d_desc_);
-    if (d_up_) (void)hipFree(d_up_);
+}
+
+// The upload / download staging, at least `words` u64: grown to exactly that, behind the stream, when short.
+uint64_t* Engine::staging(size_t words) {
+    if (!d_up_.fits(words)) {
+        hip_check(hipStreamSynchronize(ctx_->stream), "staging sync");
+        hip_check(d_up_.grow(words), "staging allocation");
+    }
+    return d_up_;
 }
 
 void Engine::ensure_desc(size_t n) {
     if (n > desc_cap_) {
-        size_t cap = std::max<size_t>(n, 4096);
+        const size_t cap = std::max<size_t>(n, 4096);
+        desc_cap_ = 0;
         for (int i = 0; i < 2; ++i) {
-            if (h_desc_[i]) {
-                hip_check(hipEventSynchronize(desc_ev_[i]), "desc event");
-                hip_check(hipHostFree(h_desc_[i]), "hipHostFree");
-            }
-            hip_check(hipHostMalloc((void**)&h_desc_[i], cap * sizeof(PbsDesc)), "hipHostMalloc");
+            if (h_desc_[i]) hip_check(hipEventSynchronize(desc_ev_[i]), "desc event");
+            hip_check(h_desc_[i].grow(cap), "pinned descriptors");
         }
         desc_cap_ = cap;
     }
-    if (n > d_desc_cap_) {
+    if (!d_desc_.fits(n)) {
         hip_check(hipStreamSynchronize(ctx_->stream), "sync");
-        if (d_desc_) hip_check(hipFree(d_desc_), "hipFree");
-        d_desc_cap_ = std::max<size_t>(n, 4096);
-        hip_check(hipMalloc(&d_desc_, d_desc_cap_ * sizeof(PbsDesc)), "hipMalloc desc");
+        hip_check(d_desc_.grow(std::max<size_t>(n, 4096)), "device descriptors");
     }
 }
 
@@ -985,12 +986,7 @@ Blocks Engine::upload_many(const uint64_t* cts, size_t n, uint32_t degree) {
     Blocks out(n);
     if (n == 0) return out;
     const size_t words = n * kBigCt + n;  // ciphertexts, then the slot pointers
-    if (words > up_cap_) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
-        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
-        hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc upload");
-        up_cap_ = words;
-    }
+    uint64_t* const d_up = staging(words);
     std::vector<uint64_t*> dst(n);
     for (size_t i = 0; i < n; ++i) {
         out[i].slot = pool_->alloc();
@@ -998,10 +994,10 @@ Blocks Engine::upload_many(const uint64_t* cts, size_t n, uint32_t degree) {
         out[i].noise = 1;
         dst[i] = out[i].slot->p;
     }
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up_ + n * kBigCt);
-    hip_check(hipMemcpyAsync(d_up_, cts, n * kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "upload");
+    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up + n * kBigCt);
+    hip_check(hipMemcpyAsync(d_up, cts, n * kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "upload");
     hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "upload");
-    hip_check(launch_scatter_blocks(d_up_, d_dst, (int)n, ctx_->stream), "upload scatter");
+    hip_check(launch_scatter_blocks(d_up, d_dst, (int)n, ctx_->stream), "upload scatter");
     hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go
     return out;
 }
@@ -1012,12 +1008,7 @@ Blocks Engine::expand_seeded(const uint8_t seed[32], const uint64_t* bodies, siz
     Blocks out(n);
     if (n == 0) return out;
     const size_t words = 2 * n;  // the bodies, then the slot pointers
-    if (words > up_cap_) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
-        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
-        hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc upload");
-        up_cap_ = words;
-    }
+    uint64_t* const d_up = staging(words);
     std::vector<uint64_t*> dst(n);
     for (size_t i = 0; i < n; ++i) {
         out[i].slot = pool_->alloc();
@@ -1025,12 +1016,12 @@ Blocks Engine::expand_seeded(const uint8_t seed[32], const uint64_t* bodies, siz
         out[i].noise = 1;
         dst[i] = out[i].slot->p;
     }
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up_ + n);
-    hip_check(hipMemcpyAsync(d_up_, bodies, n * 8, hipMemcpyHostToDevice, ctx_->stream), "seeded bodies");
+    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up + n);
+    hip_check(hipMemcpyAsync(d_up, bodies, n * 8, hipMemcpyHostToDevice, ctx_->stream), "seeded bodies");
     hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
               "seeded slots");
     const KeyWords key = bytes_key(seed);
-    hip_check(launch_expand_seeded(chacha_stream_key(key.data(), kStreamSeededMask), d_dst, d_up_, (int)n, ctx_->stream),
+    hip_check(launch_expand_seeded(chacha_stream_key(key.data(), kStreamSeededMask), d_dst, d_up, (int)n, ctx_->stream),
               "seeded expansion");
     hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
     return out;
@@ -1146,14 +1137,7 @@ Blocks Engine::compact_extract(const fhe_compact_list& x, size_t first, size_t n
     const size_t c0 = first / kPolySize, c1 = (first + n - 1) / kPolySize + 1;  // the chunks the range touches
     const size_t ca_words = (c1 - c0) * kPolySize;
     const size_t words = ca_words + 2 * n;  // C_A of the chunks, the bodies, then the slot pointers
-    if (words > up_cap_) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
-        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
-        d_up_ = nullptr;
-        up_cap_ = 0;
-        hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc upload");
-        up_cap_ = words;
-    }
+    uint64_t* const d_up = staging(words);
     std::vector<uint64_t*> dst(n);
     for (size_t i = 0; i < n; ++i) {
         out[i].slot = pool_->alloc();
@@ -1161,14 +1145,14 @@ Blocks Engine::compact_extract(const fhe_compact_list& x, size_t first, size_t n
         out[i].noise = 1;
         dst[i] = out[i].slot->p;
     }
-    uint64_t* d_cb = d_up_ + ca_words;
+    uint64_t* d_cb = d_up + ca_words;
     uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_cb + n);
-    hip_check(hipMemcpyAsync(d_up_, x.ca.data() + c0 * kPolySize, ca_words * 8, hipMemcpyHostToDevice, ctx_->stream),
+    hip_check(hipMemcpyAsync(d_up, x.ca.data() + c0 * kPolySize, ca_words * 8, hipMemcpyHostToDevice, ctx_->stream),
               "compact masks");
     hip_check(hipMemcpyAsync(d_cb, x.cb.data() + first, n * 8, hipMemcpyHostToDevice, ctx_->stream), "compact bodies");
     hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
               "compact slots");
-    hip_check(launch_compact_extract(d_up_, d_cb, d_dst, (uint32_t)(first - c0 * kPolySize), (int)n, ctx_->stream),
+    hip_check(launch_compact_extract(d_up, d_cb, d_dst, (uint32_t)(first - c0 * kPolySize), (int)n, ctx_->stream),
               "compact extraction");
     hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
     return out;
@@ -1229,14 +1213,7 @@ Blocks Engine::rerandomize(const std::vector<const Block*>& blocks, const uint8_
     const size_t chunks = (n + kPolySize - 1) / kPolySize;
     engine_check(ctx_->ensure_rr(chunks) == FHE_OK, "re-randomization workspace");
     const size_t words = 3 * n;  // the source slots, the trivial bodies, then the fresh slots
-    if (words > up_cap_) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
-        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
-        d_up_ = nullptr;
-        up_cap_ = 0;
-        hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc upload");
-        up_cap_ = words;
-    }
+    uint64_t* const d_up = staging(words);
     std::vector<const uint64_t*> src(n);
     std::vector<uint64_t> tbody(n, 0);
     std::vector<uint64_t*> dst(n);
@@ -1253,9 +1230,9 @@ Blocks Engine::rerandomize(const std::vector<const Block*>& blocks, const uint8_
         out[i].noise = b.noise;
         dst[i] = out[i].slot->p;
     }
-    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up_);
-    uint64_t* d_tbody = d_up_ + n;
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up_ + 2 * n);
+    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up);
+    uint64_t* d_tbody = d_up + n;
+    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up + 2 * n);
     hip_check(hipMemcpyAsync(d_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "rerandomize slots");
     hip_check(hipMemcpyAsync(d_tbody, tbody.data(), n * 8, hipMemcpyHostToDevice, ctx_->stream), "rerandomize bodies");
     hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "rerandomize slots");
@@ -1289,17 +1266,12 @@ Blocks Engine::upload_deferred(size_t n, uint32_t degree, std::function<std::vec
         const std::vector<uint64_t> cts = fill();
         engine_check(cts.size() == n * kBigCt, "deferred upload: ciphertext count");
         const size_t words = n * kBigCt + n;
-        if (words > up_cap_) {
-            hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
-            if (d_up_) hip_check(hipFree(d_up_), "hipFree");
-            hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc upload");
-            up_cap_ = words;
-        }
-        uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up_ + n * kBigCt);
-        hip_check(hipMemcpyAsync(d_up_, cts.data(), n * kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "upload");
+        uint64_t* const d_up = staging(words);
+        uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up + n * kBigCt);
+        hip_check(hipMemcpyAsync(d_up, cts.data(), n * kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "upload");
         hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
                   "upload");
-        hip_check(launch_scatter_blocks(d_up_, d_dst, (int)n, ctx_->stream), "upload scatter");
+        hip_check(launch_scatter_blocks(d_up, d_dst, (int)n, ctx_->stream), "upload scatter");
         hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // cts and dst go out of scope
     };
     return out;
@@ -1322,21 +1294,16 @@ void Engine::download_many(const std::vector<const Block*>& blocks, uint64_t* ct
     else
         flush();
     const size_t words = n * kBigCt + n;  // gathered ciphertexts, then the slot pointers
-    if (words > up_cap_) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "download sync");
-        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
-        hip_check(hipMalloc(&d_up_, words * 8), "hipMalloc download");
-        up_cap_ = words;
-    }
+    uint64_t* const d_up = staging(words);
     std::vector<const uint64_t*> src(n);
     for (size_t i = 0; i < n; ++i) {
         engine_check(blocks[i]->slot != nullptr && !blocks[i]->lazy(), "download of a trivial or lazy block");
         src[i] = blocks[i]->slot->p;
     }
-    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up_ + n * kBigCt);
+    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up + n * kBigCt);
     hip_check(hipMemcpyAsync(d_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "download");
-    hip_check(launch_gather_blocks(d_src, d_up_, (int)n, ctx_->stream), "download gather");
-    hip_check(hipMemcpyAsync(cts, d_up_, n * kBigCt * 8, hipMemcpyDeviceToHost, ctx_->stream), "download");
+    hip_check(launch_gather_blocks(d_src, d_up, (int)n, ctx_->stream), "download gather");
+    hip_check(hipMemcpyAsync(cts, d_up, n * kBigCt * 8, hipMemcpyDeviceToHost, ctx_->stream), "download");
     wait_check(ctx_, "download");
 }
 
@@ -1348,18 +1315,13 @@ void Engine::sync() {
 Blocks Engine::adopt_device(const uint64_t* d_cts, size_t n) {
     Blocks out(n);
     if (n == 0) return out;
-    if (n > up_cap_) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
-        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
-        hip_check(hipMalloc(&d_up_, n * 8), "hipMalloc upload");
-        up_cap_ = n;
-    }
+    uint64_t* const d_up = staging(n);
     std::vector<uint64_t*> dst(n);
     for (size_t i = 0; i < n; ++i) {
         out[i].slot = pool_->alloc();
         dst[i] = out[i].slot->p;
     }
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up_);
+    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up);
     hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "adopt");
     hip_check(launch_scatter_blocks(d_cts, d_dst, (int)n, ctx_->stream), "adopt scatter");
     hip_check(hipStreamSynchronize(ctx_->stream), "adopt sync");  // the pointer staging may be reused
@@ -1370,18 +1332,13 @@ void Engine::gather_device(const std::vector<const Block*>& blocks, uint64_t* d_
     flush();
     const size_t n = blocks.size();
     if (n == 0) return;
-    if (n > up_cap_) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
-        if (d_up_) hip_check(hipFree(d_up_), "hipFree");
-        hip_check(hipMalloc(&d_up_, n * 8), "hipMalloc upload");
-        up_cap_ = n;
-    }
+    uint64_t* const d_up = staging(n);
     std::vector<const uint64_t*> src(n);
     for (size_t i = 0; i < n; ++i) {
         engine_check(blocks[i]->slot != nullptr && !blocks[i]->lazy(), "gather of a trivial or lazy block");
         src[i] = blocks[i]->slot->p;
     }
-    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up_);
+    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up);
     hip_check(hipMemcpyAsync(d_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "gather");
     hip_check(launch_gather_blocks(d_src, d_out, (int)n, ctx_->stream), "gather");
     hip_check(hipStreamSynchronize(ctx_->stream), "gather sync");

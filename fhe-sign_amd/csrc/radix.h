@@ -100,7 +100,7 @@ private:
     int device_;
     bool dry_;                // Engine kDry: slots are distinct placeholder addresses, never dereferenced
     uintptr_t dry_next_ = 0x10000;
-    std::vector<void*> chunks_;
+    std::vector<DeviceBuf<uint64_t>> chunks_;
     std::vector<uint64_t*> free_;
     size_t total_ = 0;
 };
@@ -267,8 +267,8 @@ private:
     int host_mode_ = kDevice;
     std::unordered_map<const uint64_t*, int64_t> sim_;  // kSim: slot -> plaintext (half steps)
     std::shared_ptr<BlockPool> pool_;
-    uint64_t* d_up_ = nullptr;  // upload staging: n big LWEs, then n destination pointers
-    size_t up_cap_ = 0;
+    DeviceBuf<uint64_t> d_up_;  // upload staging: n big LWEs, then n destination pointers
+    uint64_t* staging(size_t words);
     bool trace_ = false;
     // FHE_GRAPH_STATS=1: per flush, the critical-path width and the bootstraps that share their exact
     // input with another one at input degree <= 7 (two-output blind rotation candidates); stderr
@@ -293,12 +293,11 @@ private:
     std::vector<Pending> pending_;
     size_t pending_dependent_ = 0;  // pending nodes with at least one pending producer
     int32_t pending_depth_ = 0;     // the deepest pending node (levels of the graph recorded so far)
-    PbsDesc* h_desc_[2] = {nullptr, nullptr};  // pinned, double-buffered
+    PinnedBuf<PbsDesc> h_desc_[2];  // pinned, double-buffered
     hipEvent_t desc_ev_[2] = {nullptr, nullptr};
-    size_t desc_cap_ = 0;
+    size_t desc_cap_ = 0;  // of h_desc_; 0 while either is not grown
     int desc_turn_ = 0;
-    PbsDesc* d_desc_ = nullptr;
-    size_t d_desc_cap_ = 0;
+    DeviceBuf<PbsDesc> d_desc_;
     void ensure_desc(size_t n);
     void graph_stats(const std::vector<std::vector<int32_t>>& deps);
     void flush_tail(size_t k0);

@@ -61,22 +61,16 @@ void rerandomize_host(const fhe_public_key& pk, const uint8_t seed[32], uint64_t
 using namespace fhe;
 
 int fhe_ctx::ensure_rr(size_t chunks) {
-    if (chunks <= rr_cap) return FHE_OK;
+    if (d_rr_z.fits(chunks * 2 * kPolySize)) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(stream));  // an earlier call's kernels may still read it
-    if (d_rr_z) FHE_HIP_CHECK(hipFree(d_rr_z));
-    d_rr_z = nullptr;
-    rr_cap = 0;
-    FHE_HIP_CHECK(hipMalloc(&d_rr_z, chunks * 2 * kPolySize * 8));
-    rr_cap = chunks;
+    FHE_HIP_CHECK(d_rr_z.grow(chunks * 2 * kPolySize));
     return FHE_OK;
 }
 
 int fhe_ctx::release_public_key() {
     if (stream) FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    if (d_pk_ab) (void)hipFree(d_pk_ab);
-    if (d_rr_z) (void)hipFree(d_rr_z);
-    d_pk_ab = d_rr_z = nullptr;
-    rr_cap = 0;
+    (void)d_pk_ab.reset();
+    (void)d_rr_z.reset();
     has_pk = false;
     return FHE_OK;
 }
@@ -142,7 +136,7 @@ int fhe_set_public_key(fhe_ctx* c, const fhe_public_key* pk) {
         public_key_mask(pk->seed, ab.data());
         std::memcpy(ab.data() + kPolySize, pk->body.data(), kPolySize * 8);
         auto body = [&]() -> int {
-            FHE_HIP_CHECK(hipMalloc(&c->d_pk_ab, ab.size() * 8));
+            FHE_HIP_CHECK(c->d_pk_ab.grow(ab.size()));
             FHE_HIP_CHECK(hipMemcpyAsync(c->d_pk_ab, ab.data(), ab.size() * 8, hipMemcpyHostToDevice, c->stream));
             FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
             return FHE_OK;
