@@ -1585,6 +1585,23 @@ int fhe_compressed_extract_rows(fhe_ctx* c, const fhe_compressed_list* x, uint64
     });
 }
 
+int fhe_pack_keyswitch_words(fhe_ctx* c, const uint64_t* cts, size_t count, uint64_t* P, size_t p_words,
+                             uint64_t* body) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!c->has_comp) {
+        set_error("no compression key installed (fhe_set_compression_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    if (count > kCompressedMaxBlocks) return invalid("compressed list of more than 2^24 blocks");
+    if (count && (!cts || !P || !body)) return invalid("null argument to fhe_pack_keyswitch_words");
+    if (p_words < count * (size_t)c->cp.cols()) return invalid("fhe_pack_keyswitch_words: buffer too small");
+    return guarded([&] {
+        c->engine->pack_keyswitch_words(cts, count, P, body);
+        return FHE_OK;
+    });
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------- compact ciphertext lists

@@ -1078,6 +1078,29 @@ void Engine::compress(const std::vector<const Block*>& blocks, uint8_t* packed) 
     }
 }
 
+void Engine::pack_keyswitch_words(const uint64_t* cts, size_t n, uint64_t* P, uint64_t* body) {
+    engine_check(host_mode_ == kDevice, "compress on a host-only engine");
+    need_compression(ctx_);
+    engine_check(n <= kCompressedMaxBlocks, "compressed list of more than 2^24 blocks");
+    if (n == 0) return;
+    const CompParams& cp = ctx_->cp;
+    flush();
+    engine_check(ctx_->ensure_stage(n) == FHE_OK, "staging buffer");
+    engine_check(ctx_->ensure_pk(n) == FHE_OK, "compression workspace");
+    std::vector<const uint64_t*> src(n);
+    for (size_t i = 0; i < n; ++i) src[i] = ctx_->d_stage_in + i * kBigCt;
+    hip_check(hipMemcpyAsync(ctx_->d_stage_in, cts, n * kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "rows upload");
+    hip_check(hipMemcpyAsync(ctx_->d_pk_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
+              "compress slots");
+    hip_check(launch_pack_keyswitch(ctx_->d_pk_src, (int)n, (int)cp.beta, (int)cp.ell, (int)cp.k, (int)cp.N, (int)cp.L,
+                                    ctx_->d_pk_planes, ctx_->d_pk_digits, ctx_->d_pk_body, ctx_->d_pk_P, ctx_->d_pk_out,
+                                    ctx_->stream),
+              "packing keyswitch");
+    hip_check(hipMemcpyAsync(P, ctx_->d_pk_P, n * cp.cols() * 8, hipMemcpyDeviceToHost, ctx_->stream), "words download");
+    hip_check(hipMemcpyAsync(body, ctx_->d_pk_body, n * 8, hipMemcpyDeviceToHost, ctx_->stream), "bodies download");
+    wait_check(ctx_, "packing keyswitch words");
+}
+
 void Engine::extract_rows(const fhe_compressed_list& x, uint64_t* rows) {
     engine_check(host_mode_ == kDevice, "decompress on a host-only engine");
     need_compression(ctx_);

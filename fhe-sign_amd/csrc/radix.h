@@ -204,6 +204,9 @@ public:
     Blocks decompress(const fhe_compressed_list& x);
     // the unpack + sample-extract kernel alone: n x (k' N' + 1) words to the host (tests)
     void extract_rows(const fhe_compressed_list& x, uint64_t* rows);
+    // the packing keyswitch alone over n host rows of 2049 words, launched as compress launches it: the
+    // contraction's n x (k' + 1) N' words and the n bodies to the host (tests)
+    void pack_keyswitch_words(const uint64_t* cts, size_t n, uint64_t* P, uint64_t* body);
     // A compact ciphertext list's value (public_key.h) expanded on the device, modelled on expand_seeded: fresh
     // slots, the touched chunks' C_A (16 KB each), the bodies and the slot pointers staged through the upload
     // buffer, public_key.hip's sample extraction into the slots -- word for word expand_compact_host's rows.

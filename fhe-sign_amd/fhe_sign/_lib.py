@@ -254,6 +254,7 @@ _SIGNATURES = [
     ("fhe_compressed_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_compressed_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_compressed_extract_rows", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_pack_keyswitch_words", C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t, u64p]),
     ("fhe_compression_keys_generate_seeded", C.c_int,
      [C.c_void_p, C.POINTER(CompressionParams), C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("fhe_seeded_compression_key_params", C.c_int, [C.c_void_p, C.POINTER(FheParams), C.POINTER(CompressionParams)]),

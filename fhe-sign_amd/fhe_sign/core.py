@@ -480,6 +480,20 @@ class Context:
                                                    bsk_e.ctypes.data, bsk_e.size))
         return planes, bsk, bsk_e
 
+    def pack_keyswitch_words(self, cts: np.ndarray):
+        """test hook (fhe_pack_keyswitch_words): the packing keyswitch's contraction alone over (count, 2049) rows
+        of any words, launched as compress launches it.  Returns (P, body): the (count, (k' + 1) N') words
+        sum_{j, l} d[i, j, l] PKSK[j][l] mod 2^64 and the count body words set aside"""
+        check(load().fhe_pack_keyswitch_words(self._h, None, 0, None, 0, None))  # FHE_ERR_NO_KEY first
+        c = self._comp_params
+        if c is None:
+            raise RuntimeError("pack_keyswitch_words: the key was not installed through set_compression_key")
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, BIG_CT)
+        P = np.zeros((cts.shape[0], (c.glwe_dimension + 1) * c.polynomial_size), np.uint64)
+        body = np.zeros(cts.shape[0], np.uint64)
+        check(load().fhe_pack_keyswitch_words(self._h, ptr(cts), cts.shape[0], ptr(P), P.size, ptr(body)))
+        return P, body
+
     def export_fourier_bsk(self) -> np.ndarray:
         out = np.zeros(self.params.ggsw_count() * 4 * 1024 * 2, np.float64)
         check(load().fhe_ctx_export_fourier_bsk(self._h, ptr(out, C.c_double), out.size))

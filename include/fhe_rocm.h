@@ -713,6 +713,14 @@ int fhe_compressed_expand_biguint(fhe_ctx* ctx, const fhe_compressed_list* x, fh
 /* Test hook: the unpack + sample-extract kernel alone.  rows = nblocks x (k' N' + 1) words (each stored value
  * << 52), host pointer; synchronous. */
 int fhe_compressed_extract_rows(fhe_ctx* ctx, const fhe_compressed_list* x, uint64_t* rows, size_t nwords);
+/* Test hook: the packing keyswitch's contraction alone, launched as fhe_radix_compress launches it (the same
+ * choice of kernel by count).  cts = count rows of 2049 words, any words; P = count x (k' + 1) N' words, row i
+ * = sum_{j, l} d[i, j, l] PKSK[j][l] mod 2^64, before the rotation, the bodies and the rounding to 12 bits
+ * (p_words = the buffer's size in words); body = the count body words set aside.  Host pointers; flushes and
+ * waits like a download.  FHE_ERR_NO_KEY without a compression key; FHE_ERR_INVALID for a NULL pointer with
+ * count > 0, p_words too small, or more than 2^24 rows; count = 0 does nothing. */
+int fhe_pack_keyswitch_words(fhe_ctx* ctx, const uint64_t* cts, size_t count, uint64_t* P, size_t p_words,
+                             uint64_t* body);
 
 /* ------------------------------------------------- seeded (compressed) compression key */
 /* The compression key is the largest object left for a client to send: 150,994,944 payload bytes at the

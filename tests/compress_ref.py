@@ -178,6 +178,57 @@ def contract_u64(d, pksk):
         return np.dot(np.asarray(d, np.int64).astype(np.uint64), pksk)
 
 
+def key_matrix(cp, pksk):
+    """pksk flat [2048][ell][k' + 1][N'] as the matrix `contract` takes: row j ell + l, (k' + 1) N' columns"""
+    return np.asarray(pksk, np.uint64).reshape(N_BIG * cp.ell, cols(cp))
+
+
+def contraction_words(cp, pksk, cts):
+    """P[i] = sum_{j, l} d[i, j, l] PKSK[j][l] mod 2^64, (B, (k' + 1) N'): the packing keyswitch before the
+    sign, the bodies, the rotation and the rounding to 12 bits"""
+    cts = np.asarray(cts, np.uint64).reshape(-1, BIG_CT)
+    d = digits(cts[:, :N_BIG], cp.beta, cp.ell).reshape(cts.shape[0], N_BIG * cp.ell)
+    return contract(d, key_matrix(cp, pksk))
+
+
+# The device's byte planes, restated from the layout comment at the top of csrc/compress.hip: the key's rows in
+# LEVEL-MAJOR order k = level * 2048 + j, cut into KT = 32 ell k-tiles of 64; its columns into tiles of 16, the
+# last one padded with zero columns.  int8 [8 planes][column tiles][KT][64 lanes][16]: lane l of a fragment holds
+# column l & 15 of its tile and the 16 bytes k = 64 kt + 16 (l >> 4) + jj.  Plane b holds the balanced bytes
+# (tests/ks_ref.py byte_planes): word = sum_b plane_b 256^b mod 2^64 with plane_b in [-128, 128).
+def plane_layout(cp, pksk):
+    """the int8 array (8, column tiles, 32 ell, 64, 16) of the packing key pksk flat [2048][ell][k' + 1][N']"""
+    c, KT = cols(cp), 32 * cp.ell
+    tiles = (c + 15) // 16
+    v = np.zeros((cp.ell * N_BIG, 16 * tiles), np.uint64)
+    v[:, :c] = np.asarray(pksk, np.uint64).reshape(N_BIG, cp.ell, c).transpose(1, 0, 2).reshape(cp.ell * N_BIG, c)
+    out = np.empty((8, tiles, KT, 64, 16), np.int8)
+    for b in range(8):
+        s = (v & np.uint64(255)).astype(np.int64)
+        s[s >= 128] -= 256
+        with np.errstate(over="ignore"):
+            v = (v - s.astype(np.uint64)) >> np.uint64(8)
+        # rows k = (kt, l >> 4, jj), columns (tile, l & 15) -> (tile, kt, lane = 16 (l >> 4) + (l & 15), jj)
+        f = s.astype(np.int8).reshape(KT, 4, 16, tiles, 16).transpose(3, 0, 1, 4, 2)
+        out[b] = f.reshape(tiles, KT, 64, 16)
+    return out
+
+
+def words_of_planes(cp, planes):
+    """sum_b plane_b 256^b mod 2^64 read back out of the layout: (pksk flat [2048][ell][k' + 1][N'], the padding
+    columns' bytes)"""
+    c, KT = cols(cp), 32 * cp.ell
+    tiles = (c + 15) // 16
+    p = np.asarray(planes, np.int8).reshape(8, tiles, KT, 4, 16, 16)  # (b, tile, kt, l >> 4, l & 15, jj)
+    p = p.transpose(0, 2, 3, 5, 1, 4).reshape(8, cp.ell * N_BIG, 16 * tiles)
+    v = np.zeros(p.shape[1:], np.uint64)
+    with np.errstate(over="ignore"):
+        for b in range(8):
+            v += p[b].astype(np.int64).astype(np.uint64) << np.uint64(8 * b)
+    key = v[:, :c].reshape(cp.ell, N_BIG, c).transpose(1, 0, 2)
+    return np.ascontiguousarray(key).reshape(-1), p[:, :, c:]
+
+
 def pack_keyswitch(cp, pksk, cts):
     """pksk flat [2048][ell][k' + 1][N'], cts (B, 2049) -> per GLWE the uint32 array of its k' N' + b_g
     stored values"""

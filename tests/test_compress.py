@@ -202,6 +202,64 @@ def test_edge_rows_alone(case):
     assert not vals[:kn].any() and list(vals[kn:]) == [b12, b12]
 
 
+def test_stored_bytes_cannot_see_the_low_planes():
+    """Why tests/test_pack_keyswitch_gpu.py pins the contraction's 64-bit words and not only the compressed
+    bytes: at the defaults, 257 blocks (a full GLWE and a one-block one), the stored 12-bit values do not move when
+    bits 0-15 of EVERY packing-key word are cleared -- two of the eight byte planes the GPU contracts, and every
+    carry out of them, are invisible to any comparison of compressed lists.  Clearing is a one-sided error: the
+    digits' mean is -1/2, so it shifts a block's words by about 8192 * 1/2 * 2^15 = 2^27 and a coefficient of a
+    full GLWE by up to 2^35, against a rounding step of 2^52 -- a flip has probability up to 2^-17 per
+    coefficient, about 2 % over this list (the seed below is one at which none occurs; six other seeds: 0 of
+    13,830 values moved at 16 bits, 6 at 24 bits, 1,929 at 32 bits).  Clearing bits 0-47 is the positive control:
+    that does move stored values.  Numpy only: any key words show it, so they are uniform random ones."""
+    cp, B = R.DEFAULT, 257
+    rng = np.random.default_rng(0x10B17E5)
+    key = rng.integers(0, 1 << 64, R.N_BIG * cp.ell * R.cols(cp), dtype=np.uint64)
+    cts = rng.integers(0, 1 << 64, (B, R.BIG_CT), dtype=np.uint64)
+    cts[:4] = R.edge_rows(cp.beta, cp.ell)
+    full = R.pack_keyswitch(cp, key, cts)
+    low16 = R.pack_keyswitch(cp, key & np.uint64(~0xFFFF & R.M64), cts)
+    low48 = R.pack_keyswitch(cp, key & np.uint64(~0xFFFFFFFFFFFF & R.M64), cts)
+    assert [len(g) for g in full] == [cp.k * cp.N + 256, cp.k * cp.N + 1]
+    assert all(np.array_equal(a, b) for a, b in zip(full, low16))
+    moved = sum(int((a != b).sum()) for a, b in zip(full, low48))
+    assert moved > 100  # planes 0-5 reach the rounding bit: a large share of the 2305 values moves
+
+
+PLANE_EDGE_WORDS = (0, 0x80, 0x7F, 0xFF, 0x8000, 0x7FFF, 0x8080808080808080, 0x7F7F7F7F7F7F7F7F, 0x7FFFFFFFFFFFFFFF,
+                    0x8000000000000000, 0xFFFFFFFFFFFFFFFF, 0x00FF00FF00FF00FF, 0xFF80FF80FF80FF80, 0x0123456789ABCDEF)
+
+
+@pytest.mark.parametrize("cp", [R.SMALL_A, R.CP(2, 8, 5, 7, 4, 42), R.SMALL_B, R.DEFAULT], ids=set_id)
+def test_plane_layout_round_trip_and_index_formula(cp):
+    """compress_ref.plane_layout (the GPU's byte planes, restated): sum_b plane_b 256^b gives the key words back
+    mod 2^64, padding columns excluded and all zero; every byte is in [-128, 128) by construction of int8; and
+    sampled bytes equal the layout comment's own index formula evaluated one word at a time.  Random words with
+    the carry edges (0x80 bytes, runs of 0xFF, the top bit) among them.  (2, 8, 5, 7, 4): 24 columns, a padded
+    tile"""
+    import ks_ref
+
+    c, KT, tiles = R.cols(cp), 32 * cp.ell, (R.cols(cp) + 15) // 16
+    rng = np.random.default_rng(0xB17E + cp.N)
+    key = rng.integers(0, 1 << 64, R.N_BIG * cp.ell * c, dtype=np.uint64)
+    key[:len(PLANE_EDGE_WORDS)] = np.array(PLANE_EDGE_WORDS, np.uint64)
+    key[-len(PLANE_EDGE_WORDS):] = np.array(PLANE_EDGE_WORDS, np.uint64)
+    planes = R.plane_layout(cp, key)
+    assert planes.shape == (8, tiles, KT, 64, 16) and planes.dtype == np.int8
+    words, padding = R.words_of_planes(cp, planes)
+    assert np.array_equal(words, key)
+    assert padding.size == 8 * cp.ell * R.N_BIG * (16 * tiles - c) and not padding.any()
+    # the index formula, a word at a time: every corner of the index space and random places
+    k3 = key.reshape(R.N_BIG, cp.ell, c)
+    idx = [(tt, kt, lane, jj) for tt in (0, tiles - 1) for kt in (0, 31, 32, KT - 1) for lane in (0, 15, 16, 63) for jj in (0, 15)]
+    idx += [tuple(int(x) for x in r) for r in np.stack([rng.integers(0, m, 200) for m in (tiles, KT, 64, 16)], axis=1)]
+    for tt, kt, lane, jj in idx:
+        k = 64 * kt + 16 * (lane >> 4) + jj
+        level, j, col = k // R.N_BIG, k % R.N_BIG, 16 * tt + (lane & 15)
+        want = ks_ref.byte_planes(k3[j, level, col:col + 1])[:, 0] if col < c else np.zeros(8, np.int64)
+        assert list(planes[:, tt, kt, lane, jj]) == list(want), (tt, kt, lane, jj)
+
+
 # ------------------------------------------------------------------ direct decryption
 def test_direct_decryption_of_all_16_values_in_every_slot(case):
     """16 lists of L + 1 blocks (a full GLWE and a second one): slot t of list r holds (t + r) % 16.  At the

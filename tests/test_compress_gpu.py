@@ -1,8 +1,9 @@
 """Compressed computed ciphertexts on the GPU (csrc/compress.hip through Engine::compress / decompress)
 against the host definition fhe_compress_host, which tests/test_compress.py pins word for word to
 tests/compress_ref.py.  Compression is compared byte for byte; decompression row for row with the numpy
-sample extract, word for word with the re-keyed oracle at the small parameter sets, and by value at the
-defaults.
+sample extract, word for word with the re-keyed oracle at the small parameter sets and, at the defaults
+(LWE dimension k' N' = 1024, every blind-rotate kernel), on 24 rows of a 1024-block list.  The contraction's
+64-bit words, which the bytes cannot see below their 12 bits, are pinned in tests/test_pack_keyswitch_gpu.py.
 
 Noise (test_noise_of_stored_values): m = 2^14 blocks, built as tests/test_noise_gpu.py builds its inputs --
 8192 type-A combinations 4 s0 + 2 s1 + s2 + c (22 units, covering all 16 values) and 8192 type-B 4 s + 3 c
@@ -116,6 +117,45 @@ def test_compress_is_byte_identical_to_the_host(env, B):
     assert lst.decrypt(env.priv) == v
 
 
+def _raw_rows(cp, B):
+    """uniform random rows (no encryptions: nothing is decrypted), the digit edge rows first and last"""
+    cts = np.random.default_rng(0xB16 + B).integers(0, 1 << 64, (B, R.BIG_CT), dtype=np.uint64)
+    cts[:4] = cts[B - 4:] = R.edge_rows(cp.beta, cp.ell)
+    return cts
+
+
+@pytest.mark.parametrize("B", [2048, 2064, 2352])
+def test_large_lists_are_byte_identical_to_the_host(env, B):
+    """From 2048 blocks on the contraction is k_pk_mfma<4> (256 rows per workgroup): 2048 fills eight workgroups;
+    2064 puts one 16-row tile into a ninth; 2352 leaves the last workgroup with three tiles in wave 0 and waves
+    1-3 past the count, reading digit fragments no kernel wrote.  A radix integer ends at 2048 blocks (4096 bits)
+    and a BigUintFHE is whole limbs of 16, so 2064 and 2352 are the lists nearest to 2049 and 2367 that a
+    compressed list can hold; those two counts themselves are pinned word for word, before the rounding, in
+    tests/test_pack_keyswitch_gpu.py.  Raw rows at degree 3, as the edge-row case hands them in"""
+    cp, cts = env.cp, _raw_rows(env.cp, B)
+    if B <= 2048:
+        x, form, count = env.raw(cts, 3), RADIX, 2 * B
+    else:
+        x, form, count = BigUintFHE.deserialize(R.raw_biguint_blob(env.main, cts, 3)), BIGUINT, B // 16
+    lst = x.compress()
+    blob = lst.serialize()
+    assert lst.nblocks == B
+    assert blob == CompressedCiphertextList.compress_host(env.key, cts, 3, form, count).serialize()
+    assert len(blob) == c_params(cp).wire_bytes(B) == R.wire_len(cp, B)
+
+
+def test_large_list_of_real_encryptions_decrypts(env):
+    """129 limbs = 2064 blocks (k_pk_mfma<4>, nine GLWEs, the last with 16 bodies): byte for byte the host's, and
+    the client reads the value back"""
+    v = _value(32 * 129, 11) | 1 << (32 * 129 - 1)  # the top limb is not zero: 129 limbs
+    x = BigUintFHE.new(v, env.ck)
+    assert len(x) == 129
+    lst = x.compress()
+    assert lst.nblocks == 2064
+    assert lst.serialize() == env.host(x, lst, BIGUINT, 129).serialize()
+    assert lst.decrypt(env.priv) == v
+
+
 @pytest.mark.parametrize("which", ["1", "L+1"])
 def test_compress_small_sets(small, which):
     cp = small.cp
@@ -182,6 +222,12 @@ def test_unpack_rows_at_the_defaults(env):
     B = 257
     lst = CompressedCiphertextList.compress_host(env.key, env.ck.encrypt_blocks([i % 16 for i in range(B)]), 15, RADIX, 2 * B)
     assert np.array_equal(lst.extract_rows(), R.extract_rows(env.cp, R.parse_list(env.cp, lst.serialize())[3]))
+    # nine GLWEs, the last with 16 bodies: 129 limbs, the shortest list past 2048 blocks
+    B = 2064
+    lst = CompressedCiphertextList.compress_host(env.key, env.ck.encrypt_blocks([i % 16 for i in range(B)]), 15, BIGUINT, B // 16)
+    glwes = R.parse_list(env.cp, lst.serialize())[3]
+    assert [len(g) - env.cp.k * env.cp.N for g in glwes] == [256] * 8 + [16]
+    assert np.array_equal(lst.extract_rows(), R.extract_rows(env.cp, glwes))
 
 
 def test_decompress_latency_and_throughput_kernels(env):
@@ -199,6 +245,54 @@ def test_decompress_latency_and_throughput_kernels(env):
     finally:
         env.ctx.set_wide_threshold(256)
     assert np.array_equal(lat, thr)
+
+
+@pytest.fixture(scope="module")
+def oracle_1024(env_obj):
+    """the oracle re-keyed at n = k' N' = 1024 with the default set's decompression BSK (it shares the big key)"""
+    kn = R.DEFAULT.k * R.DEFAULT.N
+    return K.rekeyed_oracle(SEED, kn, 1, np.zeros(R.N_BIG * 5 * (kn + 1), np.uint64), env_obj.key.export()[1])
+
+
+def test_decompress_words_at_the_defaults(env, oracle_1024):
+    """The decompression bootstrap at the default set runs at LWE dimension k' N' = 1024, which no other test
+    pins word for word.  1024 blocks of all 16 values, compressed on the GPU, decompressed four ways: as the
+    product does (FHE_BR_AUTO: 1024 fills qz's rounds, the second Fourier layout), under FHE_BR_QY, with the wide
+    threshold at 1024 (the latency kernel), and in centered modulus-switch mode (the rows are multiples of 2^52:
+    centring changes nothing).  All words equal; the first, the middle (across the 512 seam) and the last eight
+    rows equal the re-keyed oracle's"""
+    cp, ctx, B = env.cp, env.ctx, 1024
+    vals = [(11 * i + 5) % 16 for i in range(B)]
+    x = env.raw(env.ck.encrypt_blocks(vals), 15)
+    lst = x.compress()
+    assert lst.serialize() == env.host(x, lst).serialize()
+    rows = R.extract_rows(cp, R.parse_list(cp, lst.serialize())[3])
+    assert rows.shape == (B, cp.k * cp.N + 1) and not (rows & np.uint64((1 << 52) - 1)).any()
+    out = {}
+    try:
+        out["auto (qz)"] = lst.decompress().export()
+        ctx.set_br_kernel(4)  # FHE_BR_QY
+        out["qy"] = lst.decompress().export()
+        ctx.set_br_kernel(7)  # FHE_BR_AUTO
+        ctx.set_wide_threshold(1024)
+        out["latency"] = lst.decompress().export()
+        ctx.set_wide_threshold(256)
+        ctx.set_modulus_switch("centered")
+        out["centered"] = lst.decompress().export()
+    finally:
+        ctx.set_br_kernel(7)
+        ctx.set_wide_threshold(256)
+        ctx.set_modulus_switch("standard")
+    assert len(out) == 4
+    for name, words in out.items():
+        assert words.shape == (B, R.BIG_CT)
+        assert np.array_equal(words, out["auto (qz)"]), name
+    sel = np.r_[0:8, 508:516, 1016:1024]
+    want = R.oracle_decompress(oracle_1024, rows[sel])
+    for name, words in out.items():
+        bad = [int(i) for i, a, b in zip(sel, words[sel], want) if not np.array_equal(a, b)]
+        assert not bad, f"{name}: rows {bad} differ from the oracle"
+    assert [env.ck.decrypt_block(c) for c in out["auto (qz)"]] == vals
 
 
 def test_multi_bit_main_key_with_a_classic_decompression_key(env):
