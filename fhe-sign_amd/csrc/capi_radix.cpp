@@ -10,6 +10,7 @@
 #include <future>
 
 #include "biguint.h"
+#include "ct_digest.h"
 #include "fhe_rocm.h"
 #include "serial.h"
 
@@ -1767,6 +1768,92 @@ int fhe_rerandomize_rows(fhe_ctx* c, const uint8_t* seed, const uint64_t* rows, 
         const Blocks res = c->engine->rerandomize(blocks, seed32);
         for (size_t i = 0; i < nblocks; ++i) blocks[i] = &res[i];
         c->engine->download_many(blocks, out);
+        return FHE_OK;
+    });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------- ciphertext digests
+// The device ends of ct_digest.h: the value digest of a resident operand, the row digests computed by
+// Engine::digest.  The host definitions and the re-randomization context are in ct_digest.cpp.
+namespace {
+void value_digest(fhe_ctx* c, uint8_t kind, uint32_t bits, const std::vector<const Block*>& blocks, uint8_t out[32]) {
+    const size_t n = blocks.size();
+    std::vector<uint8_t> rowd(32 * n), tags(n);
+    std::vector<uint32_t> degrees(n), noises(n);
+    std::vector<Engine::DigestMeta> meta;
+    c->engine->digest(blocks, rowd.data(), &meta);
+    for (size_t i = 0; i < n; ++i) {
+        tags[i] = meta[i].tag;
+        degrees[i] = meta[i].degree;
+        noises[i] = meta[i].noise;
+    }
+    ct_value_digest_host(kind, bits, tags.data(), degrees.data(), noises.data(), rowd.data(), n, out);
+}
+int radix_digest(fhe_ctx* c, const fhe_radix* x, uint8_t out[32]) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    return guarded([&] {
+        std::vector<const Block*> blocks;
+        for (const Block& b : x->r.blocks) blocks.push_back(&b);
+        value_digest(c, FHE_CT_KIND_RADIX, x->bits, blocks, out);
+        return FHE_OK;
+    });
+}
+int biguint_digest(fhe_ctx* c, const fhe_biguint* x, uint8_t out[32]) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    return guarded([&] {
+        std::vector<const Block*> blocks;
+        for (const Radix& d : x->v.digits) {
+            engine_check(d.nblocks() == kLimbBlocks, "fhe_biguint_digest: a limb is not a 32-bit radix");
+            for (const Block& b : d.blocks) blocks.push_back(&b);
+        }
+        value_digest(c, FHE_CT_KIND_BIGUINT, (uint32_t)(32 * x->v.digits.size()), blocks, out);
+        return FHE_OK;
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int fhe_radix_digest(fhe_ctx* c, const fhe_radix* x, uint8_t out[32]) {
+    if (!x || !out) return invalid("null argument to fhe_radix_digest");
+    return radix_digest(c, x, out);
+}
+
+int fhe_biguint_digest(fhe_ctx* c, const fhe_biguint* x, uint8_t out[32]) {
+    if (!x || !out) return invalid("null argument to fhe_biguint_digest");
+    return biguint_digest(c, x, out);
+}
+
+int fhe_rerand_context_add_radix(fhe_ctx* c, fhe_rerand_context* rc, const fhe_radix* x) {
+    if (!rc || !x) return invalid("null argument to fhe_rerand_context_add_radix");
+    if (rc->finalized) return invalid("fhe_rerand_context_add_radix: the context gave out a seed already; a seed depends on everything added");
+    uint8_t d[32];
+    const int r = radix_digest(c, x, d);
+    return r ? r : fhe_rerand_context_add_digest(rc, d);
+}
+
+int fhe_rerand_context_add_biguint(fhe_ctx* c, fhe_rerand_context* rc, const fhe_biguint* x) {
+    if (!rc || !x) return invalid("null argument to fhe_rerand_context_add_biguint");
+    if (rc->finalized) return invalid("fhe_rerand_context_add_biguint: the context gave out a seed already; a seed depends on everything added");
+    uint8_t d[32];
+    const int r = biguint_digest(c, x, d);
+    return r ? r : fhe_rerand_context_add_digest(rc, d);
+}
+
+int fhe_ct_digest_rows(fhe_ctx* c, const uint64_t* rows, size_t nblocks, uint8_t* out) {
+    if ((!rows || !out) && nblocks) return invalid("null argument to fhe_ct_digest_rows");
+    if (nblocks > kCtDigestMaxRows) return invalid("fhe_ct_digest_rows: more than 2^24 blocks");
+    int rc = need_engine(c);
+    if (rc || !nblocks) return rc;
+    return guarded([&] {
+        const Blocks in = c->engine->upload_many(rows, nblocks, kMsgMod - 1);
+        std::vector<const Block*> blocks;
+        for (const Block& b : in) blocks.push_back(&b);
+        c->engine->digest(blocks, out);
         return FHE_OK;
     });
 }

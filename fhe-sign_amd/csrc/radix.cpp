@@ -14,6 +14,7 @@
 // on encrypted data.
 #include "radix.h"
 #include "compress_kernels.h"
+#include "ct_digest.h"
 #include "keygen.h"
 
 #include <algorithm>
@@ -1270,6 +1271,47 @@ Blocks Engine::rerandomize(const std::vector<const Block*>& blocks, const uint8_
     hip_check(launch_rerand_add(ctx_->d_rr_z, d_src, d_tbody, d_dst, (uint32_t)n, ctx_->stream), "re-randomization");
     hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
     return out;
+}
+
+// ------------------------------------------------------------------ ciphertext digests
+void Engine::digest(const std::vector<const Block*>& blocks, uint8_t* out, std::vector<DigestMeta>* meta) {
+    engine_check(host_mode_ == kDevice, "digest on a host-only engine");
+    const size_t n = blocks.size();
+    engine_check(n <= kCtDigestMaxRows, "digest of more than 2^24 blocks");
+    if (meta) meta->assign(n, DigestMeta{0, 0, 0});
+    if (n == 0) return;
+    // lazy blocks first: their combination into slots of their own (lincomb flushes)
+    Blocks real(n);
+    std::vector<const Block*> in(n);
+    for (size_t i = 0; i < n; ++i) {
+        in[i] = blocks[i];
+        if (!blocks[i]->lazy()) continue;
+        engine_check(blocks[i]->lin_cst >= 0, "digest of a lazy block below zero");
+        const uint32_t degree = blocks[i]->degree;
+        real[i] = lincomb(*blocks[i]->lin, (uint32_t)blocks[i]->lin_cst);
+        real[i].degree = degree;
+        in[i] = &real[i];
+    }
+    flush_for(in);
+    const size_t words = 2 * n + 4 * n;  // the entries (16 B each), then the digests (32 B each, 16-byte aligned)
+    uint64_t* const d_up = staging(words);
+    std::vector<CtDigestEntry> entries(n);
+    for (size_t i = 0; i < n; ++i) {
+        const Block& b = *in[i];
+        entries[i].src = b.ptr();
+        entries[i].tbody = 0;
+        if (b.trivial()) {
+            engine_check(!b.half_neg, "digest of a half-step block");
+            entries[i].tbody = (uint64_t)b.value * ctx_->p.delta();
+        }
+        if (meta) (*meta)[i] = b.trivial() ? DigestMeta{0, b.value, 0} : DigestMeta{1, b.degree, b.noise};
+    }
+    CtDigestEntry* d_entries = reinterpret_cast<CtDigestEntry*>(d_up);
+    uint8_t* d_out = reinterpret_cast<uint8_t*>(d_up + 2 * n);
+    hip_check(hipMemcpyAsync(d_entries, entries.data(), n * sizeof(CtDigestEntry), hipMemcpyHostToDevice, ctx_->stream), "digest entries");
+    hip_check(launch_ct_digest(d_entries, d_out, (uint32_t)n, ct_digest_midstates(), ctx_->stream), "ciphertext digest");
+    hip_check(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, ctx_->stream), "digest download");
+    wait_check(ctx_, "digest");
 }
 
 Blocks Engine::upload_deferred(size_t n, uint32_t degree, std::function<std::vector<uint64_t>()> fill) {

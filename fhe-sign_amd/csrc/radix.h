@@ -230,6 +230,18 @@ public:
     // 2^30, against 2^49.7 of a bootstrap's output); a trivial block becomes a slot block of degree
     // max(value, 3) with no known-value shortcut left.  Device engines with a public key only.
     Blocks rerandomize(const std::vector<const Block*>& blocks, const uint8_t seed[32]);
+    // Row digests of the blocks on the device (ct_digest.h), modelled on rerandomize: out = 32 bytes per block,
+    // word for word ct_digest_host of the blocks' exported rows.  Pending producers of the blocks are launched
+    // first (flush_for), a lazy block is made real by lincomb, a trivial block enters as the row (0, delta
+    // value).  One 16-byte entry per block is staged, one kernel, one download of 32 n bytes, one wait; the
+    // blocks are untouched.  No collective of its own: every rank hashes its own replica.  meta (optional): per
+    // block the value digest's fields -- tag 1, degree, noise label of a ciphertext (a lazy block: as made
+    // real), tag 0, the value, 0 of a trivial block.  Device engines only.
+    struct DigestMeta {
+        uint8_t tag;
+        uint32_t degree, noise;
+    };
+    void digest(const std::vector<const Block*>& blocks, uint8_t* out, std::vector<DigestMeta>* meta = nullptr);
     void download(const Block& b, uint64_t* ct);
     // the slot blocks' ciphertexts -> host, contiguous (one gather + one copy + one wait instead of a
     // round trip per block: the decryption of a 256-bit result is 128-144 blocks)

@@ -13,77 +13,10 @@
 
 #include "biguint.h"
 #include "fhe_rocm.h"
+#include "sha256.h"  // Sha256, tagged_hash
 
 namespace fhe {
 namespace {
-
-// ------------------------------------------------------------------------------- SHA-256
-struct Sha256 {
-    uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-    uint8_t buf[64];
-    size_t len = 0;
-    uint64_t total = 0;
-    static uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-    void block(const uint8_t* p) {
-        static const uint32_t K[64] = {
-            0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
-            0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
-            0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
-            0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
-            0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-            0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
-            0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
-            0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-        uint32_t w[64];
-        for (int i = 0; i < 16; ++i) w[i] = (uint32_t)p[4 * i] << 24 | (uint32_t)p[4 * i + 1] << 16 | (uint32_t)p[4 * i + 2] << 8 | p[4 * i + 3];
-        for (int i = 16; i < 64; ++i) {
-            uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3);
-            uint32_t s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-            w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-        }
-        uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-        for (int i = 0; i < 64; ++i) {
-            uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + K[i] + w[i];
-            uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-            hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-        }
-        h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
-    }
-    void update(const uint8_t* p, size_t n) {
-        total += n;
-        while (n) {
-            size_t k = std::min(n, 64 - len);
-            std::memcpy(buf + len, p, k);
-            len += k; p += k; n -= k;
-            if (len == 64) { block(buf); len = 0; }
-        }
-    }
-    std::array<uint8_t, 32> final() {
-        uint64_t bits = total * 8;
-        uint8_t pad = 0x80;
-        update(&pad, 1);
-        uint8_t z = 0;
-        while (len != 56) update(&z, 1);
-        uint8_t L[8];
-        for (int i = 0; i < 8; ++i) L[i] = (uint8_t)(bits >> (56 - 8 * i));
-        update(L, 8);
-        std::array<uint8_t, 32> out;
-        for (int i = 0; i < 8; ++i)
-            for (int j = 0; j < 4; ++j) out[4 * i + j] = (uint8_t)(h[i] >> (24 - 8 * j));
-        return out;
-    }
-};
-
-std::array<uint8_t, 32> tagged_hash(const char* tag, const std::vector<uint8_t>& msg) {
-    Sha256 t;
-    t.update((const uint8_t*)tag, std::strlen(tag));
-    auto th = t.final();
-    Sha256 s;
-    s.update(th.data(), 32);
-    s.update(th.data(), 32);
-    s.update(msg.data(), msg.size());
-    return s.final();
-}
 
 // ------------------------------------------------------------------------------- u256
 struct U256 {
@@ -594,6 +527,42 @@ int fhe_schnorr_sign_fhe_with_k0(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t
                 ms(t0, t1), ms(t1, t2), ms(t2, clk::now()));
     }
     return rc;
+}
+
+// sign_fhe_with_k0 on a re-randomized privkey_fhe, the seed bound to (domain, r_x || pubkey_x || msg, the
+// ciphertext's own digest).  The re-randomization is complete before the signing path starts: no deferred
+// encryption is in flight while it can fail, and the signing path joins its helper thread as the call above does.
+int fhe_schnorr_sign_fhe_with_k0_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
+                                        const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode,
+                                        const uint8_t* domain, size_t domain_len, uint8_t sig[64]) {
+    if (!ctx || !ck || (len && !msg) || !k0 || !privkey || !privkey_fhe || (domain_len && !domain) || !sig) {
+        set_error("null argument to fhe_schnorr_sign_fhe_with_k0_rerand");
+        return FHE_ERR_INVALID;
+    }
+    if (!ctx->has_pk) {
+        set_error("no public key installed (fhe_set_public_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    fhe_rerand_context* rc = nullptr;
+    fhe_biguint* fresh = nullptr;
+    uint8_t seed[32];
+    int r = fhe_rerand_context_new(domain, domain_len, &rc);
+    if (!r) {
+        const U256 d = nmod(U256::from_be(privkey));
+        std::vector<uint8_t> bound = be32(pmul(generator(), U256::from_be(k0)).x);  // r_x (the prologue's R = k0 G)
+        const std::vector<uint8_t> px = be32(pubkey_even_y(d).x);
+        bound.insert(bound.end(), px.begin(), px.end());
+        bound.insert(bound.end(), msg, msg + len);
+        r = fhe_rerand_context_add_bytes(rc, bound.data(), bound.size());
+    }
+    if (!r) r = fhe_rerand_context_add_biguint(ctx, rc, privkey_fhe);
+    if (!r) r = fhe_rerand_context_seed(rc, 0, seed);
+    if (!r) r = fhe_biguint_rerandomize(ctx, privkey_fhe, seed, &fresh);
+    for (volatile uint8_t& b : seed) b = 0;  // used for this call, kept nowhere
+    fhe_rerand_context_destroy(rc);
+    if (!r) r = fhe_schnorr_sign_fhe_with_k0(ctx, ck, msg, len, k0, privkey, fresh, mode, sig);
+    fhe_biguint_destroy(fresh);
+    return r;
 }
 
 // A batch of independent sign_fhe_with_k0 calls run as one engine schedule (their bootstraps share

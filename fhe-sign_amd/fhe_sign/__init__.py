@@ -15,6 +15,9 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
                                       without any secret, .expand() on the GPU
   Context.set_public_key / x.re_randomize(seed)   tfhe's re_randomize: a fresh public-key encryption of zero added
                                       to every block on the GPU (rerandomize_host: the host definition)
+  ReRandomizationContext / re_randomize_bound / x.digest()   tfhe's ReRandomizationContext: the seed is a hash of
+                                      the ciphertexts' own bytes, digested on the GPU (ct_digest_host: the host
+                                      definition), plus domain separators
   Context.set_modulus_switch("centered")   tfhe's centered mean noise reduction: the public half of the modulus
                                       switch's rounding error leaves the body on the GPU before every blind
                                       rotation (ms_center_host: the host definition)
@@ -30,5 +33,6 @@ from .integer import (  # noqa: F401,E402
     CompressedBigUintFHE, CompressedFheUint, CompressedFheUint8, CompressedFheUint32, CompressedFheUint64,
     CompressedFheUint128, CompressedFheUint256, CompressedCiphertextList,
     CompactCiphertextList, CompactCiphertextListBuilder,
-    rerandomization_seed, rerandomize_host, rerandomize_rows, rerandomize_zero_host)
+    rerandomization_seed, rerandomize_host, rerandomize_rows, rerandomize_zero_host,
+    ReRandomizationContext, ct_digest_host, ct_digest_rows, ct_value_digest_host, re_randomize_bound)
 from .schnorr import Schnorr, compute_nonce, public_key_x  # noqa: F401,E402

@@ -298,6 +298,21 @@ _SIGNATURES = [
     ("fhe_rerandomize_rows", C.c_int, [C.c_void_p, C.c_char_p, u64p, C.c_size_t, u64p]),
     ("fhe_ctx_time_rerand_zero", C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_float)]),
     ("fhe_rerandomize_seed", C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, u8p]),
+    ("fhe_ct_digest_host", C.c_int, [u64p, C.c_size_t, u8p]),
+    ("fhe_ct_value_digest_host", C.c_int, [C.c_uint8, C.c_uint32, u8p, u32p, u32p, u8p, C.c_size_t, u8p]),
+    ("fhe_rerand_context_new", C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_rerand_context_add_bytes", C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
+    ("fhe_rerand_context_add_digest", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("fhe_rerand_context_seed", C.c_int, [C.c_void_p, C.c_uint64, u8p]),
+    ("fhe_rerand_context_destroy", None, [C.c_void_p]),
+    ("fhe_radix_digest", C.c_int, [C.c_void_p, C.c_void_p, u8p]),
+    ("fhe_biguint_digest", C.c_int, [C.c_void_p, C.c_void_p, u8p]),
+    ("fhe_rerand_context_add_radix", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fhe_rerand_context_add_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("fhe_ct_digest_rows", C.c_int, [C.c_void_p, u64p, C.c_size_t, u8p]),
+    ("fhe_ctx_time_ct_digest", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_float)]),
+    ("fhe_schnorr_sign_fhe_with_k0_rerand", C.c_int, [C.c_void_p, C.c_void_p, u8p, C.c_size_t, u8p, u8p, C.c_void_p, C.c_int,
+                                                     C.c_char_p, C.c_size_t, u8p]),
     ("fhe_schnorr_public_key", C.c_int, [u8p, u8p]),
     ("fhe_schnorr_compute_nonce", C.c_int, [u8p, u8p, C.c_size_t, u8p, u8p]),
     ("fhe_schnorr_sign_with_k0", C.c_int, [u8p, C.c_size_t, u8p, u8p, u8p]),

@@ -578,6 +578,12 @@ class Context:
         """0 = 64-bit VALU keyswitch, 1 = int8 matrix-core keyswitch (default); identical results"""
         check(load().fhe_ctx_set_ks_kernel(self._h, int(kind)))
 
+    def time_ct_digest(self, nblocks: int, reps: int) -> float:
+        """measurement hook (fhe_ctx_time_ct_digest): mean milliseconds of k_ct_digest over nblocks resident rows"""
+        ms = C.c_float()
+        check(load().fhe_ctx_time_ct_digest(self._h, nblocks, reps, C.byref(ms)))
+        return ms.value
+
     def set_modulus_switch(self, mode: str) -> None:
         """"standard" (default) or "centered" (fhe_ctx_set_modulus_switch): in centered mode every keyswitch this
         context launches from now on is followed by k_ms_center, which takes the public half of the modulus

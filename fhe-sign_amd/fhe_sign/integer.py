@@ -126,6 +126,13 @@ class FheUint:
         check(load().fhe_radix_rerandomize(_ctx().handle, self._h, _rerand_seed(seed), C.byref(h)))
         return self._wrap(h, self.bits)
 
+    def digest(self) -> bytes:
+        """the 32-byte value digest D(self) (fhe_radix_digest): the blocks are hashed on the GPU, 32 bytes each
+        come back; self is untouched"""
+        out = (C.c_uint8 * 32)()
+        check(load().fhe_radix_digest(_ctx().handle, self._h, out))
+        return bytes(out)
+
     # ---- helpers
     def _bin(self, fn, other):
         h = C.c_void_p()
@@ -413,6 +420,12 @@ class BigUintFHE:
         check(load().fhe_biguint_rerandomize(_ctx().handle, self._h, _rerand_seed(seed), C.byref(h)))
         return BigUintFHE(h)
 
+    def digest(self) -> bytes:
+        """the 32-byte value digest of the digits in order, 16 blocks each (fhe_biguint_digest)"""
+        out = (C.c_uint8 * 32)()
+        check(load().fhe_biguint_digest(_ctx().handle, self._h, out))
+        return bytes(out)
+
     __add__ = add
     __mul__ = mul
 
@@ -457,6 +470,89 @@ def rerandomization_seed(domain: bytes, data: bytes) -> bytes:
     out = (C.c_uint8 * 32)()
     check(load().fhe_rerandomize_seed(domain, len(domain), data, len(data), out))
     return bytes(out)
+
+
+def ct_digest_host(rows) -> np.ndarray:
+    """the host definition of the row digest (fhe_ct_digest_host): (n, 32) bytes for n rows of 2049 words; no
+    context, no GPU"""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2049)
+    out = np.zeros((rows.shape[0], 32), np.uint8)
+    check(load().fhe_ct_digest_host(ptr(rows), rows.shape[0], ptr(out, C.c_uint8)))
+    return out
+
+
+def ct_digest_rows(rows, ctx=None) -> np.ndarray:
+    """test hook (fhe_ct_digest_rows): the GPU path over n x 2049 host words, any n up to 2^24"""
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, 2049)
+    out = np.zeros((rows.shape[0], 32), np.uint8)
+    check(load().fhe_ct_digest_rows((ctx or _ctx()).handle, ptr(rows), rows.shape[0], ptr(out, C.c_uint8)))
+    return out
+
+
+def ct_value_digest_host(kind: int, bits: int, tags, degrees, noises, rowdigests) -> bytes:
+    """fhe_ct_value_digest_host: D(x) from the per-block fields and row digests; kind 0 radix, 1 BigUintFHE"""
+    tags = np.ascontiguousarray(tags, dtype=np.uint8)
+    degrees, noises = np.ascontiguousarray(degrees, dtype=np.uint32), np.ascontiguousarray(noises, dtype=np.uint32)
+    rowdigests = np.ascontiguousarray(rowdigests, dtype=np.uint8).reshape(-1, 32)
+    n = tags.size
+    if not (degrees.size == noises.size == rowdigests.shape[0] == n):
+        raise ValueError("one tag, degree, noise and row digest per block")
+    out = (C.c_uint8 * 32)()
+    check(load().fhe_ct_value_digest_host(kind, bits, ptr(tags, C.c_uint8), ptr(degrees, C.c_uint32), ptr(noises, C.c_uint32),
+                                          ptr(rowdigests, C.c_uint8), n, out))
+    return bytes(out)
+
+
+class ReRandomizationContext:
+    """tfhe-rs' ReRandomizationContext (fhe_rerand_context_*): a running hash over a domain separator and, in call
+    order, caller bytes and the digests of ciphertexts; seed(i) is the 32-byte seed of the i-th re_randomize call.
+    The first seed() finalizes the context: a later add raises FheError (a seed depends on everything added)."""
+
+    def __init__(self, domain: bytes):
+        domain = bytes(domain)
+        self._h = C.c_void_p()
+        check(load().fhe_rerand_context_new(domain, len(domain), C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_rerand_context_destroy(self._h)
+            self._h = None
+
+    def add_bytes(self, data: bytes):
+        data = bytes(data)
+        check(load().fhe_rerand_context_add_bytes(self._h, data, len(data)))
+        return self
+
+    def add_digest(self, digest: bytes):
+        digest = bytes(digest)
+        if len(digest) != 32:
+            raise ValueError("a value digest is 32 bytes")
+        check(load().fhe_rerand_context_add_digest(self._h, digest))
+        return self
+
+    def add(self, x):
+        """the value digest of an FheUint or a BigUintFHE, computed on the GPU"""
+        fn = load().fhe_rerand_context_add_biguint if isinstance(x, BigUintFHE) else load().fhe_rerand_context_add_radix
+        check(fn(_ctx().handle, self._h, x.handle))
+        return self
+
+    def seed(self, index: int) -> bytes:
+        out = (C.c_uint8 * 32)()
+        check(load().fhe_rerand_context_seed(self._h, index, out))
+        return bytes(out)
+
+
+def re_randomize_bound(domain: bytes, values, data: bytes = b"") -> list:
+    """re-randomizes every value under a seed bound to all of them: one ReRandomizationContext over `domain`, the
+    bytes `data` (if any), then every value's digest in order; value i is re-randomized with seed(i).  No seed is
+    passed in or out, so replicas and the ranks of a communicator compute the same ciphertexts."""
+    values = list(values)
+    rc = ReRandomizationContext(domain)
+    if data:
+        rc.add_bytes(data)
+    for x in values:
+        rc.add(x)
+    return [x.re_randomize(rc.seed(i)) for i, x in enumerate(values)]
 
 
 SEEDED_RADIX, SEEDED_BIGUINT = 0, 1  # FHE_SEEDED_*

@@ -66,8 +66,18 @@ class Schnorr:
         s_without_mod = k_fhe.add(e_fhe.mul(privkey_fhe, mode), mode).to_biguint(client_key)
         return rx + _b32(s_without_mod % CURVE_ORDER)
 
-    def sign_fhe_with_k0(self, message: bytes, k0: int, privkey: int, privkey_fhe, client_key, mode: int = COMPAT) -> bytes:
+    def sign_fhe_with_k0(self, message: bytes, k0: int, privkey: int, privkey_fhe, client_key, mode: int = COMPAT,
+                         rerandomize_domain=None) -> bytes:
+        """rerandomize_domain (bytes): sign with a re-randomized copy of privkey_fhe, the seed bound to the domain,
+        r_x || pubkey_x || message and the ciphertext's own digest (fhe_schnorr_sign_fhe_with_k0_rerand; needs
+        Context.set_public_key).  The signature is the same bytes either way."""
         sig = (C.c_uint8 * 64)()
+        if rerandomize_domain is not None:
+            dom = bytes(rerandomize_domain)
+            check(load().fhe_schnorr_sign_fhe_with_k0_rerand(_ctx().handle, client_key.handle, _buf(message), len(message),
+                                                             _buf(_b32(k0)), _buf(_b32(privkey)), privkey_fhe.handle, mode,
+                                                             dom, len(dom), sig))
+            return bytes(sig)
         check(load().fhe_schnorr_sign_fhe_with_k0(_ctx().handle, client_key.handle, _buf(message), len(message),
                                                   _buf(_b32(k0)), _buf(_b32(privkey)), privkey_fhe.handle, mode, sig))
         return bytes(sig)

@@ -923,6 +923,60 @@ int fhe_ctx_time_rerand_zero(fhe_ctx* ctx, const uint8_t seed[32], size_t nblock
 int fhe_rerandomize_seed(const uint8_t* domain, size_t domain_len, const uint8_t* data, size_t data_len,
                          uint8_t out[32]);
 
+/* ------------------------------------------------------------------- ciphertext digests, bound seeds */
+/* A re-randomization seed bound to the ciphertexts themselves (tfhe-rs' ReRandomizationContext): the seed is a
+ * hash of the ciphertexts' own bytes plus domain separators, so nobody can choose a ciphertext knowing the seed
+ * it will get, and every replica and every rank that holds the same ciphertexts derives the same seed -- no
+ * NULL seed, no seed handed round.  The ciphertexts are hashed where they live: a gfx950 kernel, 32 bytes per
+ * block across the bus.  SHA-256 throughout; H_t(m) = SHA-256(T || T || m), T = SHA-256(t), the signer's tagged
+ * hash.  The hash and the framing are this engine's own (tfhe-rs' bytes are not reproduced: parity unpinned).
+ * ROW DIGEST of a big LWE ciphertext (2049 u64 words, little-endian, 16,392 bytes):
+ *   leaf[j]   = H_"fhe-rocm/ct-leaf"(row bytes [256 j, 256 j + 256)), j < 64;
+ *   node[g]   = H_"fhe-rocm/ct-node"(leaf[8 g] || ... || leaf[8 g + 7]), g < 8;
+ *   rowdigest = H_"fhe-rocm/ct-row"(node[0] || ... || node[7] || u64le(body)).
+ * A trivial block enters as the row (mask 0, body delta value), fhe_radix_rerandomize's convention.
+ * VALUE DIGEST  D(x) = H_"fhe-rocm/ct-value"(u8 kind || u32le(bits) || u32le(nblocks) || for each block in order:
+ * u8 tag || u32le(degree) || u32le(noise) || rowdigest): kind FHE_CT_KIND_RADIX, or FHE_CT_KIND_BIGUINT with
+ * bits = 32 digits, the digits in order, 16 blocks each (the empty vector: nblocks 0); tag 1 for a ciphertext
+ * with its degree and noise label, tag 0 for a trivial block with its value in the degree field and noise 0 --
+ * the per-block fields of the serialized form.
+ * CONTEXT  a running SHA-256 over T_c || T_c || u64le(|domain|) || domain, T_c = SHA-256("fhe-rocm/rerandomize-
+ * context"), then the items in call order as u8 kind || u64le(len) || payload: FHE_RERAND_ITEM_BYTES caller bytes
+ * (a function description, a request id, a public key's serialization if the caller wants it bound),
+ * FHE_RERAND_ITEM_DIGEST a 32-byte value digest.  root = the final digest; seed(i) = H_"fhe-rocm/rerandomize-
+ * seed"(root || u64le(i)).  The first seed call finalizes the context: any later add returns FHE_ERR_INVALID,
+ * because a seed must depend on everything that was added.  One index serves one re-randomization call. */
+#define FHE_CT_KIND_RADIX 0
+#define FHE_CT_KIND_BIGUINT 1
+#define FHE_RERAND_ITEM_BYTES 1
+#define FHE_RERAND_ITEM_DIGEST 2
+typedef struct fhe_rerand_context fhe_rerand_context;
+/* out = 32 bytes per row of 2049 words; no context, no GPU.  The word-for-word definition of the device path.
+ * FHE_ERR_INVALID for a NULL argument or more than 2^24 rows. */
+int fhe_ct_digest_host(const uint64_t* rows, size_t nblocks, uint8_t* out);
+int fhe_ct_value_digest_host(uint8_t kind, uint32_t bits, const uint8_t* tags, const uint32_t* degrees,
+                             const uint32_t* noises, const uint8_t* rowdigests, size_t nblocks, uint8_t out[32]);
+int fhe_rerand_context_new(const uint8_t* domain, size_t domain_len, fhe_rerand_context** rc);
+int fhe_rerand_context_add_bytes(fhe_rerand_context* rc, const uint8_t* data, size_t len);
+int fhe_rerand_context_add_digest(fhe_rerand_context* rc, const uint8_t digest[32]);
+int fhe_rerand_context_seed(fhe_rerand_context* rc, uint64_t index, uint8_t out[32]);
+void fhe_rerand_context_destroy(fhe_rerand_context* rc);
+/* D(x), the row digests computed on the GPU: pending bootstraps x depends on are launched first (under a
+ * communicator the plain flush a decryption makes), a lazy block is made real; one kernel, one download of 32
+ * bytes per block, one wait.  x is untouched.  No collective: every rank hashes its own replica of the operand
+ * and gets the same bytes.  Needs a server key, not a public key. */
+int fhe_radix_digest(fhe_ctx* ctx, const fhe_radix* x, uint8_t out[32]);
+int fhe_biguint_digest(fhe_ctx* ctx, const fhe_biguint* x, uint8_t out[32]);
+/* fhe_rerand_context_add_digest of fhe_radix_digest / fhe_biguint_digest */
+int fhe_rerand_context_add_radix(fhe_ctx* ctx, fhe_rerand_context* rc, const fhe_radix* x);
+int fhe_rerand_context_add_biguint(fhe_ctx* ctx, fhe_rerand_context* rc, const fhe_biguint* x);
+/* Test hook: the device path over nblocks host rows of 2049 words (any count up to 2^24): upload into slots,
+ * digest, download 32 bytes per row into out. */
+int fhe_ct_digest_rows(fhe_ctx* ctx, const uint64_t* rows, size_t nblocks, uint8_t* out);
+/* Measurement hook: the digest kernel alone, `reps` launches over nblocks resident rows between two HIP events
+ * on the context's stream; *ms = the mean per launch. */
+int fhe_ctx_time_ct_digest(fhe_ctx* ctx, size_t nblocks, uint32_t reps, float* ms);
+
 /* ------------------------------------------------------------------- Schnorr / BIP-340 */
 /* The caller of the hot path (src/schnorr.rs).  32-byte scalars are big-endian.  The plaintext
  * EC / hash steps run on the host; the FHE block s = k + e*d runs on the GPU engine. */
@@ -949,6 +1003,15 @@ int fhe_schnorr_sign_prologue(const uint8_t* msg, size_t msg_len, const uint8_t 
 int fhe_schnorr_sign_fhe_with_k0(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t msg_len,
                                  const uint8_t k0[32], const uint8_t privkey[32],
                                  const fhe_biguint* privkey_fhe, int mode, uint8_t sig[64]);
+/* fhe_schnorr_sign_fhe_with_k0 on a re-randomized copy of privkey_fhe, the seed bound to the request: a
+ * re-randomization context over `domain`, the bytes r_x || pubkey_x || msg and the value digest of privkey_fhe
+ * added, privkey_fhe re-randomized with seed(0) before anything else of the call starts, then the existing
+ * signing path on the result.  sig is byte for byte the existing call's; privkey_fhe is untouched.  Works under
+ * a communicator (every rank derives the same seed).  FHE_ERR_NO_KEY without an installed public key. */
+int fhe_schnorr_sign_fhe_with_k0_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t msg_len,
+                                        const uint8_t k0[32], const uint8_t privkey[32],
+                                        const fhe_biguint* privkey_fhe, int mode, const uint8_t* domain,
+                                        size_t domain_len, uint8_t sig[64]);
 /* count independent sign_fhe_with_k0 calls as ONE engine schedule (their bootstraps share launch
  * levels: a batch of signatures costs far less than count single calls on one GPU).  msgs[i] /
  * lens[i]; k0s, privkeys: count x 32 bytes; sigs: count x 64 bytes, each identical to the single call */
