@@ -12,6 +12,7 @@
 #include "biguint.h"
 #include "ct_digest.h"
 #include "fhe_rocm.h"
+#include "oprf.h"
 #include "serial.h"
 
 struct fhe_radix {
@@ -1856,6 +1857,115 @@ int fhe_ct_digest_rows(fhe_ctx* c, const uint64_t* rows, size_t nblocks, uint8_t
         c->engine->digest(blocks, out);
         return FHE_OK;
     });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------- oblivious pseudo-random values
+// tfhe-rs' FheUint::generate_oblivious_pseudo_random[_bounded]: the radix ends of oprf.h.  The host definitions,
+// the row kernel's test entries and fhe_oprf_blocks are in oprf.cpp, the device path is Engine::oprf.
+namespace {
+// the checks of every draw, before anything is launched; seed32 = the call's seed
+int oprf_check(fhe_ctx* c, const uint8_t* seed, uint8_t seed32[32]) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (seed) {
+        std::memcpy(seed32, seed, 32);
+        return FHE_OK;
+    }
+    if (c->attached() && c->nranks > 1)
+        return invalid("an oblivious pseudo-random value under a communicator needs a seed: with seed = NULL every rank "
+                       "would draw its own and the ranks' ciphertexts would diverge");
+    if (!os_entropy32(seed32)) {
+        set_error("getrandom failed: no seed for the oblivious pseudo-random value");
+        return FHE_ERR_UNSUPPORTED;
+    }
+    return FHE_OK;
+}
+// nblocks blocks whose low random_bits bits are random: full blocks on the rows of their index, an odd top bit
+// as a 1-bit block on its row, trivial zeros above
+Radix radix_random(Engine& e, const uint8_t seed[32], uint32_t nblocks, uint32_t random_bits) {
+    Radix r;
+    r.blocks = e.oprf(seed, random_bits / kMsgBits, kMsgBits, random_bits % kMsgBits);
+    r.blocks.resize(nblocks, Block::make_trivial(0));
+    return r;
+}
+uint32_t bit_length(const BigConst& v) {
+    for (size_t i = v.size(); i-- > 0;)
+        if (v[i]) return (uint32_t)(64 * i) + 64 - (uint32_t)__builtin_clzll(v[i]);
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int fhe_radix_random(fhe_ctx* c, const uint8_t* seed, uint32_t width_bits, uint32_t random_bits, fhe_radix** out) {
+    if (!out) return invalid("null argument to fhe_radix_random");
+    if (!valid_bits(width_bits)) return invalid("fhe_radix_random: the width must be even and 2 .. " + std::to_string(FHE_RADIX_MAX_BITS));
+    if (random_bits < 1 || random_bits > width_bits) return invalid("fhe_radix_random: random_bits must be 1 .. the width");
+    uint8_t seed32[32];
+    int rc = oprf_check(c, seed, seed32);
+    if (rc) return rc;
+    rc = guarded([&] {
+        *out = wrap(radix_random(*c->engine, seed32, width_bits / kMsgBits, random_bits), width_bits);
+        return FHE_OK;
+    });
+    wipe32(seed32);
+    return rc;
+}
+
+int fhe_radix_random_below(fhe_ctx* c, const uint8_t* seed, uint32_t width_bits, const uint64_t* bound, size_t nwords,
+                           uint32_t extra_bits, fhe_radix** out) {
+    if (!out || (!bound && nwords)) return invalid("null argument to fhe_radix_random_below");
+    if (!valid_bits(width_bits))
+        return invalid("fhe_radix_random_below: the width must be even and 2 .. " + std::to_string(FHE_RADIX_MAX_BITS));
+    BigConst b = words_of(bound, nwords);
+    const uint32_t blen = bit_length(b);
+    if (blen == 0) return invalid("fhe_radix_random_below: the bound must be positive");
+    // bit_length(bound - 1)
+    BigConst b1 = b;
+    for (size_t i = 0; i < b1.size(); ++i)
+        if (b1[i]-- != 0) break;
+    const uint32_t range_bits = bit_length(b1);
+    if (range_bits > width_bits) return invalid("fhe_radix_random_below: values below the bound do not fit the width");
+    // (r bound) >> m of an m-bit r, computed at m + bit_length(bound) bits: the product does not wrap
+    const uint64_t m = (uint64_t)range_bits + extra_bits, wide = (m + blen + 1) / 2 * 2;
+    if (wide > FHE_RADIX_MAX_BITS)
+        return invalid("fhe_radix_random_below: bit_length(bound - 1) + extra_bits + bit_length(bound) = " + std::to_string(m + blen) +
+                       " bits exceed the " + std::to_string(FHE_RADIX_MAX_BITS) + " a radix integer holds");
+    uint8_t seed32[32];
+    int rc = oprf_check(c, seed, seed32);
+    if (rc) return rc;
+    rc = guarded([&] {
+        Engine& e = *c->engine;
+        Radix r = radix_random(e, seed32, (uint32_t)wide / kMsgBits, (uint32_t)m);
+        if (m) r = radix_scalar_shr(e, radix_scalar_mul(e, r, b), (uint32_t)m);
+        *out = wrap(radix_resize(r, width_bits / kMsgBits), width_bits);
+        return FHE_OK;
+    });
+    wipe32(seed32);
+    return rc;
+}
+
+int fhe_biguint_random(fhe_ctx* c, const uint8_t* seed, uint32_t bits, fhe_biguint** out) {
+    if (!out) return invalid("null argument to fhe_biguint_random");
+    if (bits % 32 != 0 || bits / kMsgBits > kOprfMaxRows) return invalid("fhe_biguint_random: bits must be a multiple of 32");
+    uint8_t seed32[32];
+    int rc = oprf_check(c, seed, seed32);
+    if (rc) return rc;
+    rc = guarded([&] {
+        const Blocks all = c->engine->oprf(seed32, bits / kMsgBits, kMsgBits);
+        auto v = std::make_unique<fhe_biguint>();
+        for (size_t at = 0; at < all.size(); at += kLimbBlocks) {
+            Radix d;
+            d.blocks.assign(all.begin() + at, all.begin() + at + kLimbBlocks);
+            v->v.digits.push_back(std::move(d));
+        }
+        *out = v.release();
+        return FHE_OK;
+    });
+    wipe32(seed32);
+    return rc;
 }
 
 }  // extern "C"

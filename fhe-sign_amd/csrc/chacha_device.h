@@ -1,7 +1,8 @@
 // chacha_device.h -- the ChaCha20 block function (RFC 8439) on the device, shared by the key
 // generation stream kernel (keygen.hip), the seeded-ciphertext expansion (seeded.hip), the seeded server
-// key's install (seeded_key.hip) and the seeded compression key's (seeded_compression.hip); seeded.hip and
-// seeded_key.hip also share the quad exchange for coalesced stores.
+// key's install (seeded_key.hip), the seeded compression key's (seeded_compression.hip) and the rows of the
+// oblivious pseudo-random values (oprf.hip); seeded.hip, seeded_key.hip and oprf.hip also share the quad
+// exchange for coalesced stores.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -176,6 +176,8 @@ struct fhe_ctx {
     int register_lut(const uint32_t* table, uint32_t* id);
     // LUT with outputs in half message steps (raw PbsItems): f(v) = half[v] * delta / 2, v < 16
     int register_lut_half(const int32_t* half, uint32_t* id);
+    // the staircase accumulator of the oblivious pseudo-random values (oprf.cpp: oprf_lut_poly), one per `bits`
+    int register_lut_oprf(uint32_t bits, uint32_t* id);
     // KS + BR(+SE) over device arrays, async on `stream`
     int pbs_device(const uint64_t* d_in, size_t count, const uint32_t* d_lut, uint64_t* d_out);
     // blind rotate (+SE) of `count` modulus-switched inputs in d_ms, kernel chosen by batch size

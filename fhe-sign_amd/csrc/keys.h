@@ -122,6 +122,10 @@ constexpr uint32_t kStreamSeededCbsk = 108;
 // a compact list's encryption seed (105 / 106) does not make related ciphertexts.
 constexpr uint32_t kStreamRerandBinary = 109;
 constexpr uint32_t kStreamRerandNoise = 110;
+// Oblivious pseudo-random values (oprf.h), keyed by a call's PUBLIC seed: row b's n mask words
+// are the first n u64 words of ChaCha blocks [b R, (b + 1) R), R = ceil(n / 8) -- a row starts on a block
+// boundary, whatever the workspace's stride or the number of rows is.
+constexpr uint32_t kStreamOprf = 111;
 
 }  // namespace fhe
 

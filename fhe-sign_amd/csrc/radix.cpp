@@ -16,6 +16,7 @@
 #include "compress_kernels.h"
 #include "ct_digest.h"
 #include "keygen.h"
+#include "oprf.h"
 
 #include <algorithm>
 #include <array>
@@ -1147,6 +1148,55 @@ Blocks Engine::decompress(const fhe_compressed_list& x) {
               "decompress descriptors");
     hip_check(ctx_->blind_rotate(ctx_->comp_keys(), ctx_->d_cdesc, nullptr, nullptr, n), "decompression blind rotate");
     hip_check(hipStreamSynchronize(ctx_->stream), "decompress sync");  // host buffers may go, the staging be reused
+    pbs_count += n;
+    return out;
+}
+
+// ------------------------------------------------------------------ oblivious pseudo-random values
+Blocks Engine::oprf(const uint8_t seed[32], size_t count, uint32_t bits, uint32_t tail_bits) {
+    engine_check(host_mode_ == kDevice, "oprf on a host-only engine");
+    const Params& p = ctx_->p;
+    const uint32_t max_bits = oprf_max_bits(p);
+    if (bits < 1 || bits > max_bits || tail_bits > max_bits)
+        throw std::runtime_error("oprf: bits must be 1 .. log2(message_modulus) = " + std::to_string(max_bits));
+    const size_t n = count + (tail_bits ? 1 : 0);
+    engine_check(n <= kOprfMaxRows, "oprf: more than 2^23 rows of one seed");
+    Blocks out(n);
+    if (n == 0) return out;
+    uint32_t lut = 0, tail_lut = 0;
+    engine_check(ctx_->register_lut_oprf(bits, &lut) == FHE_OK && (!tail_bits || ctx_->register_lut_oprf(tail_bits, &tail_lut) == FHE_OK) &&
+                     ctx_->sync_luts() == FHE_OK,
+                 "oprf accumulator");
+    // the workspace as it stands (at least kOprfChunk rows) is the chunk: a large call does not grow it
+    constexpr size_t kOprfChunk = 4096;
+    const size_t chunk = std::min(n, std::max(ctx_->ms_cap, kOprfChunk));
+    engine_check(ctx_->ensure_ms(chunk) == FHE_OK, "bootstrap workspace");
+    if (!d_oprf_desc_.fits(chunk)) {
+        hip_check(hipStreamSynchronize(ctx_->stream), "oprf descriptors sync");
+        hip_check(d_oprf_desc_.grow(std::max<size_t>(chunk, 256)), "oprf descriptors");
+    }
+    std::vector<PbsDesc> desc(n);
+    std::memset(desc.data(), 0, n * sizeof(PbsDesc));
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t b = i < count ? bits : tail_bits;
+        out[i].slot = pool_->alloc();
+        out[i].degree = (1u << b) - 1;
+        out[i].noise = 1;
+        desc[i].lut = i < count ? lut : tail_lut;
+        desc[i].cst = oprf_body_const(p, b);  // the blind rotation ignores it (no terms, no keyswitch): the body add's
+        desc[i].dst = out[i].slot->p;
+    }
+    const KeyWords key = bytes_key(seed);
+    const ChaChaKey ck = chacha_stream_key(key.data(), kStreamOprf);
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        hip_check(launch_oprf_rows(ck, ctx_->d_ms, (uint32_t)at, (uint32_t)m, p.n, ctx_->stream), "oprf rows");
+        hip_check(hipMemcpyAsync(d_oprf_desc_, desc.data() + at, m * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream),
+                  "oprf descriptors");
+        hip_check(ctx_->blind_rotate(ctx_->main_keys(), d_oprf_desc_, nullptr, nullptr, m), "oprf blind rotate");
+        hip_check(launch_oprf_body_add(d_oprf_desc_, (uint32_t)m, ctx_->stream), "oprf body constant");
+    }
+    hip_check(hipStreamSynchronize(ctx_->stream), "oprf sync");  // host buffers may go
     pbs_count += n;
     return out;
 }

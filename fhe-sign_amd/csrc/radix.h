@@ -242,6 +242,17 @@ public:
         uint32_t degree, noise;
     };
     void digest(const std::vector<const Block*>& blocks, uint8_t* out, std::vector<DigestMeta>* meta = nullptr);
+    // Oblivious pseudo-random blocks (oprf.h): block b < count = the bootstrap of row b of the PUBLIC 32-byte
+    // seed through the `bits`-bit staircase, degree 2^bits - 1, noise 1; with tail_bits != 0 one more block, row
+    // `count` at tail_bits (a radix value's odd top bit).  Eager, modelled on decompress: fresh slots, the row
+    // kernel into the bootstrap workspace, descriptors without terms, the blind rotation under the main key set
+    // (the kernel chosen by count, as for any level), the body constant -- all on the context's stream behind
+    // whatever is launched.  No keyswitch, no upload, no flush: pending deferred nodes stay pending, and the
+    // workspace they will use is theirs again once this is through (stream order).  Counts above the workspace
+    // go in chunks.  No collective: it is deterministic, every rank (and every emulated one) computes every
+    // block.  Independent of fhe_ctx_set_modulus_switch: the rows are not centered, their phase is the
+    // randomness.  Device engines only.
+    Blocks oprf(const uint8_t seed[32], size_t count, uint32_t bits, uint32_t tail_bits = 0);
     void download(const Block& b, uint64_t* ct);
     // the slot blocks' ciphertexts -> host, contiguous (one gather + one copy + one wait instead of a
     // round trip per block: the decryption of a 256-bit result is 128-144 blocks)
@@ -313,6 +324,7 @@ private:
     size_t desc_cap_ = 0;  // of h_desc_; 0 while either is not grown
     int desc_turn_ = 0;
     DeviceBuf<PbsDesc> d_desc_;
+    DeviceBuf<PbsDesc> d_oprf_desc_;  // oprf's descriptors, one chunk (the level descriptors above may be in flight)
     void ensure_desc(size_t n);
     void graph_stats(const std::vector<std::vector<int32_t>>& deps);
     void flush_tail(size_t k0);

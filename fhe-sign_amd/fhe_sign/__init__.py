@@ -21,12 +21,16 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
   Context.set_modulus_switch("centered")   tfhe's centered mean noise reduction: the public half of the modulus
                                       switch's rounding error leaves the body on the GPU before every blind
                                       rotation (ms_center_host: the host definition)
+  FheUint.random(seed) / random_below(bound, seed) / BigUintFHE.random(bits, seed)   tfhe's
+                                      generate_oblivious_pseudo_random[_bounded]: a seed becomes an encrypted uniformly
+                                      random value on the GPU, one blind rotation per block, no keyswitch, no upload
+                                      (oprf_rows_host, oprf_lut_host: the host definitions)
   Schnorr.sign_fhe_with_k0 / sign_fhe src/schnorr.rs:154-290
 All ciphertext arithmetic runs on the GPU through lib/libfhe_rocm.so; this package only marshals.
 """
 from ._lib import CompressionParams, FheError, FheParams, load  # noqa: F401
 from .core import (ClientKey, CompactPublicKey, CompressedCompressionKey, CompressedServerKey, CompressionKey, CompressionKeys, CompressionPrivateKey, Context, ServerKey, comm_unique_id, default_params,  # noqa: F401
-                   default_compression_params, generate_keys, ms_center_host, ms_stride, multi_bit_params, tuning)
+                   default_compression_params, generate_keys, ms_center_host, ms_stride, multi_bit_params, oprf_lut_host, oprf_rows_host, tuning)
 from .integer import (  # noqa: F401,E402
     COMPAT, FAST, PUBLIC, BigUintFHE, FheBool, FheUint, FheUint8, FheUint32, FheUint64, FheUint128, FheUint256, set_server_key,
     LEVEL_SPLIT, level_log, rank_pbs, stats, to_u32_digits,

@@ -311,6 +311,15 @@ _SIGNATURES = [
     ("fhe_rerand_context_add_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("fhe_ct_digest_rows", C.c_int, [C.c_void_p, u64p, C.c_size_t, u8p]),
     ("fhe_ctx_time_ct_digest", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_float)]),
+    ("fhe_oprf_rows_host", C.c_int, [C.c_char_p, C.c_uint32, C.c_size_t, C.c_size_t, u64p]),
+    ("fhe_oprf_lut_host", C.c_int, [C.POINTER(FheParams), C.c_uint32, u64p]),
+    ("fhe_oprf_rows", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_size_t, C.c_size_t, u64p]),
+    ("fhe_ctx_time_oprf_rows", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    ("fhe_oprf_blocks", C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, u64p]),
+    ("fhe_radix_random", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("fhe_radix_random_below", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, u64p, C.c_size_t, C.c_uint32,
+                                         C.POINTER(C.c_void_p)]),
+    ("fhe_biguint_random", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("fhe_schnorr_sign_fhe_with_k0_rerand", C.c_int, [C.c_void_p, C.c_void_p, u8p, C.c_size_t, u8p, u8p, C.c_void_p, C.c_int,
                                                      C.c_char_p, C.c_size_t, u8p]),
     ("fhe_schnorr_public_key", C.c_int, [u8p, u8p]),

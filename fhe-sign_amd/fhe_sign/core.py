@@ -421,6 +421,32 @@ def ms_center_host(rows, stride=None) -> np.ndarray:
     return buf
 
 
+def _oprf_seed(seed) -> bytes:
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes")
+    return seed
+
+
+def oprf_rows_host(seed, n: int, count: int, stride=None) -> np.ndarray:
+    """the host definition of the oblivious pseudo-random values' rows (fhe_oprf_rows_host): (count, stride) words,
+    row b's n mask words from ChaCha blocks [b R, (b + 1) R), R = ceil(n / 8), of the PUBLIC 32-byte seed's stream,
+    0 at word n, MS_PAD_WORD above (default stride n + 1; ms_stride(n) is the bootstrap workspace's).  No GPU."""
+    stride = n + 1 if stride is None else int(stride)
+    out = np.zeros((int(count), max(stride, 1)), np.uint64)
+    check(load().fhe_oprf_rows_host(_oprf_seed(seed), int(n), int(count), stride, ptr(out)))
+    return out
+
+
+def oprf_lut_host(bits: int, params: FheParams | None = None) -> np.ndarray:
+    """the accumulator polynomial of a `bits`-bit oblivious pseudo-random block (fhe_oprf_lut_host): 2048 words,
+    coefficient i = (2 floor(i 2^bits / 4096) + 1) delta / 2.  No GPU."""
+    p = params if params is not None else default_params()
+    out = np.zeros(2048, np.uint64)
+    check(load().fhe_oprf_lut_host(C.byref(p), int(bits), ptr(out)))
+    return out
+
+
 class Context:
     """One GPU + installed server key (tfhe::set_server_key, src/schnorr.rs:443)."""
 
@@ -609,6 +635,26 @@ class Context:
         """measurement hook (fhe_ctx_time_ms_center): mean ms of one k_ms_center launch over count rows"""
         ms = C.c_float()
         check(load().fhe_ctx_time_ms_center(self._h, int(count), int(n), int(stride), int(reps), C.byref(ms)))
+        return float(ms.value)
+
+    def oprf_rows(self, seed, n: int, count: int, stride=None) -> np.ndarray:
+        """test hook (fhe_oprf_rows): k_oprf_rows over a scratch buffer, returned as oprf_rows_host lays its rows
+        out: (count, stride) words, padding included.  Needs no server key."""
+        stride = n + 1 if stride is None else int(stride)
+        out = np.zeros((int(count), max(stride, 1)), np.uint64)
+        check(load().fhe_oprf_rows(self._h, _oprf_seed(seed), int(n), int(count), stride, ptr(out)))
+        return out
+
+    def oprf_blocks(self, seed, count: int, bits: int) -> np.ndarray:
+        """test hook (fhe_oprf_blocks): the raw (count, 2049) words of blocks 0 .. count - 1 of the seed at `bits`"""
+        out = np.zeros((int(count), BIG_CT), np.uint64)
+        check(load().fhe_oprf_blocks(self._h, _oprf_seed(seed), int(count), int(bits), ptr(out)))
+        return out
+
+    def time_oprf_rows(self, count: int, n: int, reps: int = 30) -> float:
+        """measurement hook (fhe_ctx_time_oprf_rows): mean ms of one k_oprf_rows launch over count workspace rows"""
+        ms = C.c_float()
+        check(load().fhe_ctx_time_oprf_rows(self._h, int(count), int(n), int(reps), C.byref(ms)))
         return float(ms.value)
 
     def set_wide_threshold(self, threshold: int) -> None:

@@ -87,6 +87,34 @@ class FheUint:
         check(load().fhe_radix_trivial(_ctx().handle, ptr(w), bits, C.byref(h)))
         return cls._wrap(h, bits)
 
+    @classmethod
+    def random(cls, seed=None, random_bits=None, bits=None):
+        """tfhe-rs' generate_oblivious_pseudo_random(seed, random_bits) (fhe_radix_random): an encrypted value
+        uniform in [0, 2^random_bits) (default: the whole width) that the server makes by itself on the GPU and
+        only the client-key holder can read.  seed: 32 PUBLIC bytes; the same seed and key give the same words, so
+        a seed serves one call.  None draws OS entropy -- refused under a communicator of more than one rank,
+        where callers derive the seed (rerandomization_seed, ReRandomizationContext.seed)."""
+        bits = bits or cls.BITS
+        h = C.c_void_p()
+        check(load().fhe_radix_random(_ctx().handle, _rerand_seed(seed), bits, bits if random_bits is None else int(random_bits),
+                                      C.byref(h)))
+        return cls._wrap(h, bits)
+
+    @classmethod
+    def random_below(cls, bound: int, seed=None, extra_bits: int = 64, bits=None):
+        """tfhe-rs' generate_oblivious_pseudo_random_bounded (fhe_radix_random_below): an encrypted value in
+        [0, bound), at most 2^-extra_bits from uniform: (m random bits * bound) >> m, m = bit_length(bound - 1) +
+        extra_bits.  Seed rules as random's."""
+        bits = bits or cls.BITS
+        bound = int(bound)
+        if bound < 0:
+            raise ValueError("the bound is a positive integer")
+        w = _words(bound, max(64, (bound.bit_length() + 63) // 64 * 64))
+        h = C.c_void_p()
+        check(load().fhe_radix_random_below(_ctx().handle, _rerand_seed(seed), bits, ptr(w), w.size, int(extra_bits),
+                                            C.byref(h)))
+        return cls._wrap(h, bits)
+
     def decrypt(self, client_key) -> int:
         n = (self.bits + 63) // 64
         w = np.zeros(n, np.uint64)
@@ -295,6 +323,14 @@ class BigUintFHE:
         limbs = np.array(to_u32_digits(value), dtype=np.uint32)
         h = C.c_void_p()
         check(load().fhe_biguint_encrypt(_ctx().handle, client_key.handle, ptr(limbs, C.c_uint32), limbs.size, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def random(cls, bits: int, seed=None):
+        """FheUint.random over bits / 32 digits (fhe_biguint_random; bits a multiple of 32): block i of the whole
+        on row i of the seed"""
+        h = C.c_void_p()
+        check(load().fhe_biguint_random(_ctx().handle, _rerand_seed(seed), int(bits), C.byref(h)))
         return cls(h)
 
     def serialize(self) -> bytes:

@@ -977,6 +977,62 @@ int fhe_ct_digest_rows(fhe_ctx* ctx, const uint64_t* rows, size_t nblocks, uint8
  * on the context's stream; *ms = the mean per launch. */
 int fhe_ctx_time_ct_digest(fhe_ctx* ctx, size_t nblocks, uint32_t reps, float* ms);
 
+/* ------------------------------------------------------------------- oblivious pseudo-random values */
+/* tfhe-rs' FheUint::generate_oblivious_pseudo_random(seed, random_bits) and its bounded form: the server makes
+ * an encrypted uniformly random value by itself, which nobody but the client-key holder can read -- blinding
+ * values, random challenges, masks, without a round trip to the client.  No keyswitch, no upload: a gfx950
+ * kernel writes LWE rows straight into the bootstrap workspace and one blind rotation does the rest.
+ * With n the LWE dimension, N = 2048, delta = 2^63 / (message_modulus carry_modulus), 1 <= bits <=
+ * log2(message_modulus), p = 2^bits:
+ * ROWS         mask word j < n of row b = u64 word j of ChaCha blocks [b R, (b + 1) R), R = ceil(n / 8), of the
+ *              stream (key = the 32 seed bytes, nonce {111, "ROCM", 0}, the seeded ciphertexts' word order); body
+ *              word n = 0; in a layout of `stride` words per row the words above n hold 0xA5A55A5AC3C33C3C.  A row
+ *              starts on a block boundary: the definition depends neither on the stride nor on the row count.
+ * ACCUMULATOR  coefficient i < N = (2 floor(i p / 2N) + 1) delta / 2: no half-box rotation, no negated head.
+ * BLOCK b      = sample extraction of the blind rotation of row b through the accumulator under the installed
+ *              key set, then (p - 1) delta / 2 added to the body.  With m~ = -sum ms(a_i) s_i mod 2N (ms: the blind
+ *              rotation's 12-bit rounding) it encrypts floor(m~ p / 2N) + p / 2 for m~ < N and p / 2 - 1 -
+ *              floor((m~ - N) p / 2N) otherwise: in [0, p), uniform over the stream for a non-zero small key, and
+ *              decided by the rounding alone (the bootstrap's noise does not move the selected coefficient's
+ *              value).  Degree p - 1, noise 1: an ordinary clean block.  The rows are NOT centered and the result
+ *              does not depend on fhe_ctx_set_modulus_switch: the phase is the randomness.
+ * RADIX VALUE  of width_bits with random_bits r <= width_bits: blocks 0 .. floor(r / 2) - 1 at bits = 2 on the rows
+ *              of their index, for an odd r block floor(r / 2) at bits = 1 on its row, trivial zeros above: uniform
+ *              in [0, 2^r).
+ * BOUNDED      random_below(bound, extra_bits): m = bit_length(bound - 1) + extra_bits; the result is
+ *              (the m-bit value of the seed * bound) >> m at the caller's width, at most 2^-extra_bits from uniform
+ *              on [0, bound).  Composed from the cast, the clear multiply and the clear shift of the radix layer.
+ * SEEDS        A seed is PUBLIC.  The same seed, key and bits give the same words (replicas and ranks agree), so
+ *              one seed serves one call; values drawn from one seed at different bits or widths are correlated.
+ *              seed = NULL draws 32 bytes of OS entropy -- refused (FHE_ERR_INVALID) under a communicator of more
+ *              than one rank, as fhe_radix_rerandomize's is: callers there derive the seed (fhe_rerandomize_seed,
+ *              fhe_rerand_context_seed).
+ * Eager: the kernels run on the context's stream behind whatever is launched; recorded but unflushed operations
+ * stay pending.  Under a communicator every rank computes every block (no collective).  Classic and multi-bit
+ * keys, every LWE dimension the key install accepts.  FHE_ERR_NO_KEY without a server key; FHE_ERR_INVALID with a
+ * message for bits, widths or bounds out of range. */
+/* The host definitions; no context, no GPU.  rows: count x stride words, stride >= n + 1, 1 <= n <= 2048, at most
+ * 2^23 rows.  lut: the 2048 accumulator words for `params` and `bits`. */
+int fhe_oprf_rows_host(const uint8_t seed[32], uint32_t n, size_t count, size_t stride, uint64_t* out);
+int fhe_oprf_lut_host(const fhe_params* params, uint32_t bits, uint64_t* out);
+/* Test hook: the row kernel (k_oprf_rows) over a scratch buffer in the bootstrap workspace's layout (n + 1 words
+ * rounded up to 8 per row), each row's first min(stride, that) words copied to `out`, the marker above them.
+ * Needs no server key, so any n runs without a key generation.  Same validation.  Synchronous. */
+int fhe_oprf_rows(fhe_ctx* ctx, const uint8_t seed[32], uint32_t n, size_t count, size_t stride, uint64_t* out);
+/* Measurement hook: the row kernel alone, `reps` launches over `count` workspace rows between two HIP events on
+ * the context's stream; *ms = the mean per launch. */
+int fhe_ctx_time_oprf_rows(fhe_ctx* ctx, size_t count, uint32_t n, uint32_t reps, float* ms);
+/* Test hook: the raw blocks, count x 2049 words, blocks 0 .. count - 1 of the seed at `bits`. */
+int fhe_oprf_blocks(fhe_ctx* ctx, const uint8_t seed[32], size_t count, uint32_t bits, uint64_t* out_words);
+int fhe_radix_random(fhe_ctx* ctx, const uint8_t seed[32] /* NULL: OS entropy */, uint32_t width_bits,
+                     uint32_t random_bits, fhe_radix** out);
+/* bound: nwords little-endian u64 words, > 0, values below it fitting width_bits; FHE_ERR_INVALID when
+ * bit_length(bound - 1) + extra_bits + bit_length(bound) exceeds FHE_RADIX_MAX_BITS */
+int fhe_radix_random_below(fhe_ctx* ctx, const uint8_t seed[32] /* NULL: OS entropy */, uint32_t width_bits,
+                           const uint64_t* bound_words, size_t nwords, uint32_t extra_bits, fhe_radix** out);
+/* BigUintFHE of bits / 32 digits (bits a multiple of 32), block i of the whole on row i */
+int fhe_biguint_random(fhe_ctx* ctx, const uint8_t seed[32] /* NULL: OS entropy */, uint32_t bits, fhe_biguint** out);
+
 /* ------------------------------------------------------------------- Schnorr / BIP-340 */
 /* The caller of the hot path (src/schnorr.rs).  32-byte scalars are big-endian.  The plaintext
  * EC / hash steps run on the host; the FHE block s = k + e*d runs on the GPU engine. */
