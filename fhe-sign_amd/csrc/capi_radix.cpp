@@ -907,6 +907,206 @@ int fhe_columns_decrypt(fhe_ctx* c, const fhe_client_key* ck, const fhe_columns*
 
 void fhe_columns_destroy(fhe_columns* x) { delete x; }
 
+// x mod (2^k_bits - c), c public words: radix_rem_pseudo_mersenne; the result has k_bits bits
+int fhe_radix_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a, uint32_t k_bits, const uint64_t* c_words, size_t nc,
+                                  fhe_radix** out) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!a || !out || !c_words || !nc) {
+        set_error("invalid arguments to fhe_radix_rem_pseudo_mersenne");
+        return FHE_ERR_INVALID;
+    }
+    const BigConst cc = words_of(c_words, nc);
+    return guarded([&] {
+        *out = wrap(radix_rem_pseudo_mersenne(*c->engine, a->r, k_bits, cc), k_bits);
+        return FHE_OK;
+    });
+}
+
+// the same on a column form (fhe_biguint_mul_add_columns, fhe_radix_scalar_mul_add_columns): the first
+// fold reads the columns unpropagated
+int fhe_columns_rem_pseudo_mersenne(fhe_ctx* c, const fhe_columns* x, uint32_t k_bits, const uint64_t* c_words, size_t nc,
+                                    fhe_radix** out) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x || !out || !c_words || !nc) {
+        set_error("invalid arguments to fhe_columns_rem_pseudo_mersenne");
+        return FHE_ERR_INVALID;
+    }
+    const BigConst cc = words_of(c_words, nc);
+    return guarded([&] {
+        *out = wrap(radix_rem_pseudo_mersenne_columns(*c->engine, x->cols, x->nblocks, k_bits, cc), k_bits);
+        return FHE_OK;
+    });
+}
+
+// (k + m a) mod (2^k_bits - c) for public m, k below the modulus, the product reduced as it is formed
+// (radix_scalar_mul_add_rem_pseudo_mersenne)
+int fhe_radix_scalar_mul_add_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a, const uint64_t* m, size_t nm,
+                                                 const uint64_t* k, size_t nk, uint32_t k_bits, const uint64_t* c_words,
+                                                 size_t nc, fhe_radix** out) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!a || !out || !c_words || !nc || (!m && nm) || (!k && nk)) {
+        set_error("invalid arguments to fhe_radix_scalar_mul_add_rem_pseudo_mersenne");
+        return FHE_ERR_INVALID;
+    }
+    const BigConst cc = words_of(c_words, nc), vm = words_of(m, nm), vk = words_of(k, nk);
+    return guarded([&] {
+        *out = wrap(radix_scalar_mul_add_rem_pseudo_mersenne(*c->engine, a->r, vm, vk, k_bits, cc), k_bits);
+        return FHE_OK;
+    });
+}
+
+namespace {
+// a host engine's clean result -> words
+void put_radix_words(Engine& e, const Radix& r, uint64_t* w, size_t nwords) {
+    engine_check(nwords * 64 >= 2 * (size_t)r.nblocks(), "sim: word buffer too small");
+    for (size_t i = 0; i < nwords; ++i) w[i] = 0;
+    for (uint32_t q = 0; q < r.nblocks(); ++q) {
+        const int64_t h2 = e.sim_half2(r.blocks[q]);
+        engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 8, "sim radix: an output block off its digit range");
+        w[q / 32] |= (uint64_t)(h2 / 2) << (2 * (q % 32));
+    }
+}
+void put_schedule(const Engine& e, uint64_t* pbs, uint64_t* levels, uint32_t* level_sizes, size_t cap) {
+    if (pbs) *pbs = e.pbs_count;
+    if (levels) *levels = e.levels;
+    for (size_t i = 0; level_sizes && i < e.level_log.size() && i < cap; ++i) level_sizes[i] = e.level_log[i];
+}
+bool host_width_ok(uint32_t bits) {
+    if (bits >= 2 && bits % 2 == 0 && bits <= FHE_RADIX_MAX_BITS) return true;
+    set_error("operand width must be even and within 2 .. FHE_RADIX_MAX_BITS");
+    return false;
+}
+}  // namespace
+
+// Simulated run (Engine kSim, no GPU, no key) of x mod (2^k_bits - c) on a `bits`-wide operand: out gets
+// the k_bits-wide result (words LSB first, nout >= ceil(k_bits / 64)); *pbs, *levels, *folds optional
+int fhe_host_sim_rem_pseudo_mersenne(uint32_t bits, const uint64_t* x, uint32_t k_bits, const uint64_t* c_words, size_t nc,
+                                     uint64_t* out, size_t nout, uint64_t* pbs, uint64_t* levels, uint32_t* folds) {
+    if (!x || !c_words || !nc || !out) return FHE_ERR_INVALID;
+    if (!host_width_ok(bits)) return FHE_ERR_INVALID;
+    const BigConst cc = words_of(c_words, nc);
+    return guarded([&] {
+        fhe_ctx c;
+        Engine e(&c, Engine::kSim);
+        Radix A;
+        for (uint32_t q = 0; q < bits / 2; ++q) A.blocks.push_back(e.sim_block((uint32_t)(x[q / 32] >> (2 * (q % 32))) & 3u, 3));
+        const Radix R = radix_rem_pseudo_mersenne(e, A, k_bits, cc, folds);
+        e.flush();
+        engine_check(2 * R.nblocks() == k_bits, "sim: the remainder's width is not k");
+        put_radix_words(e, R, out, nout);
+        put_schedule(e, pbs, levels, nullptr, 0);
+        return FHE_OK;
+    });
+}
+
+// Dry run (Engine kDry) of the same: bootstraps, launch levels, level sizes (up to cap), folds, and the
+// recording-order fingerprint (Engine::fingerprint: equal across processes iff the same graph is recorded
+// in the same order)
+int fhe_host_rem_pseudo_mersenne_stats(uint32_t bits, uint32_t k_bits, const uint64_t* c_words, size_t nc, uint64_t* pbs,
+                                       uint64_t* levels, uint32_t* level_sizes, size_t cap, uint32_t* folds,
+                                       uint64_t* fingerprint) {
+    if (!c_words || !nc || !pbs || !levels) return FHE_ERR_INVALID;
+    if (!host_width_ok(bits)) return FHE_ERR_INVALID;
+    const BigConst cc = words_of(c_words, nc);
+    return guarded([&] {
+        fhe_ctx c;
+        Engine e(&c, Engine::kDry);
+        Radix A;
+        for (uint32_t q = 0; q < bits / 2; ++q) A.blocks.push_back(e.dry_block(3));
+        const Radix R = radix_rem_pseudo_mersenne(e, A, k_bits, cc, folds);
+        e.flush();
+        put_schedule(e, pbs, levels, level_sizes, cap);
+        if (fingerprint) *fingerprint = e.fingerprint;
+        return FHE_OK;
+    });
+}
+
+// Simulated (sim != 0, kSim) or dry (kDry; encrypted limbs' values are ignored, their counts matter; public
+// operands are read in both) run of the reduced signer's FHE block: (k + a * b) mod (2^k_bits - c).
+//   mode FHE_COMPAT / FHE_FAST: all three encrypted, biguint_mul_add_columns then the column-form reduction;
+//     cols_out (optional, ncols words) gets the column form's value, *col_bits its width -- what the
+//     unreduced signer decrypts, so out == cols_out mod n whatever carries the compat product lost.
+//   mode FHE_SIGN_PUBLIC_OPERANDS: a and k public, b encrypted, the product reduced as it is formed
+//     (radix_scalar_mul_add_rem_pseudo_mersenne: what fhe_schnorr_eval_s_public records).
+//   mode FHE_SIGN_PUBLIC_OPERANDS | FHE_HOST_MUL_THEN_FOLD: the same operands through the unreduced public
+//     signer's column form (b widened to its exact width) and the column-form reduction: the alternative
+//     the residue form is measured against.
+int fhe_host_biguint_mul_add_rem(int sim, const uint32_t* a, size_t la, const uint32_t* b, size_t lb, const uint32_t* k,
+                                 size_t lk, int mode, uint32_t k_bits, const uint64_t* c_words, size_t nc, uint64_t* out,
+                                 size_t nout, uint64_t* cols_out, size_t ncols, uint32_t* col_bits, uint64_t* pbs,
+                                 uint64_t* levels, uint32_t* level_sizes, size_t cap, uint32_t* folds,
+                                 uint64_t* fingerprint) {
+    const bool then_fold = (mode & FHE_HOST_MUL_THEN_FOLD) != 0;
+    mode &= ~FHE_HOST_MUL_THEN_FOLD;
+    if ((la && !a) || (lb && !b) || (lk && !k) || !c_words || !nc || (sim && !out) ||
+        (mode != kCompat && mode != kFast && mode != FHE_SIGN_PUBLIC_OPERANDS) ||
+        (then_fold && mode != FHE_SIGN_PUBLIC_OPERANDS))
+        return FHE_ERR_INVALID;
+    const BigConst cc = words_of(c_words, nc);
+    return guarded([&] {
+        fhe_ctx c;
+        Engine e(&c, sim ? Engine::kSim : Engine::kDry);
+        auto enc = [&](uint32_t v) { return sim ? e.sim_block(v, 3) : e.dry_block(3); };
+        auto make = [&](const uint32_t* v, size_t n) {
+            BigUint r;
+            for (size_t i = 0; i < n; ++i) {
+                Radix d;
+                for (uint32_t q = 0; q < kLimbBlocks; ++q) d.blocks.push_back(enc((v[i] >> (2 * q)) & 3u));
+                r.digits.push_back(std::move(d));
+            }
+            return r;
+        };
+        auto words = [](const uint32_t* v, size_t n) {
+            BigConst w((n + 1) / 2, 0);
+            for (size_t i = 0; i < n; ++i) w[i / 2] |= (uint64_t)v[i] << (32 * (i % 2));
+            return w;
+        };
+        auto col_value = [&](const std::vector<Blocks>& cols, uint32_t nb) {
+            if (col_bits) *col_bits = 2 * nb;
+            if (!sim || !cols_out) return;
+            engine_check(ncols * 64 >= 2 * (size_t)nb, "sim columns: word buffer too small");
+            column_value(cols, nb, [&](const Block& x) {
+                const int64_t h2 = e.sim_half2(x);
+                engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 32, "sim columns: a block off its message range");
+                return h2 / 2;
+            }, cols_out, ncols);
+        };
+        Radix R;
+        if (mode == FHE_SIGN_PUBLIC_OPERANDS) {
+            const BigUint B = make(b, lb);
+            Radix d;
+            for (const Radix& x : B.digits) d.blocks.insert(d.blocks.end(), x.blocks.begin(), x.blocks.end());
+            if (then_fold) {
+                const uint32_t nb = (uint32_t)(16 * lb + 16 * std::max(la, lk) + 1);
+                engine_check(2 * (uint64_t)nb <= FHE_RADIX_MAX_BITS, "operand width out of range");
+                const Radix dw = radix_resize(d, nb);
+                const std::vector<Blocks> cols =
+                    radix_mul_add_columns(e, dw, radix_trivial(words(a, la), nb), radix_trivial(words(k, lk), nb), nb);
+                R = radix_rem_pseudo_mersenne_columns(e, cols, nb, k_bits, cc, folds);
+                e.flush();
+                col_value(cols, nb);
+            } else {
+                R = radix_scalar_mul_add_rem_pseudo_mersenne(e, d, words(a, la), words(k, lk), k_bits, cc, folds);
+                e.flush();
+            }
+        } else {
+            const BigUint A = make(a, la), B = make(b, lb), K = make(k, lk);
+            uint32_t nb = 0;
+            const std::vector<Blocks> cols = biguint_mul_add_columns(e, A, B, K, mode, &nb);
+            R = radix_rem_pseudo_mersenne_columns(e, cols, nb, k_bits, cc, folds);
+            e.flush();
+            col_value(cols, nb);
+        }
+        if (sim) put_radix_words(e, R, out, nout);
+        put_schedule(e, pbs, levels, level_sizes, cap);
+        if (fingerprint) *fingerprint = e.fingerprint;
+        return FHE_OK;
+    });
+}
+
 // Simulated runs (no GPU, no key; Engine kSim): the operands are "encrypted" blocks whose plaintext
 // the engine shadows on the host, so the algorithms take every encrypted path (no trivial folding)
 // while each bootstrap is evaluated from its LUT and range-checked -- the end-to-end results of the

@@ -3590,4 +3590,387 @@ Radix radix_scalar_rem(Engine& e, const Radix& a, const BigConst& dd) {
     return radix_sub(e, a, qd);
 }
 
+// ============================================================================ pseudo-Mersenne reduction
+// x mod n, n = 2^k - c public.  2^k == c (mod n), so x = L + 4^K H == L + c H (K = k / 2): a fold.  The
+// identity holds for ANY split of the columns at K -- L and H are the column sums below / from K, carries
+// unresolved -- so a fold reads a column form as it is and leaves one: the products' entries (clear digits
+// of c times entries of H, no bootstrap) join L's columns and are only compressed (every column a sum <= 6
+// of <= 3 blocks), never carry-propagated.  A carry propagation costs 7-8 launch levels; a reduction that
+// paid one per fold had more levels than the general division it replaces.
+//
+// Exactness.  Unpropagated columns cannot tell value from value + 4^width, so nothing here is taken mod
+// 4^width: a digit -1 of c's recoding {-1, 0, 1, 2} enters as the complement (deg - y) and the deg it owes
+// is NOT subtracted but accumulated in a public E (the columns sum to L + c H + E exactly, every entry
+// nonnegative).  E joins a public offset, off = sum of the E's mod n, and the last step takes it out again.
+//
+// Fold count.  From a public bound alone, never from data: with x <= B (2^width - 1, or what the columns'
+// degrees give), L <= min(B, its degrees), H <= min(B >> k, its degrees), the next bound is L + H c + E; it
+// shrinks by about k - bitlen(c) bits per fold as long as c < 2^(k-2) (3 c < 2^k: then bound(L) + H c is
+// below B whenever H >= 3).  Folds stop once B + n' < 4 n, n' = (n - off) mod n: U = T + n' == x (mod n) has
+// at most four candidates U - j n.
+//
+// Last step, k + 2 bits.  P_j = T + n' + j c for j < m (m <= 4 candidates), propagated side by side (their
+// levels are shared).  U - j n = P_j - j 2^k, so U >= j n iff the top block of P_j (P_j >> k, at most 3) is
+// >= j, and then U - j n is P_j's low k bits when it is the remainder.  a_j = [top_j >= j] comes out of the
+// propagation's own last level, u = a_1 + .. + a_(m-1) is the number of subtractions, and one select reads
+// block i of P_u: k / 2 clean blocks.  For T < 2 n and off = 0 (an operand no wider than k + 1 bits) this is
+// the textbook single conditional subtraction.
+//
+// Every bootstrap is a column compression, a carry state / prefix or a select of the existing machinery,
+// the clear digits riding in the fused linear prologue; no kernel of its own.
+namespace {
+BigConst big_shr(const BigConst& v, uint32_t s) {
+    BigConst r;
+    for (size_t w = s / 64; w < v.size(); ++w) {
+        uint64_t x = v[w] >> (s % 64);
+        if (s % 64 && w + 1 < v.size()) x |= v[w + 1] << (64 - s % 64);
+        r.push_back(x);
+    }
+    return big_norm(r);
+}
+BigConst big_min(const BigConst& a, const BigConst& b) { return big_cmp(a, b) <= 0 ? a : b; }
+BigConst big_mod(const BigConst& a, const BigConst& n) {
+    if (big_cmp(a, n) < 0) return big_norm(a);
+    BigConst r = a;
+    big_sub_inplace(r, big_mul(big_div(a, n), n));
+    return big_norm(r);
+}
+// sum_q v[q] 4^q for nonnegative v
+BigConst big_from_digits(const std::vector<int64_t>& v) {
+    BigConst D;
+    auto shl2 = [](const BigConst& x) { return big_add(big_add(x, x), big_add(x, x)); };
+    for (size_t q = v.size(); q-- > 0;) D = big_add(shl2(D), BigConst{(uint64_t)v[q]});
+    return big_norm(D);
+}
+// sum_{j in [from, to)} degree(cols[j]) 4^(j - from)
+BigConst degree_bound(const std::vector<Blocks>& cols, uint32_t from, uint32_t to) {
+    std::vector<int64_t> d;
+    for (uint32_t j = from; j < to && j < cols.size(); ++j) d.push_back(col_degree(cols[j]));
+    return big_from_digits(d);
+}
+uint32_t blocks_for(const BigConst& bound) { return std::max<uint32_t>(1, (big_bitlen(bound) + 1) / 2); }
+bool live(const Block& b) { return !(b.trivial() && b.value == 0); }
+// every column at most one clean block
+bool columns_clean(const std::vector<Blocks>& cols) {
+    for (const Blocks& c : cols) {
+        uint32_t n = 0;
+        for (const Block& b : c)
+            if (live(b)) {
+                ++n;
+                if (b.lazy() || b.degree > 3 || b.noise > 1) return false;
+            }
+        if (n > 1) return false;
+    }
+    return true;
+}
+// cols[0, n) as one clean block per position: as they are when they already are, else one propagation
+// (exact when the columns' value is below 4^n; wrapping at n otherwise)
+Radix normalize_columns(Engine& e, std::vector<Blocks> cols, uint32_t n) {
+    cols.resize(n);
+    if (!columns_clean(cols)) return radix_propagate_columns(e, std::move(cols), n);
+    Radix r;
+    r.blocks.assign(n, Block::make_trivial(0));
+    for (uint32_t k = 0; k < n; ++k)
+        for (const Block& b : cols[k])
+            if (live(b)) r.blocks[k] = b;
+    return r;
+}
+void compress_only(Engine& e, std::vector<Blocks>& cols) {
+    ColProblem P;
+    P.nblocks = (uint32_t)cols.size();
+    P.cols = std::move(cols);
+    std::vector<ColProblem*> ptrs{&P};
+    compress_columns(e, ptrs);
+    cols = std::move(P.cols);
+}
+struct PmModulus {
+    uint32_t k_bits, K;
+    BigConst c, n, n4;
+    std::vector<int32_t> t;  // c's base-4 digits recoded to {-1, 0, 1, 2}, one more than c has
+    BigConst s_neg;          // sum of 4^q over the digits -1
+};
+PmModulus pm_modulus(uint32_t k_bits, const BigConst& cc) {
+    PmModulus m;
+    engine_check(k_bits % 2 == 0 && k_bits >= 2 && k_bits + 2 <= FHE_RADIX_MAX_BITS,
+                 "pseudo-Mersenne reduction: k must be even, 2 <= k <= FHE_RADIX_MAX_BITS - 2");
+    m.k_bits = k_bits;
+    m.K = k_bits / 2;
+    m.c = big_norm(cc);
+    engine_check(!m.c.empty(), "pseudo-Mersenne reduction: c must be positive");
+    engine_check(big_bitlen(m.c) + 2 <= k_bits, "pseudo-Mersenne reduction: c must be below 2^(k - 2)");
+    m.n = big_pow2(k_bits);
+    big_sub_inplace(m.n, m.c);
+    m.n = big_norm(m.n);
+    m.n4 = big_add(big_add(m.n, m.n), big_add(m.n, m.n));
+    int32_t carry = 0;
+    for (uint32_t q = 0, nd = (big_bitlen(m.c) + 1) / 2; q <= nd; ++q) {
+        int32_t v = (q < nd ? (int32_t)((m.c[(2 * q) / 64] >> ((2 * q) % 64)) & 3u) : 0) + carry;
+        carry = 0;
+        if (v >= 3) {
+            v -= 4;
+            carry = 1;
+        }
+        m.t.push_back(v);
+    }
+    std::vector<int64_t> neg;
+    for (int32_t v : m.t) neg.push_back(v < 0 ? 1 : 0);
+    m.s_neg = big_from_digits(neg);
+    return m;
+}
+// an entry of a high column that the clear digits can scale as it is: 2 y and deg - y stay inside a
+// lookup's input range and noise budget
+bool foldable(const Block& b) { return b.trivial() || (b.degree <= 7 && b.noise <= 6); }
+// t y as a column entry, t in {1, 2}
+Block scaled(const Block& y, int32_t t) {
+    if (t == 1) return y;
+    if (!y.lazy()) return block_lazy({{y, t}}, 0, (uint32_t)t * y.degree);
+    std::vector<Term> u;
+    for (const Term& x : *y.lin) u.push_back({x.b, x.coef * t});
+    return block_lazy(u, t * y.lin_cst, (uint32_t)t * y.degree);
+}
+// out[p + q] += t_q * (entries of hcols[p]) for c's recoded digits t_q: exact and nonnegative, the deg each
+// complement owes summed into *owed (digits: sum owed[j] 4^j = E)
+void pm_products(const PmModulus& M, const std::vector<Blocks>& hcols, std::vector<Blocks>& out,
+                 std::vector<int64_t>& owed) {
+    std::vector<int64_t> pos(out.size() + 1, 0);  // public nonnegative parts
+    owed.assign(out.size(), 0);
+    for (uint32_t p = 0; p < hcols.size(); ++p)
+        for (const Block& y : hcols[p]) {
+            if (!live(y)) continue;
+            for (uint32_t q = 0; q < M.t.size(); ++q) {
+                const int32_t t = M.t[q];
+                if (t == 0) continue;
+                engine_check(p + q < out.size(), "pseudo-Mersenne fold: a product entry beyond its columns");
+                if (y.trivial()) {
+                    (t > 0 ? pos : owed)[p + q] += (int64_t)std::abs(t) * y.value;
+                } else if (t > 0) {
+                    out[p + q].push_back(scaled(y, t));
+                } else {
+                    int64_t kc = 0;
+                    push_signed(out[p + q], kc, y, -1);
+                    owed[p + q] -= kc;
+                }
+            }
+        }
+    for (size_t j = 0; j < out.size(); ++j) {
+        pos[j + 1] += pos[j] / 4;
+        if (pos[j] % 4) out[j].push_back(Block::make_trivial((uint32_t)(pos[j] % 4)));
+    }
+    engine_check(pos[out.size()] == 0, "pseudo-Mersenne fold: public part beyond its columns");
+}
+
+// cols (nblocks positions) hold x + off0 (off0 a public residue mod n; exact: the column sum itself, else
+// the sum mod 4^nblocks) -> x mod n
+Radix pm_reduce(Engine& e, const PmModulus& M, std::vector<Blocks> cols, uint32_t nblocks, bool exact, BigConst off,
+                uint32_t* folds) {
+    engine_check(nblocks >= 1 && 2 * (uint64_t)nblocks <= FHE_RADIX_MAX_BITS,
+                 "pseudo-Mersenne reduction: operand width out of range");
+    const uint32_t K = M.K, k_bits = M.k_bits;
+    cols.resize(nblocks);
+    BigConst B = degree_bound(cols, 0, nblocks);
+    if (!exact && big_bitlen(B) > 2 * nblocks) {
+        // the columns could reach 4^nblocks, where their value wraps: the wrap is part of the value, so it
+        // is resolved (one propagation at nblocks) before anything is folded
+        const Radix r = radix_propagate_columns(e, std::move(cols), nblocks);
+        cols.assign(nblocks, {});
+        for (uint32_t j = 0; j < nblocks; ++j) cols[j] = {r.blocks[j]};
+        B = degree_bound(cols, 0, nblocks);
+    } else {
+        compress_only(e, cols);  // nothing to do for a radix integer or a compressed column form
+        B = big_min(B, degree_bound(cols, 0, nblocks));
+    }
+    auto residue = [&] {  // n' = (n - off) mod n
+        BigConst r = M.n;
+        if (off.empty()) return BigConst{};
+        big_sub_inplace(r, off);
+        return big_norm(r);
+    };
+    constexpr uint32_t kLazyHighMax = 96;  // high parts up to this many columns are folded entry by entry
+    uint32_t nf = 0;
+    while (big_cmp(big_add(B, residue()), M.n4) >= 0) {
+        engine_check(++nf <= 2 * FHE_RADIX_MAX_BITS, "pseudo-Mersenne reduction: the fold bound does not shrink");
+        const uint32_t w = (uint32_t)cols.size();
+        engine_check(w > K, "pseudo-Mersenne reduction: nothing above 2^k to fold");
+        const BigConst BL = big_min(B, degree_bound(cols, 0, K));
+        const BigConst BH = big_min(big_shr(B, k_bits), degree_bound(cols, K, w));
+        std::vector<Blocks> hcols(cols.begin() + K, cols.end());
+        // the high part entry by entry where every entry can take the digits as it is (a compressed column
+        // holds up to 3: that many times the product entries, against the 7 levels of a propagation);
+        // a wide or unbootstrapped high part (the signer's columns) is normalized first, alone
+        bool lazy_ok = hcols.size() <= kLazyHighMax || columns_clean(hcols);
+        for (const Blocks& c : hcols)
+            for (const Block& b : c) lazy_ok = lazy_ok && foldable(b);
+        const uint32_t hb = blocks_for(BH);
+        // what the complements will owe: (the high part's degrees) x (the weights of c's digits -1)
+        BigConst high_deg = degree_bound(hcols, 0, (uint32_t)hcols.size());
+        if (!lazy_ok) {
+            high_deg = big_pow2(2 * hb);
+            big_sub_inplace(high_deg, BigConst{1});
+        }
+        const BigConst e_est = big_mul(high_deg, M.s_neg);
+        const BigConst b_est = big_norm(big_add(big_add(BL, big_mul(BH, M.c)), e_est));
+        BigConst np_est = big_mod(big_add(off, e_est), M.n);
+        if (!np_est.empty()) {
+            BigConst r = M.n;
+            big_sub_inplace(r, np_est);
+            np_est = big_norm(r);
+        }
+        BigConst b16 = b_est;
+        for (int i = 0; i < 4; ++i) b16 = big_add(b16, b16);
+        const bool unpropagated = big_cmp(b_est, B) < 0 &&
+                                  (big_cmp(big_add(b_est, np_est), M.n4) < 0 || big_cmp(b16, B) <= 0);
+        if (!unpropagated) {
+            // Close to 2^k the unpropagated form stops paying: its low part is bounded by its degrees (about
+            // 2 x 2^k) and the complements' E does not shrink with the value (small moduli, c near 2^(k-2)).
+            // The textbook fold instead: everything propagated, (2^k - 1) + (B >> k) c, which reaches 2 n.
+            const Radix T = normalize_columns(e, std::move(cols), blocks_for(B));
+            BigConst low = big_pow2(k_bits);
+            big_sub_inplace(low, BigConst{1});
+            const BigConst nB = big_norm(big_add(big_min(B, low), big_mul(big_shr(B, k_bits), M.c)));
+            engine_check(big_cmp(nB, B) < 0, "pseudo-Mersenne reduction: the fold bound does not shrink");
+            Radix H, C = radix_trivial(M.c, (big_bitlen(M.c) + 1) / 2);
+            if (T.nblocks() > K) H.blocks.assign(T.blocks.begin() + K, T.blocks.end());
+            const uint32_t nb = blocks_for(nB);
+            std::vector<ColProblem> probs = mul_problems(e, {{&H, &C}}, nb, {}, false);
+            for (uint32_t j = 0; j < K && j < nb && j < T.nblocks(); ++j) probs[0].cols[j].push_back(T.blocks[j]);
+            const Radix T2 = propagate_many(e, probs)[0];
+            cols.assign(nb, {});
+            for (uint32_t j = 0; j < nb; ++j) cols[j] = {T2.blocks[j]};
+            B = big_min(nB, degree_bound(cols, 0, nb));
+            continue;
+        }
+        if (!lazy_ok) {
+            const Radix H = normalize_columns(e, std::move(hcols), hb);
+            hcols.assign(hb, {});
+            for (uint32_t j = 0; j < hb; ++j) hcols[j] = {H.blocks[j]};
+        }
+        while (!hcols.empty() && !col_live(hcols.back())) hcols.pop_back();
+        // columns: enough for every entry's position (a complement may sit above the value's own width)
+        std::vector<Blocks> out(std::max<uint32_t>(K, (uint32_t)(hcols.size() + M.t.size())));
+        std::vector<int64_t> owed;
+        pm_products(M, hcols, out, owed);
+        const BigConst E = big_from_digits(owed);
+        const BigConst nB = big_norm(big_add(big_add(BL, big_mul(BH, M.c)), E));
+        engine_check(big_cmp(nB, b_est) <= 0 && big_cmp(nB, B) < 0, "pseudo-Mersenne reduction: the fold bound does not shrink");
+        out.resize(std::max<size_t>(out.size(), blocks_for(nB)));
+        for (uint32_t j = 0; j < K; ++j) out[j].insert(out[j].end(), cols[j].begin(), cols[j].end());
+        compress_only(e, out);
+        cols = std::move(out);
+        B = nB;
+        off = big_mod(big_add(off, E), M.n);
+    }
+    if (folds) *folds = nf;
+    // U = T + n' < 4 n: m candidates U - j n
+    const BigConst np = residue();
+    const BigConst umax = big_add(B, np);
+    uint32_t m = 1;
+    for (BigConst jn = M.n; big_cmp(umax, jn) >= 0; jn = big_add(jn, M.n)) ++m;
+    engine_check(m <= 4, "pseudo-Mersenne reduction: more than four candidates");
+    cols.resize(K + 1);  // B < 4 n < 4^(K + 1) and no entry is negative: whatever sits above holds zero
+    if (m == 1 && np.empty()) return normalize_columns(e, std::move(cols), K);
+    std::vector<ColProblem> probs(m);
+    BigConst add = np;
+    for (uint32_t j = 0; j < m; ++j, add = big_add(add, M.c)) {
+        probs[j].nblocks = K + 1;
+        probs[j].cols = cols;
+        const Radix A = radix_trivial(add, K + 1);
+        for (uint32_t i = 0; i <= K; ++i)
+            if (A.blocks[i].value) probs[j].cols[i].push_back(A.blocks[i]);
+    }
+    const std::vector<Blocks> car = propagate_carries(e, probs);
+    std::vector<PbsItem> items;
+    for (uint32_t j = 0; j < m; ++j) {
+        final_items(probs[j], car[j], K, items);
+        if (j == 0) continue;
+        PbsItem top;  // a_j = [P_j >> k >= j]
+        for (const Block& b : probs[j].cols[K]) top.terms.push_back({b, 1});
+        if (K > 0) top.terms.push_back({car[j][K - 1], 1});
+        top.table = lut1([j](uint32_t v) { return v >= j ? 1u : 0u; });
+        items.push_back(top);
+    }
+    Blocks outs = e.run(items);
+    std::vector<Blocks> P(m);
+    Blocks a;
+    size_t o = 0;
+    for (uint32_t j = 0; j < m; ++j) {
+        P[j].assign(outs.begin() + o, outs.begin() + o + K);
+        o += K;
+        if (j > 0) a.push_back(outs[o++]);
+    }
+    Radix res;
+    if (m == 1) {
+        res.blocks = P[0];
+        return res;
+    }
+    Block u = a[0];
+    if (m > 2) {  // the number of subtractions as one clean block
+        PbsItem it;
+        for (const Block& b : a) it.terms.push_back({b, 1});
+        it.table = lut1([](uint32_t v) { return v & 3; });
+        std::vector<PbsItem> one{it};
+        u = e.run(one)[0];
+    }
+    std::vector<PbsItem> halves;
+    for (uint32_t i = 0; i < K; ++i)
+        for (uint32_t j = 0; j < m; ++j) halves.push_back(item2(u, P[j][i], lut2([j](uint32_t s, uint32_t v) { return s == j ? v : 0u; })));
+    Blocks h = e.run(halves);
+    std::vector<PbsItem> fin;
+    for (uint32_t i = 0; i < K; ++i) {
+        PbsItem it;
+        for (uint32_t j = 0; j < m; ++j) it.terms.push_back({h[(size_t)i * m + j], 1});
+        it.table = LUT_MOD4();
+        fin.push_back(it);
+    }
+    res.blocks = e.run(fin);
+    for (Block& b : res.blocks) b.degree = std::min<uint32_t>(b.degree, 3);
+    return res;
+}
+}  // namespace
+
+Radix radix_rem_pseudo_mersenne_columns(Engine& e, const std::vector<Blocks>& cols_in, uint32_t nblocks, uint32_t k_bits,
+                                        const BigConst& cc, uint32_t* folds) {
+    const PmModulus M = pm_modulus(k_bits, cc);
+    std::vector<Blocks> cols(cols_in.begin(), cols_in.begin() + std::min<size_t>(cols_in.size(), nblocks));
+    return pm_reduce(e, M, std::move(cols), nblocks, false, {}, folds);
+}
+
+Radix radix_rem_pseudo_mersenne(Engine& e, const Radix& a, uint32_t k_bits, const BigConst& c, uint32_t* folds) {
+    std::vector<Blocks> cols(a.nblocks());
+    for (uint32_t j = 0; j < a.nblocks(); ++j) {
+        engine_check(!a.blocks[j].lazy() && a.blocks[j].degree <= 3, "pseudo-Mersenne reduction needs clean operands");
+        cols[j] = {a.blocks[j]};
+    }
+    return radix_rem_pseudo_mersenne_columns(e, cols, a.nblocks(), k_bits, c, folds);
+}
+
+Radix radix_scalar_mul_add_rem_pseudo_mersenne(Engine& e, const Radix& d, const BigConst& m, const BigConst& k,
+                                               uint32_t k_bits, const BigConst& c, uint32_t* folds) {
+    const PmModulus M = pm_modulus(k_bits, c);
+    engine_check(big_cmp(big_norm(m), M.n) < 0 && big_cmp(big_norm(k), M.n) < 0,
+                 "pseudo-Mersenne multiply-add: the clear operands must be below the modulus");
+    // r_i = m 4^i mod n; m d == sum_i d_i r_i (mod n), every summand below 3 n
+    const uint32_t nd = d.nblocks();
+    std::vector<BigConst> R(nd);
+    BigConst r = big_norm(m);
+    for (uint32_t i = 0; i < nd; ++i) {
+        R[i] = r;
+        r = big_add(big_add(r, r), big_add(r, r));
+        while (big_cmp(r, M.n) >= 0) big_sub_inplace(r, M.n);
+        r = big_norm(r);
+    }
+    // exact columns (const_products' excess form: the recoded digits' -3's left out and returned in E)
+    // positions 0 .. K (a residue's digits and its recoding carry), each the sum of at most nd entries <= 6
+    const uint32_t nb = M.K + 2 + blocks_for(BigConst{8ull * nd});
+    engine_check(2 * (uint64_t)nb <= FHE_RADIX_MAX_BITS && nd < (1u << 12),
+                 "pseudo-Mersenne multiply-add: operand width out of range");
+    std::vector<Blocks> cols(nb);
+    BigConst E;
+    const_products(d, R, nb, cols, true, &E);
+    const Radix tk = radix_trivial(k, nb);
+    for (uint32_t j = 0; j < nb; ++j)
+        if (tk.blocks[j].value) cols[j].push_back(tk.blocks[j]);
+    return pm_reduce(e, M, std::move(cols), nb, true, big_mod(E, M.n), folds);
+}
+
+
 }  // namespace fhe

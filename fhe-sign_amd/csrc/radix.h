@@ -433,6 +433,26 @@ Radix radix_scalar_mul_add(Engine& e, const Radix& a, const BigConst& m, const B
 // floor(a / d) and a mod d for a clear divisor d != 0 of any width (Granlund-Montgomery multiply)
 Radix radix_scalar_div(Engine& e, const Radix& a, const BigConst& d);
 Radix radix_scalar_rem(Engine& e, const Radix& a, const BigConst& d);
+// x mod (2^k_bits - c) for a public pseudo-Mersenne modulus (k_bits even, 2 <= k_bits <= FHE_RADIX_MAX_BITS
+// - 2, 0 < c < 2^(k_bits - 2); anything else throws), x of any width: folds x <- (x mod 2^k) + (x >> k) c,
+// each a clear-scalar multiply-add of the shrinking high part that reads and leaves unpropagated columns,
+// their number fixed from a public bound on x (2^width - 1, or what the blocks' degrees give); then, at
+// k + 2 bits, the up to four candidates T - j n propagated side by side and one select (radix.cpp has the
+// bound and the exactness argument).  k_bits / 2 clean blocks.  The recording depends on (width, k, c,
+// degrees) only.  *folds (optional): the number of folds taken.
+Radix radix_rem_pseudo_mersenne(Engine& e, const Radix& a, uint32_t k_bits, const BigConst& c, uint32_t* folds = nullptr);
+// The same on a column form (radix_mul_add_columns, biguint_mul_add_columns: value = sum_j sum cols[j] 4^j
+// mod 4^nblocks).  The fold is linear, so the first one reads the columns as they are: the columns below
+// k_bits / 2 join the fold's own columns unpropagated; a wide or unbootstrapped high part (the signer's) is
+// normalized on its own, at half the width, before it meets c.  Columns whose degrees could reach
+// 4^nblocks are propagated first (the wrap is part of the value).
+Radix radix_rem_pseudo_mersenne_columns(Engine& e, const std::vector<Blocks>& cols, uint32_t nblocks, uint32_t k_bits,
+                                        const BigConst& c, uint32_t* folds = nullptr);
+// Enc(d) (clean blocks) and clear 256-bit-style words e, k -> (k + e d) mod (2^k_bits - c) without ever
+// forming e d: sum_i d_i (e 4^i mod n) + k in columns (every entry a clear multiple of a block of d), then
+// radix_rem_pseudo_mersenne_columns' few-block fold.  e, k < n.
+Radix radix_scalar_mul_add_rem_pseudo_mersenne(Engine& e, const Radix& d, const BigConst& m, const BigConst& k,
+                                               uint32_t k_bits, const BigConst& c, uint32_t* folds = nullptr);
 inline Radix radix_scalar_and(Engine& e, const Radix& a, uint64_t mask) { return radix_scalar_and(e, a, BigConst{mask}); }
 inline Radix radix_scalar_add(Engine& e, const Radix& a, uint64_t s) { return radix_scalar_add(e, a, BigConst{s}); }
 inline Radix radix_scalar_mul(Engine& e, const Radix& a, uint64_t s) { return radix_scalar_mul(e, a, BigConst{s}); }

@@ -420,13 +420,37 @@ struct SignJob {
     SignCore c;
     fhe_biguint *e_fhe = nullptr, *k_fhe = nullptr;
     fhe_columns* s_cols = nullptr;  // s_without_mod in column form
+    fhe_radix* s_red = nullptr;     // reduced: Enc(s_without_mod mod n), 256 bits
+    bool reduced = false;
     uint32_t bits = 0;
     ~SignJob() {
         fhe_biguint_destroy(e_fhe);
         fhe_biguint_destroy(k_fhe);
         fhe_columns_destroy(s_cols);
+        fhe_radix_destroy(s_red);
     }
 };
+
+// n = 2^256 - kNC: the curve order as a pseudo-Mersenne modulus (fhe_radix_rem_pseudo_mersenne)
+const uint64_t kNC[3] = {0x402DA1732FC9BEBFull, 0x4551231950B75FC4ull, 0x1ull};
+
+// Enc((k + e d') mod n) for clear e, k < n: the product is reduced as it is formed (sum of d'_i (e 4^i mod n),
+// then a few-block fold) -- 128 x 128 digit entries and one short fold where multiply-then-fold pays the same
+// entries and three folds on top (dry schedules: DESIGN 6j)
+int eval_s_public(fhe_ctx* ctx, const U256& e, const U256& k, const fhe_biguint* privkey_fhe, fhe_radix** s) {
+    size_t L = 0;
+    int rc = fhe_biguint_len(privkey_fhe, &L);
+    if (rc) return rc;
+    if (L == 0 || 32 * L > FHE_RADIX_MAX_BITS) {
+        set_error("privkey_fhe must have between 1 and FHE_RADIX_MAX_BITS / 32 limbs");
+        return FHE_ERR_INVALID;
+    }
+    fhe_radix* d = nullptr;
+    rc = fhe_biguint_to_radix(privkey_fhe, (uint32_t)(32 * L), &d);
+    if (!rc) rc = fhe_radix_scalar_mul_add_rem_pseudo_mersenne(ctx, d, e.w, 4, k.w, 4, 256, kNC, 3, s);
+    fhe_radix_destroy(d);
+    return rc;
+}
 
 // plaintext prologue and the client-side encryptions (uploads) of e and k
 int sign_prepare(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
@@ -453,6 +477,7 @@ int sign_prepare(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t le
 int sign_begin(fhe_ctx* ctx, const fhe_biguint* privkey_fhe, int mode, SignJob* j) {
     const SignCore& c = j->c;
     int rc = FHE_OK;
+    if (mode == FHE_SIGN_PUBLIC_OPERANDS && j->reduced) return eval_s_public(ctx, c.e, c.k, privkey_fhe, &j->s_red);
     if (mode == FHE_SIGN_PUBLIC_OPERANDS) {
         // s = e * Enc(d') + k with e, k clear: one radix wide enough for the exact value
         // (d' < 2^(32 L), e, k < 2^256  =>  s < 2^(32 L + 257))
@@ -473,12 +498,29 @@ int sign_begin(fhe_ctx* ctx, const fhe_biguint* privkey_fhe, int mode, SignJob* 
     }
     // FHE block (src/schnorr.rs:272-276): k_fhe + e_fhe * privkey_fhe as one schedule (limbs
     // identical to the reference's mul, then add)
-    return fhe_biguint_mul_add_columns(ctx, j->e_fhe, privkey_fhe, j->k_fhe, mode, &j->s_cols);
+    rc = fhe_biguint_mul_add_columns(ctx, j->e_fhe, privkey_fhe, j->k_fhe, mode, &j->s_cols);
+    // reduced: the folds read the column form as it is; what is decrypted is s itself
+    if (!rc && j->reduced) rc = fhe_columns_rem_pseudo_mersenne(ctx, j->s_cols, 256, kNC, 3, &j->s_red);
+    return rc;
 }
 
 int sign_end(fhe_ctx* ctx, fhe_client_key* ck, SignJob* j, uint8_t sig[64]) {
     std::vector<uint32_t> limbs;
     int rc = FHE_OK;
+    if (j->reduced) {
+        // the only plaintext of the call: s, the second half of the signature.  No host % n: a value that is
+        // not below n means the reduction went wrong, and is an error, never something to repair here
+        U256 s;
+        rc = fhe_radix_decrypt(ctx, ck, j->s_red, s.w, 4);
+        if (rc) return rc;
+        if (cmp(s, kN) >= 0) {
+            set_error("reduced signer: the decrypted s is not below the curve order");
+            return FHE_ERR_INVALID;
+        }
+        j->c.r.x.to_be(sig);
+        s.to_be(sig + 32);
+        return FHE_OK;
+    }
     {
         uint32_t bits = 0;
         fhe_columns_bits(j->s_cols, &bits);
@@ -507,13 +549,14 @@ int sign_end(fhe_ctx* ctx, fhe_client_key* ck, SignJob* j, uint8_t sig[64]) {
 
 extern "C" {
 
-// Schnorr::sign_fhe_with_k0 (src/schnorr.rs:235-290)
-int fhe_schnorr_sign_fhe_with_k0(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
-                                 const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, uint8_t sig[64]) {
+// one signature, unreduced (the reference's block) or reduced
+static int sign_one(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
+                    const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, bool reduced, uint8_t sig[64]) {
     if (!sig) return FHE_ERR_INVALID;
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     SignJob j;
+    j.reduced = reduced;
     // e and k are encrypted on a helper thread while sign_begin records the FHE block; their upload
     // lands right before the block's first launch
     int rc = sign_prepare(ctx, ck, msg, len, k0, privkey, privkey_fhe, mode, &j, true);
@@ -529,12 +572,51 @@ int fhe_schnorr_sign_fhe_with_k0(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t
     return rc;
 }
 
+// Schnorr::sign_fhe_with_k0 (src/schnorr.rs:235-290)
+int fhe_schnorr_sign_fhe_with_k0(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
+                                 const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, uint8_t sig[64]) {
+    return sign_one(ctx, ck, msg, len, k0, privkey, privkey_fhe, mode, false, sig);
+}
+
+// The same signature with s reduced mod n under encryption (fhe_columns_rem_pseudo_mersenne on the column
+// form; the public-operand mode reduces the product as it is formed): the call decrypts 256 bits, exactly
+// s, instead of the 513-bit k + e d' from which d' follows by one division.  No host % n on this path.
+int fhe_schnorr_sign_fhe_with_k0_reduced(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len,
+                                         const uint8_t k0[32], const uint8_t privkey[32], const fhe_biguint* privkey_fhe,
+                                         int mode, uint8_t sig[64]) {
+    return sign_one(ctx, ck, msg, len, k0, privkey, privkey_fhe, mode, true, sig);
+}
+
+// The server's half alone: Enc((k + e d') mod n) from Enc(e), Enc(k), Enc(d'); no client key in sight
+int fhe_schnorr_eval_s(fhe_ctx* ctx, const fhe_biguint* e_fhe, const fhe_biguint* k_fhe, const fhe_biguint* privkey_fhe,
+                       int mode, fhe_radix** s) {
+    if (!ctx || !e_fhe || !k_fhe || !privkey_fhe || !s || (mode != FHE_BIGUINT_COMPAT && mode != FHE_BIGUINT_FAST)) {
+        set_error("invalid arguments to fhe_schnorr_eval_s (mode: FHE_BIGUINT_COMPAT or FHE_BIGUINT_FAST)");
+        return FHE_ERR_INVALID;
+    }
+    fhe_columns* cols = nullptr;
+    int rc = fhe_biguint_mul_add_columns(ctx, e_fhe, privkey_fhe, k_fhe, mode, &cols);
+    if (!rc) rc = fhe_columns_rem_pseudo_mersenne(ctx, cols, 256, kNC, 3, s);
+    fhe_columns_destroy(cols);
+    return rc;
+}
+
+// ... with e and k in the clear (32 bytes big-endian each, both below n)
+int fhe_schnorr_eval_s_public(fhe_ctx* ctx, const uint8_t e[32], const uint8_t k[32], const fhe_biguint* privkey_fhe,
+                              fhe_radix** s) {
+    if (!ctx || !e || !k || !privkey_fhe || !s) {
+        set_error("null argument to fhe_schnorr_eval_s_public");
+        return FHE_ERR_INVALID;
+    }
+    return eval_s_public(ctx, U256::from_be(e), U256::from_be(k), privkey_fhe, s);
+}
+
 // sign_fhe_with_k0 on a re-randomized privkey_fhe, the seed bound to (domain, r_x || pubkey_x || msg, the
 // ciphertext's own digest).  The re-randomization is complete before the signing path starts: no deferred
 // encryption is in flight while it can fail, and the signing path joins its helper thread as the call above does.
-int fhe_schnorr_sign_fhe_with_k0_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
-                                        const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode,
-                                        const uint8_t* domain, size_t domain_len, uint8_t sig[64]) {
+static int sign_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
+                       const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, const uint8_t* domain,
+                       size_t domain_len, bool reduced, uint8_t sig[64]) {
     if (!ctx || !ck || (len && !msg) || !k0 || !privkey || !privkey_fhe || (domain_len && !domain) || !sig) {
         set_error("null argument to fhe_schnorr_sign_fhe_with_k0_rerand");
         return FHE_ERR_INVALID;
@@ -560,18 +642,33 @@ int fhe_schnorr_sign_fhe_with_k0_rerand(fhe_ctx* ctx, fhe_client_key* ck, const 
     if (!r) r = fhe_biguint_rerandomize(ctx, privkey_fhe, seed, &fresh);
     for (volatile uint8_t& b : seed) b = 0;  // used for this call, kept nowhere
     fhe_rerand_context_destroy(rc);
-    if (!r) r = fhe_schnorr_sign_fhe_with_k0(ctx, ck, msg, len, k0, privkey, fresh, mode, sig);
+    if (!r) r = sign_one(ctx, ck, msg, len, k0, privkey, fresh, mode, reduced, sig);
     fhe_biguint_destroy(fresh);
     return r;
 }
 
+int fhe_schnorr_sign_fhe_with_k0_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
+                                        const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode,
+                                        const uint8_t* domain, size_t domain_len, uint8_t sig[64]) {
+    return sign_rerand(ctx, ck, msg, len, k0, privkey, privkey_fhe, mode, domain, domain_len, false, sig);
+}
+
+// the two together: a re-randomized privkey_fhe, and s reduced before it is decrypted
+int fhe_schnorr_sign_fhe_with_k0_rerand_reduced(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len,
+                                                const uint8_t k0[32], const uint8_t privkey[32],
+                                                const fhe_biguint* privkey_fhe, int mode, const uint8_t* domain,
+                                                size_t domain_len, uint8_t sig[64]) {
+    return sign_rerand(ctx, ck, msg, len, k0, privkey, privkey_fhe, mode, domain, domain_len, true, sig);
+}
+
 // A batch of independent sign_fhe_with_k0 calls run as one engine schedule (their bootstraps share
 // launch levels); signature i is byte-identical to the single call's.
-int fhe_schnorr_sign_fhe_with_k0_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint8_t* const* msgs,
-                                       const size_t* lens, const uint8_t* k0s, const uint8_t* privkeys,
-                                       const fhe_biguint* const* privkeys_fhe, int mode, uint8_t* sigs) {
+static int sign_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint8_t* const* msgs, const size_t* lens,
+                      const uint8_t* k0s, const uint8_t* privkeys, const fhe_biguint* const* privkeys_fhe, int mode,
+                      bool reduced, uint8_t* sigs) {
     if (count && (!msgs || !lens || !k0s || !privkeys || !privkeys_fhe || !sigs)) return FHE_ERR_INVALID;
     std::vector<SignJob> jobs(count);
+    for (SignJob& j : jobs) j.reduced = reduced;
     for (size_t i = 0; i < count; ++i) {  // uploads first: the engine graph is not started yet
         int rc = sign_prepare(ctx, ck, msgs[i], lens[i], k0s + 32 * i, privkeys + 32 * i, privkeys_fhe[i], mode, &jobs[i]);
         if (rc) return rc;
@@ -587,6 +684,19 @@ int fhe_schnorr_sign_fhe_with_k0_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t 
         if (rc) return rc;
     }
     return FHE_OK;
+}
+
+int fhe_schnorr_sign_fhe_with_k0_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint8_t* const* msgs,
+                                       const size_t* lens, const uint8_t* k0s, const uint8_t* privkeys,
+                                       const fhe_biguint* const* privkeys_fhe, int mode, uint8_t* sigs) {
+    return sign_batch(ctx, ck, count, msgs, lens, k0s, privkeys, privkeys_fhe, mode, false, sigs);
+}
+
+// the batch with every s reduced under encryption (SignJob and the schedule shared as above)
+int fhe_schnorr_sign_fhe_with_k0_batch_reduced(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint8_t* const* msgs,
+                                               const size_t* lens, const uint8_t* k0s, const uint8_t* privkeys,
+                                               const fhe_biguint* const* privkeys_fhe, int mode, uint8_t* sigs) {
+    return sign_batch(ctx, ck, count, msgs, lens, k0s, privkeys, privkeys_fhe, mode, true, sigs);
 }
 
 // Schnorr::sign_fhe (src/schnorr.rs:154-211): encrypts the private key itself

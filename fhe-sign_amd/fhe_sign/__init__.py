@@ -26,6 +26,9 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
                                       random value on the GPU, one blind rotation per block, no keyswitch, no upload
                                       (oprf_rows_host, oprf_lut_host: the host definitions)
   Schnorr.sign_fhe_with_k0 / sign_fhe src/schnorr.rs:154-290
+  x.rem_pseudo_mersenne(k, c) / Schnorr.eval_s / sign_fhe_with_k0(reduce=True)   x mod (2^k - c) by folds (both
+                                      secp256k1 moduli: SECP256K1_N_C, SECP256K1_P_C); the signer reduces s mod n
+                                      under encryption, so the one decrypted value is the signature's s
 All ciphertext arithmetic runs on the GPU through lib/libfhe_rocm.so; this package only marshals.
 """
 from ._lib import CompressionParams, FheError, FheParams, load  # noqa: F401
@@ -33,7 +36,7 @@ from .core import (ClientKey, CompactPublicKey, CompressedCompressionKey, Compre
                    default_compression_params, generate_keys, ms_center_host, ms_stride, multi_bit_params, oprf_lut_host, oprf_rows_host, tuning)
 from .integer import (  # noqa: F401,E402
     COMPAT, FAST, PUBLIC, BigUintFHE, FheBool, FheUint, FheUint8, FheUint32, FheUint64, FheUint128, FheUint256, set_server_key,
-    LEVEL_SPLIT, level_log, rank_pbs, stats, to_u32_digits,
+    LEVEL_SPLIT, level_log, rank_pbs, stats, to_u32_digits, SECP256K1_N_C, SECP256K1_P_C,
     CompressedBigUintFHE, CompressedFheUint, CompressedFheUint8, CompressedFheUint32, CompressedFheUint64,
     CompressedFheUint128, CompressedFheUint256, CompressedCiphertextList,
     CompactCiphertextList, CompactCiphertextListBuilder,

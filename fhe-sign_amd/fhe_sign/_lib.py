@@ -331,6 +331,27 @@ _SIGNATURES = [
     ("fhe_schnorr_sign_fhe_with_k0_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p),
                                                     C.POINTER(C.c_size_t), C.c_char_p, C.c_char_p,
                                                     C.POINTER(C.c_void_p), C.c_int, C.c_char_p]),
+    ("fhe_radix_rem_pseudo_mersenne", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u64p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_columns_rem_pseudo_mersenne", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u64p, C.c_size_t,
+                                                  C.POINTER(C.c_void_p)]),
+    ("fhe_radix_scalar_mul_add_rem_pseudo_mersenne", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u64p, C.c_size_t,
+                                                               C.c_uint32, u64p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_host_sim_rem_pseudo_mersenne", C.c_int, [C.c_uint32, u64p, C.c_uint32, u64p, C.c_size_t, u64p, C.c_size_t, u64p,
+                                                   u64p, u32p]),
+    ("fhe_host_rem_pseudo_mersenne_stats", C.c_int, [C.c_uint32, C.c_uint32, u64p, C.c_size_t, u64p, u64p, u32p, C.c_size_t,
+                                                     u32p, u64p]),
+    ("fhe_host_biguint_mul_add_rem", C.c_int, [C.c_int, u32p, C.c_size_t, u32p, C.c_size_t, u32p, C.c_size_t, C.c_int,
+                                               C.c_uint32, u64p, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, u32p, u64p,
+                                               u64p, u32p, C.c_size_t, u32p, u64p]),
+    ("fhe_schnorr_sign_fhe_with_k0_reduced", C.c_int, [C.c_void_p, C.c_void_p, u8p, C.c_size_t, u8p, u8p, C.c_void_p,
+                                                      C.c_int, u8p]),
+    ("fhe_schnorr_sign_fhe_with_k0_rerand_reduced", C.c_int, [C.c_void_p, C.c_void_p, u8p, C.c_size_t, u8p, u8p, C.c_void_p,
+                                                             C.c_int, C.c_char_p, C.c_size_t, u8p]),
+    ("fhe_schnorr_sign_fhe_with_k0_batch_reduced", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p),
+                                                            C.POINTER(C.c_size_t), C.c_char_p, C.c_char_p,
+                                                            C.POINTER(C.c_void_p), C.c_int, C.c_char_p]),
+    ("fhe_schnorr_eval_s", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fhe_schnorr_eval_s_public", C.c_int, [C.c_void_p, u8p, u8p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_schnorr_sign_fhe", C.c_int, [C.c_void_p, C.c_void_p, u8p, C.c_size_t, u8p, u8p, C.c_int, u8p]),
     ("fhe_schnorr_verify", C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, u8p, C.c_size_t]),
 ]

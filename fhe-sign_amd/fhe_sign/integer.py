@@ -19,6 +19,10 @@ COMPAT = 0  # exact replay of src/biguint.rs:214-254 incl. the wrapping add at :
 FAST = 1    # true product/sum, single wide carry propagation
 PUBLIC = 2  # signer only: e and k stay clear, s = e * Enc(d') + k as a wide scalar multiply-add
 
+# secp256k1's moduli as 2^256 - c (FheUint.rem_pseudo_mersenne(256, c))
+SECP256K1_N_C = 0x14551231950B75FC4402DA1732FC9BEBF  # the curve order n
+SECP256K1_P_C = 2**32 + 977                          # the field prime p
+
 _tls = threading.local()
 
 
@@ -230,6 +234,19 @@ class FheUint:
             return self._bin("fhe_radix_rem", d)
         return self._scalar_any("fhe_radix_scalar_rem", d, wrap=False)
 
+    def rem_pseudo_mersenne(self, k_bits: int, c: int):
+        """self mod (2^k_bits - c) for a public pseudo-Mersenne modulus, as an FheUint of k_bits
+        (fhe_radix_rem_pseudo_mersenne): a few folds x <- (x mod 2^k) + (x >> k) c and one conditional subtraction
+        instead of `%`'s general division.  k_bits even, 0 < c < 2^(k_bits - 2); self of any width.  secp256k1:
+        (256, SECP256K1_N_C) and (256, SECP256K1_P_C)."""
+        k_bits, c = int(k_bits), int(c)
+        if c < 0:
+            raise ValueError("c must be positive")
+        w = _words(c, max(64, (c.bit_length() + 63) // 64 * 64))
+        h = C.c_void_p()
+        check(load().fhe_radix_rem_pseudo_mersenne(_ctx().handle, self._h, k_bits, ptr(w), w.size, C.byref(h)))
+        return self._wrap(h, k_bits)
+
     def serialize(self) -> bytes:
         """ciphertext bytes (own format, include/fhe_rocm.h); restore with FheUint.deserialize"""
         return serialize_with(load().fhe_radix_serialize, _ctx().handle, self._h)
@@ -411,6 +428,10 @@ class BigUintFHE:
         h = C.c_void_p()
         check(load().fhe_biguint_to_radix(self._h, bits, C.byref(h)))
         return FheUint._wrap(h, bits)
+
+    def rem_pseudo_mersenne(self, k_bits: int, c: int):
+        """the limbs' value mod (2^k_bits - c) as an FheUint of k_bits (FheUint.rem_pseudo_mersenne on to_radix)"""
+        return self.to_radix(32 * max(1, len(self))).rem_pseudo_mersenne(k_bits, c)
 
     def clone(self):
         h = C.c_void_p()

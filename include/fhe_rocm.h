@@ -351,6 +351,18 @@ int fhe_radix_scalar_mul_add_words(fhe_ctx* ctx, const fhe_radix* a, const uint6
                                    size_t nk, fhe_radix** out);
 int fhe_radix_scalar_div_words(fhe_ctx* ctx, const fhe_radix* a, const uint64_t* d, size_t nwords, fhe_radix** out);
 int fhe_radix_scalar_rem_words(fhe_ctx* ctx, const fhe_radix* a, const uint64_t* d, size_t nwords, fhe_radix** out);
+/* a mod (2^k_bits - c) for a public pseudo-Mersenne modulus (both moduli of secp256k1 are of this shape): folds
+ * x <- (x mod 2^k) + (x >> k) c, their number fixed by a's width, k and c (never by data), then one conditional
+ * subtraction.  k_bits even, 2 <= k_bits <= FHE_RADIX_MAX_BITS - 2; 0 < c < 2^(k_bits - 2) (c_words LSB first);
+ * anything else is FHE_ERR_INVALID with a message.  a of any width; out is an FheUint<k_bits> of clean blocks.
+ * Far cheaper than fhe_radix_scalar_rem_words with the same modulus, whose general division this avoids. */
+int fhe_radix_rem_pseudo_mersenne(fhe_ctx* ctx, const fhe_radix* a, uint32_t k_bits, const uint64_t* c_words, size_t nc,
+                                  fhe_radix** out);
+/* (k + m * a) mod (2^k_bits - c) for public m, k below the modulus: m * a is never formed, the sum of
+ * a_i * (m 4^i mod n) over a's blocks is, which leaves a few-block fold. */
+int fhe_radix_scalar_mul_add_rem_pseudo_mersenne(fhe_ctx* ctx, const fhe_radix* a, const uint64_t* m, size_t nm,
+                                                 const uint64_t* k, size_t nk, uint32_t k_bits, const uint64_t* c_words,
+                                                 size_t nc, fhe_radix** out);
 /* Ciphertext serialization (radix integers and BigUintFHE limb vectors; same format as the keys).
  * Deserialization needs a context whose server key has the same parameters; block degree / noise
  * metadata travels with the ciphertext and is checked against the radix layer's budget. */
@@ -467,6 +479,35 @@ int fhe_host_sim_biguint_mul_add_columns(const uint32_t* a, size_t la, const uin
  * prefix columns: vals holds nprefix records of 31 block values (each <= 3): column 0's block, then
  * the two blocks of each column 1..15; K = sum_m (column m's sum) 4^m.  g: nprefix outputs. */
 int fhe_host_sim_chain_g(const uint8_t* vals, size_t nprefix, uint32_t* g, uint64_t* pbs, uint64_t* levels);
+/* Pseudo-Mersenne reduction x mod (2^k_bits - c) (fhe_radix_rem_pseudo_mersenne below) without a GPU or a key.
+ * Simulated run on a `bits`-wide operand x (words LSB first): out gets the k_bits-wide result (nout >=
+ * ceil(k_bits / 64) words); pbs, levels, folds optional.  Refusals (odd k, c = 0, c >= 2^(k-2), bits above
+ * FHE_RADIX_MAX_BITS) return FHE_ERR_INVALID with a message, as the device entry points do. */
+int fhe_host_sim_rem_pseudo_mersenne(uint32_t bits, const uint64_t* x, uint32_t k_bits, const uint64_t* c_words, size_t nc,
+                                     uint64_t* out, size_t nout, uint64_t* pbs, uint64_t* levels, uint32_t* folds);
+/* Dry run of the same on an encrypted `bits`-wide operand: bootstraps, launch levels, level sizes (up to cap),
+ * the number of folds (fixed by bits, k and c) and the recording-order fingerprint (optional). */
+int fhe_host_rem_pseudo_mersenne_stats(uint32_t bits, uint32_t k_bits, const uint64_t* c_words, size_t nc, uint64_t* pbs,
+                                       uint64_t* levels, uint32_t* level_sizes, size_t cap, uint32_t* folds,
+                                       uint64_t* fingerprint);
+/* The reduced signer's FHE block (k + a * b) mod (2^k_bits - c) on limbs (LSB first), simulated (sim != 0) or
+ * dry (sim == 0: encrypted limbs' values are not read, only their counts matter; public a and k are read
+ * in both, their digits shape the graph).
+ *   mode FHE_BIGUINT_COMPAT / FHE_BIGUINT_FAST: a, b, k encrypted; fhe_biguint_mul_add_columns, then the
+ *     column-form reduction.  cols_out (optional, ncols words) gets the value of the column form -- what the
+ *     unreduced signer decrypts, the compat product's lost carries included -- and *col_bits its width:
+ *     out == cols_out mod n.
+ *   mode FHE_SIGN_PUBLIC_OPERANDS: a and k public, b encrypted; the product reduced as it is formed (what
+ *     fhe_schnorr_eval_s_public records).
+ *   mode FHE_SIGN_PUBLIC_OPERANDS | FHE_HOST_MUL_THEN_FOLD: the same through the unreduced public signer's
+ *     column form and the column-form reduction (the alternative the former is measured against).
+ * out: k_bits-wide result (sim only); pbs, levels, level_sizes, folds, fingerprint optional. */
+#define FHE_HOST_MUL_THEN_FOLD 0x800
+int fhe_host_biguint_mul_add_rem(int sim, const uint32_t* a, size_t la, const uint32_t* b, size_t lb, const uint32_t* k,
+                                 size_t lk, int mode, uint32_t k_bits, const uint64_t* c_words, size_t nc, uint64_t* out,
+                                 size_t nout, uint64_t* cols_out, size_t ncols, uint32_t* col_bits, uint64_t* pbs,
+                                 uint64_t* levels, uint32_t* level_sizes, size_t cap, uint32_t* folds,
+                                 uint64_t* fingerprint);
 
 /* ------------------------------------------------------------------- BigUintFHE */
 /* struct BigUintFHE { digits: Vec<FheUint32> } (src/biguint.rs:8-13), device-resident. */
@@ -505,6 +546,10 @@ int fhe_biguint_mul_add_columns(fhe_ctx* ctx, const fhe_biguint* a, const fhe_bi
 /* m * a + k (m, k public words) in column form, value mod 2^(a's bits) */
 int fhe_radix_scalar_mul_add_columns(fhe_ctx* ctx, const fhe_radix* a, const uint64_t* m, size_t nm, const uint64_t* k,
                                      size_t nk, fhe_columns** out);
+/* fhe_radix_rem_pseudo_mersenne on a column form: the folds are linear,
+ * so the first one reads the columns unpropagated -- only the part above 2^k_bits is normalized, on its own. */
+int fhe_columns_rem_pseudo_mersenne(fhe_ctx* ctx, const fhe_columns* x, uint32_t k_bits, const uint64_t* c_words,
+                                    size_t nc, fhe_radix** out);
 int fhe_columns_bits(const fhe_columns* x, uint32_t* bits);
 int fhe_columns_decrypt(fhe_ctx* ctx, const fhe_client_key* ck, const fhe_columns* x, uint64_t* words, size_t nwords);
 void fhe_columns_destroy(fhe_columns* x);
@@ -1074,6 +1119,33 @@ int fhe_schnorr_sign_fhe_with_k0_rerand(fhe_ctx* ctx, fhe_client_key* ck, const 
 int fhe_schnorr_sign_fhe_with_k0_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint8_t* const* msgs,
                                        const size_t* lens, const uint8_t* k0s, const uint8_t* privkeys,
                                        const fhe_biguint* const* privkeys_fhe, int mode, uint8_t* sigs);
+/* The signature with s reduced mod n UNDER ENCRYPTION.  The calls above decrypt s_without_mod = k + e d' (about
+ * 513 bits) and reduce on the host, as the reference does; whoever sees that plaintext has d' (e is public and
+ * floor(s_without_mod / e) is d' or a neighbour).  These decrypt 256 bits whose plaintext is exactly the
+ * signature's s -- public anyway.  The column form goes through fhe_columns_rem_pseudo_mersenne (n = 2^256 - c,
+ * c of 129 bits: three folds, then one propagation and select at 258 bits); FHE_SIGN_PUBLIC_OPERANDS reduces the product as
+ * it is formed (fhe_radix_scalar_mul_add_rem_pseudo_mersenne).  No host % n: a decrypted value not below n is
+ * FHE_ERR_INVALID.  Same arguments, modes and signature bytes as the unreduced calls. */
+int fhe_schnorr_sign_fhe_with_k0_reduced(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t msg_len,
+                                         const uint8_t k0[32], const uint8_t privkey[32],
+                                         const fhe_biguint* privkey_fhe, int mode, uint8_t sig[64]);
+int fhe_schnorr_sign_fhe_with_k0_rerand_reduced(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t msg_len,
+                                                const uint8_t k0[32], const uint8_t privkey[32],
+                                                const fhe_biguint* privkey_fhe, int mode, const uint8_t* domain,
+                                                size_t domain_len, uint8_t sig[64]);
+int fhe_schnorr_sign_fhe_with_k0_batch_reduced(fhe_ctx* ctx, fhe_client_key* ck, size_t count,
+                                               const uint8_t* const* msgs, const size_t* lens, const uint8_t* k0s,
+                                               const uint8_t* privkeys, const fhe_biguint* const* privkeys_fhe, int mode,
+                                               uint8_t* sigs);
+/* The server's half alone, for a deployment where another party decrypts: Enc(s), s = (k + e d') mod n, as an
+ * FheUint256 of clean blocks (every radix op, compression, serialization and re-randomization applies).  Takes
+ * no client key.  mode FHE_BIGUINT_COMPAT (the reference's limbs, lost carries included, then reduced) or
+ * FHE_BIGUINT_FAST. */
+int fhe_schnorr_eval_s(fhe_ctx* ctx, const fhe_biguint* e_fhe, const fhe_biguint* k_fhe, const fhe_biguint* privkey_fhe,
+                       int mode, fhe_radix** s);
+/* ... with e and k in the clear (big-endian, both below n) */
+int fhe_schnorr_eval_s_public(fhe_ctx* ctx, const uint8_t e[32], const uint8_t k[32], const fhe_biguint* privkey_fhe,
+                              fhe_radix** s);
 /* Schnorr::sign_fhe (src/schnorr.rs:154-211) */
 int fhe_schnorr_sign_fhe(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t msg_len,
                          const uint8_t aux_rand[32], const uint8_t privkey[32], int mode, uint8_t sig[64]);
