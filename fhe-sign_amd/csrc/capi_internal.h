@@ -1,0 +1,89 @@
+// capi_internal.h -- what the C-API files of the radix layer share (capi_radix.cpp: the device entry points,
+// capi_host.cpp: the host-only hooks).  Private to csrc/.
+#pragma once
+#include <exception>
+#include <vector>
+
+#include "biguint.h"
+#include "fhe_rocm.h"
+
+struct fhe_radix {
+    fhe::Radix r;
+    uint32_t bits = 0;
+};
+
+struct fhe_biguint {
+    fhe::BigUint v;
+};
+
+struct fhe_columns {
+    std::vector<fhe::Blocks> cols;
+    uint32_t nblocks = 0;
+};
+
+namespace fhe {
+
+template <class F>
+int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const EngineError& e) {  // carries its status (FHE_ERR_TIMEOUT, FHE_ERR_HIP)
+        set_error(e.what());
+        return e.code;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return FHE_ERR_INVALID;
+    }
+}
+
+inline BigConst words_of(const uint64_t* s, size_t nwords) { return BigConst(s, s + nwords); }
+
+// the blocks of a column form, for Engine::flush_for
+inline std::vector<const Block*> col_blocks(const std::vector<Blocks>& cols) {
+    std::vector<const Block*> v;
+    for (const Blocks& col : cols)
+        for (const Block& b : col)
+            if (!b.trivial()) v.push_back(&b);
+    return v;
+}
+
+// sum_j sum cols[j] 4^j mod 4^nblocks into words (LSB first), each column entry's value from val():
+// trivial blocks as they are, lazy blocks as their linear combination of slot blocks
+template <class V>
+void column_value(const std::vector<Blocks>& cols, uint32_t nblocks, V&& val, uint64_t* words, size_t nwords) {
+    std::vector<uint64_t> acc((2 * (size_t)nblocks + 63) / 64 + 2, 0);
+    auto add_at = [&](uint32_t j, int64_t v) {  // acc += v 4^j (every entry's value is >= 0)
+        engine_check(v >= 0, "column value below zero");
+        unsigned __int128 add = (unsigned __int128)(uint64_t)v << ((2 * j) % 64);
+        uint64_t carry = 0;
+        for (size_t w = (2 * (size_t)j) / 64; w < acc.size() && (add || carry); ++w) {
+            const unsigned __int128 s2 = (unsigned __int128)acc[w] + (uint64_t)add + carry;
+            acc[w] = (uint64_t)s2;
+            carry = (uint64_t)(s2 >> 64);
+            add >>= 64;
+        }
+    };
+    for (uint32_t j = 0; j < nblocks && j < cols.size(); ++j) {
+        int64_t v = 0;
+        for (const Block& b : cols[j]) {
+            if (b.trivial()) {
+                v += b.value;
+            } else if (b.lazy()) {
+                v += b.lin_cst;
+                for (const Term& t : *b.lin) v += (int64_t)t.coef * val(t.b);
+            } else {
+                v += val(b);
+            }
+        }
+        add_at(j, v);
+    }
+    const uint32_t bits = 2 * nblocks;
+    for (size_t w = 0; w < nwords; ++w) {
+        uint64_t x = w < acc.size() ? acc[w] : 0;
+        if (64 * w >= bits) x = 0;
+        else if (64 * (w + 1) > bits) x &= (bits % 64) ? ((1ull << (bits % 64)) - 1) : ~0ull;
+        words[w] = x;
+    }
+}
+
+}  // namespace fhe

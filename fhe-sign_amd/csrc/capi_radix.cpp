@@ -9,42 +9,14 @@
 
 #include <future>
 
-#include "biguint.h"
+#include "capi_internal.h"
 #include "ct_digest.h"
-#include "fhe_rocm.h"
 #include "oprf.h"
 #include "serial.h"
-
-struct fhe_radix {
-    fhe::Radix r;
-    uint32_t bits = 0;
-};
-
-struct fhe_biguint {
-    fhe::BigUint v;
-};
-
-struct fhe_columns {
-    std::vector<fhe::Blocks> cols;
-    uint32_t nblocks = 0;
-};
 
 using namespace fhe;
 
 namespace {
-
-template <class F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const EngineError& e) {  // carries its status (FHE_ERR_TIMEOUT, FHE_ERR_HIP)
-        set_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return FHE_ERR_INVALID;
-    }
-}
 
 int need_engine(fhe_ctx* c) {
     if (!c) {
@@ -76,8 +48,6 @@ fhe_radix* wrap(Radix r, uint32_t bits) {
 
 bool valid_bits(uint32_t bits) { return bits >= 2 && bits <= FHE_RADIX_MAX_BITS && bits % 2 == 0; }
 
-BigConst words_of(const uint64_t* s, size_t nwords) { return BigConst(s, s + nwords); }
-
 // run a binary op on two radix of equal width
 template <class F>
 int binop(fhe_ctx* c, const fhe_radix* a, const fhe_radix* b, fhe_radix** out, F&& f) {
@@ -106,45 +76,6 @@ int unop(fhe_ctx* c, const fhe_radix* a, fhe_radix** out, F&& f) {
 }
 
 }  // namespace
-
-// sum_j sum cols[j] 4^j mod 4^nblocks into words (LSB first), each column entry's value from val():
-// trivial blocks as they are, lazy blocks as their linear combination of slot blocks
-template <class V>
-static void column_value(const std::vector<Blocks>& cols, uint32_t nblocks, V&& val, uint64_t* words, size_t nwords) {
-    std::vector<uint64_t> acc((2 * (size_t)nblocks + 63) / 64 + 2, 0);
-    auto add_at = [&](uint32_t j, int64_t v) {  // acc += v 4^j (every entry's value is >= 0)
-        engine_check(v >= 0, "column value below zero");
-        unsigned __int128 add = (unsigned __int128)(uint64_t)v << ((2 * j) % 64);
-        uint64_t carry = 0;
-        for (size_t w = (2 * (size_t)j) / 64; w < acc.size() && (add || carry); ++w) {
-            const unsigned __int128 s2 = (unsigned __int128)acc[w] + (uint64_t)add + carry;
-            acc[w] = (uint64_t)s2;
-            carry = (uint64_t)(s2 >> 64);
-            add >>= 64;
-        }
-    };
-    for (uint32_t j = 0; j < nblocks && j < cols.size(); ++j) {
-        int64_t v = 0;
-        for (const Block& b : cols[j]) {
-            if (b.trivial()) {
-                v += b.value;
-            } else if (b.lazy()) {
-                v += b.lin_cst;
-                for (const Term& t : *b.lin) v += (int64_t)t.coef * val(t.b);
-            } else {
-                v += val(b);
-            }
-        }
-        add_at(j, v);
-    }
-    const uint32_t bits = 2 * nblocks;
-    for (size_t w = 0; w < nwords; ++w) {
-        uint64_t x = w < acc.size() ? acc[w] : 0;
-        if (64 * w >= bits) x = 0;
-        else if (64 * (w + 1) > bits) x &= (bits % 64) ? ((1ull << (bits % 64)) - 1) : ~0ull;
-        words[w] = x;
-    }
-}
 
 namespace fhe {
 void engine_eager_next_batch(fhe_ctx* c, bool on) {
@@ -225,15 +156,6 @@ int fhe_radix_trivial(fhe_ctx* c, const uint64_t* words, uint32_t bits, fhe_radi
     for (uint32_t k = 0; k < bits / 2; ++k) r.blocks.push_back(Block::make_trivial(word_bits(words, 2 * k, bits)));
     *out = wrap(std::move(r), bits);
     return FHE_OK;
-}
-
-// the blocks of a column form, for Engine::flush_for
-static std::vector<const Block*> col_blocks(const std::vector<Blocks>& cols) {
-    std::vector<const Block*> v;
-    for (const Blocks& col : cols)
-        for (const Block& b : col)
-            if (!b.trivial()) v.push_back(&b);
-    return v;
 }
 
 // the value of a column form (sum_j sum cols[j] 4^j mod 4^nblocks): every slot block (lazy entries:
@@ -513,30 +435,6 @@ int fhe_radix_cast(fhe_ctx* c, const fhe_radix* a, uint32_t bits, fhe_radix** ou
     (void)c;
     return FHE_OK;
 }
-int fhe_schedule_levels(const int32_t* off, const int32_t* deps, size_t n, int mode, int32_t* level_of,
-                        int32_t* nlevels) {
-    return fhe_schedule_levels_ranks(off, deps, n, mode, 1, level_of, nlevels);
-}
-
-int fhe_schedule_levels_ranks(const int32_t* off, const int32_t* deps, size_t n, int mode, int ranks, int32_t* level_of,
-                              int32_t* nlevels) {
-    if ((n && (!off || !level_of)) || !nlevels || (mode != 0 && mode != 1) || ranks < 1) return FHE_ERR_INVALID;
-    return guarded([&] {
-        std::vector<std::vector<int32_t>> g(n);
-        for (size_t i = 0; i < n; ++i)
-            for (int32_t k = off[i]; k < off[i + 1]; ++k) {
-                engine_check(deps && deps[k] >= 0 && (size_t)deps[k] < i, "dependency must name an earlier node");
-                g[i].push_back(deps[k]);
-            }
-        // the engine's flush (radix.cpp): a fanned-out level's fill granule is one latency round per rank
-        std::vector<std::vector<int32_t>> lv = schedule_levels(g, mode, (size_t)256 * (size_t)ranks);
-        for (size_t l = 0; l < lv.size(); ++l)
-            for (int32_t i : lv[l]) level_of[i] = (int32_t)l + 1;
-        *nlevels = (int32_t)lv.size();
-        return FHE_OK;
-    });
-}
-
 int fhe_ctx_level_log(fhe_ctx* c, uint32_t* sizes, size_t cap, size_t* n, int reset) {
     if (!c || !n || (cap && !sizes)) return FHE_ERR_INVALID;
     if (!c->engine) {
@@ -702,158 +600,6 @@ int fhe_biguint_mul(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, int 
     });
 }
 
-// Host-only run of the BigUintFHE mul / mul-add on publicly known limbs (no GPU, no key): every block
-// is trivial, so the engine folds each lookup on the host (Engine host_only) -- the radix algorithms'
-// indexing, LUTs and carry logic checked on the CPU against the reference's limb loop.
-int fhe_host_biguint_mul(const uint32_t* a, size_t la, const uint32_t* b, size_t lb, const uint32_t* k, size_t lk,
-                         int mode, uint32_t* out, size_t cap, size_t* n) {
-    if ((la && !a) || (lb && !b) || (lk && !k) || !n || (mode != kCompat && mode != kFast)) return FHE_ERR_INVALID;
-    return guarded([&] {
-        fhe_ctx c;  // parameters only: a host-only engine never touches the device
-        Engine e(&c, Engine::kHostFold);
-        auto make = [](const uint32_t* v, size_t n) {
-            BigUint r;
-            for (size_t i = 0; i < n; ++i) r.digits.push_back(radix_trivial(v[i], 0, kLimbBlocks));
-            return r;
-        };
-        const BigUint A = make(a, la), B = make(b, lb);
-        const BigUint R = k ? biguint_mul_add(e, A, B, make(k, lk), mode) : biguint_mul(e, A, B, mode);
-        *n = R.digits.size();
-        engine_check(R.digits.size() <= cap || !out, "output buffer too small");
-        for (size_t i = 0; out && i < R.digits.size(); ++i) {
-            uint64_t v = 0;
-            for (uint32_t q = 0; q < R.digits[i].nblocks(); ++q) {
-                const Block& blk = R.digits[i].blocks[q];
-                engine_check(blk.trivial() && !blk.half_neg && blk.value < 4, "host mul: a non-trivial output block");
-                v |= (uint64_t)blk.value << (2 * q);
-            }
-            out[i] = (uint32_t)v;
-        }
-        return FHE_OK;
-    });
-}
-
-// The recording-order fingerprint (Engine::fingerprint) of a dry la x lb BigUintFHE mul (or k + a * b)
-int fhe_host_biguint_mul_fingerprint(size_t la, size_t lb, size_t lk, int mode, uint64_t* fp) {
-    if (!fp || (mode != kCompat && mode != kFast)) return FHE_ERR_INVALID;
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kDry);
-        auto make = [&](size_t n) {
-            BigUint r;
-            for (size_t i = 0; i < n; ++i) {
-                Radix d;
-                for (uint32_t q = 0; q < kLimbBlocks; ++q) d.blocks.push_back(e.dry_block(3));
-                r.digits.push_back(std::move(d));
-            }
-            return r;
-        };
-        const BigUint A = make(la), B = make(lb);
-        const BigUint R = lk ? biguint_mul_add(e, A, B, make(lk), mode) : biguint_mul(e, A, B, mode);
-        e.flush();
-        *fp = e.fingerprint;
-        return FHE_OK;
-    });
-}
-
-// Test hooks of the radix size rules (radix.h Tuning): process-wide, *previous gets the old value
-int fhe_host_set_tuning(int key, int64_t value, int64_t* previous) {
-    Tuning& t = tuning();
-    int64_t old;
-    switch (key) {
-    case FHE_TUNE_KARA_MIN: old = t.kara_min; t.kara_min = (uint32_t)std::max<int64_t>(0, value); break;
-    case FHE_TUNE_KARA_COMPAT_MIN: old = t.kara_compat_min; t.kara_compat_min = (uint32_t)std::max<int64_t>(0, value); break;
-    case FHE_TUNE_KARA_FORCE: old = t.kara_force; t.kara_force = value != 0; break;
-    case FHE_TUNE_DIV_R16_LEAD: old = t.div_r16_lead; t.div_r16_lead = (uint32_t)std::max<int64_t>(0, value); break;
-    case FHE_TUNE_FLUSH_DEPTH: old = t.flush_depth; t.flush_depth = (uint32_t)std::max<int64_t>(0, value); break;
-    case FHE_TUNE_SCALAR_DIV_RESIDUE:
-        old = t.scalar_div_residue;
-        t.scalar_div_residue = value < 0 ? -1 : value != 0;
-        break;
-    default: return FHE_ERR_INVALID;
-    }
-    if (previous) *previous = old;
-    return FHE_OK;
-}
-
-// Dry run (no GPU): the same op on la x lb "encrypted" limbs (placeholder blocks) recorded and scheduled
-// by the engine without launching anything -- its bootstrap count, launch levels and level sizes.
-int fhe_host_biguint_mul_stats(size_t la, size_t lb, size_t lk, int mode, uint64_t* pbs, uint64_t* levels,
-                               uint32_t* level_sizes, size_t cap) {
-    const bool columns = (mode & FHE_HOST_STATS_COLUMNS) != 0;  // the signer's column form instead
-    const bool callsite = (mode & FHE_HOST_CALL_SITE) != 0;    // mul, then add (the product released)
-    const bool dec = (mode & FHE_HOST_DECRYPT_SUM) != 0;       // ... and the sum's decryption launched
-    mode &= ~(FHE_HOST_STATS_COLUMNS | FHE_HOST_CALL_SITE | FHE_HOST_DECRYPT_SUM);
-    if (!pbs || !levels || (mode != kCompat && mode != kFast)) return FHE_ERR_INVALID;
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kDry);
-        auto make = [&](size_t n) {
-            BigUint r;
-            for (size_t i = 0; i < n; ++i) {
-                Radix d;
-                for (uint32_t q = 0; q < kLimbBlocks; ++q) d.blocks.push_back(e.dry_block(3));
-                r.digits.push_back(std::move(d));
-            }
-            return r;
-        };
-        const BigUint A = make(la), B = make(lb);
-        BigUint R;
-        std::vector<Blocks> cols;
-        uint32_t nb = 0;
-        if (columns)
-            cols = biguint_mul_add_columns(e, A, B, make(lk), mode, &nb);
-        else if (callsite && lk)
-            R = biguint_add(e, make(lk), biguint_mul(e, A, B, mode), mode);
-        else
-            R = lk ? biguint_mul_add(e, A, B, make(lk), mode) : biguint_mul(e, A, B, mode);
-        if (dec && R.sum_cols)
-            e.flush_for(col_blocks(*R.sum_cols));
-        else
-            e.flush();
-        *pbs = e.pbs_count;
-        *levels = e.levels;
-        for (size_t i = 0; level_sizes && i < e.level_log.size() && i < cap; ++i) level_sizes[i] = e.level_log[i];
-        return FHE_OK;
-    });
-}
-
-// Dry run of one radix op on encrypted operands of the given widths (FHE_HOST_OP_*): its bootstrap
-// count and launch levels as the engine schedules them, nothing launched.
-int fhe_host_radix_stats(int op, uint32_t bits, uint64_t* pbs, uint64_t* levels, uint32_t* level_sizes, size_t cap) {
-    if (!pbs || !levels || bits < 2 || bits % 2 || bits > FHE_RADIX_MAX_BITS) return FHE_ERR_INVALID;
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kDry);
-        auto make = [&] {
-            Radix r;
-            for (uint32_t q = 0; q < bits / 2; ++q) r.blocks.push_back(e.dry_block(3));
-            return r;
-        };
-        const Radix A = make(), B = make();
-        std::vector<Radix> keep;  // results stay referenced through the flush (else they are dead nodes)
-        switch (op) {
-        case FHE_HOST_OP_DIVREM: {
-            auto qr = radix_divrem(e, A, B);
-            keep = {qr.first, qr.second};
-            break;
-        }
-        case FHE_HOST_OP_MUL: keep = {radix_mul(e, A, B, bits / 2)}; break;
-        case FHE_HOST_OP_ADD: keep = {radix_sum(e, {&A, &B}, bits / 2)}; break;
-        case FHE_HOST_OP_SUB: keep = {radix_sub(e, A, B)}; break;
-        case FHE_HOST_OP_SHR: keep = {radix_shr(e, A, B)}; break;
-        case FHE_HOST_OP_LT: keep = {Radix{{radix_lt(e, A, B)}}}; break;
-        case FHE_HOST_OP_DIV_SCALAR: keep = {radix_scalar_div(e, A, BigConst{0xC0FFEE01u})}; break;
-        default: engine_check(false, "unknown host op");
-        }
-        e.flush();
-        *pbs = e.pbs_count;
-        *levels = e.levels;
-        for (size_t i = 0; level_sizes && i < e.level_log.size() && i < cap; ++i) level_sizes[i] = e.level_log[i];
-        return FHE_OK;
-    });
-}
-
 // k + a * b in column form for decryption (biguint_mul_add_columns): the FHE work of the mode's
 // mul-add without its final carry propagation, which the decryption resolves on the host
 int fhe_biguint_mul_add_columns(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, const fhe_biguint* k, int mode,
@@ -954,360 +700,6 @@ int fhe_radix_scalar_mul_add_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a,
     const BigConst cc = words_of(c_words, nc), vm = words_of(m, nm), vk = words_of(k, nk);
     return guarded([&] {
         *out = wrap(radix_scalar_mul_add_rem_pseudo_mersenne(*c->engine, a->r, vm, vk, k_bits, cc), k_bits);
-        return FHE_OK;
-    });
-}
-
-namespace {
-// a host engine's clean result -> words
-void put_radix_words(Engine& e, const Radix& r, uint64_t* w, size_t nwords) {
-    engine_check(nwords * 64 >= 2 * (size_t)r.nblocks(), "sim: word buffer too small");
-    for (size_t i = 0; i < nwords; ++i) w[i] = 0;
-    for (uint32_t q = 0; q < r.nblocks(); ++q) {
-        const int64_t h2 = e.sim_half2(r.blocks[q]);
-        engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 8, "sim radix: an output block off its digit range");
-        w[q / 32] |= (uint64_t)(h2 / 2) << (2 * (q % 32));
-    }
-}
-void put_schedule(const Engine& e, uint64_t* pbs, uint64_t* levels, uint32_t* level_sizes, size_t cap) {
-    if (pbs) *pbs = e.pbs_count;
-    if (levels) *levels = e.levels;
-    for (size_t i = 0; level_sizes && i < e.level_log.size() && i < cap; ++i) level_sizes[i] = e.level_log[i];
-}
-bool host_width_ok(uint32_t bits) {
-    if (bits >= 2 && bits % 2 == 0 && bits <= FHE_RADIX_MAX_BITS) return true;
-    set_error("operand width must be even and within 2 .. FHE_RADIX_MAX_BITS");
-    return false;
-}
-}  // namespace
-
-// Simulated run (Engine kSim, no GPU, no key) of x mod (2^k_bits - c) on a `bits`-wide operand: out gets
-// the k_bits-wide result (words LSB first, nout >= ceil(k_bits / 64)); *pbs, *levels, *folds optional
-int fhe_host_sim_rem_pseudo_mersenne(uint32_t bits, const uint64_t* x, uint32_t k_bits, const uint64_t* c_words, size_t nc,
-                                     uint64_t* out, size_t nout, uint64_t* pbs, uint64_t* levels, uint32_t* folds) {
-    if (!x || !c_words || !nc || !out) return FHE_ERR_INVALID;
-    if (!host_width_ok(bits)) return FHE_ERR_INVALID;
-    const BigConst cc = words_of(c_words, nc);
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kSim);
-        Radix A;
-        for (uint32_t q = 0; q < bits / 2; ++q) A.blocks.push_back(e.sim_block((uint32_t)(x[q / 32] >> (2 * (q % 32))) & 3u, 3));
-        const Radix R = radix_rem_pseudo_mersenne(e, A, k_bits, cc, folds);
-        e.flush();
-        engine_check(2 * R.nblocks() == k_bits, "sim: the remainder's width is not k");
-        put_radix_words(e, R, out, nout);
-        put_schedule(e, pbs, levels, nullptr, 0);
-        return FHE_OK;
-    });
-}
-
-// Dry run (Engine kDry) of the same: bootstraps, launch levels, level sizes (up to cap), folds, and the
-// recording-order fingerprint (Engine::fingerprint: equal across processes iff the same graph is recorded
-// in the same order)
-int fhe_host_rem_pseudo_mersenne_stats(uint32_t bits, uint32_t k_bits, const uint64_t* c_words, size_t nc, uint64_t* pbs,
-                                       uint64_t* levels, uint32_t* level_sizes, size_t cap, uint32_t* folds,
-                                       uint64_t* fingerprint) {
-    if (!c_words || !nc || !pbs || !levels) return FHE_ERR_INVALID;
-    if (!host_width_ok(bits)) return FHE_ERR_INVALID;
-    const BigConst cc = words_of(c_words, nc);
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kDry);
-        Radix A;
-        for (uint32_t q = 0; q < bits / 2; ++q) A.blocks.push_back(e.dry_block(3));
-        const Radix R = radix_rem_pseudo_mersenne(e, A, k_bits, cc, folds);
-        e.flush();
-        put_schedule(e, pbs, levels, level_sizes, cap);
-        if (fingerprint) *fingerprint = e.fingerprint;
-        return FHE_OK;
-    });
-}
-
-// Simulated (sim != 0, kSim) or dry (kDry; encrypted limbs' values are ignored, their counts matter; public
-// operands are read in both) run of the reduced signer's FHE block: (k + a * b) mod (2^k_bits - c).
-//   mode FHE_COMPAT / FHE_FAST: all three encrypted, biguint_mul_add_columns then the column-form reduction;
-//     cols_out (optional, ncols words) gets the column form's value, *col_bits its width -- what the
-//     unreduced signer decrypts, so out == cols_out mod n whatever carries the compat product lost.
-//   mode FHE_SIGN_PUBLIC_OPERANDS: a and k public, b encrypted, the product reduced as it is formed
-//     (radix_scalar_mul_add_rem_pseudo_mersenne: what fhe_schnorr_eval_s_public records).
-//   mode FHE_SIGN_PUBLIC_OPERANDS | FHE_HOST_MUL_THEN_FOLD: the same operands through the unreduced public
-//     signer's column form (b widened to its exact width) and the column-form reduction: the alternative
-//     the residue form is measured against.
-int fhe_host_biguint_mul_add_rem(int sim, const uint32_t* a, size_t la, const uint32_t* b, size_t lb, const uint32_t* k,
-                                 size_t lk, int mode, uint32_t k_bits, const uint64_t* c_words, size_t nc, uint64_t* out,
-                                 size_t nout, uint64_t* cols_out, size_t ncols, uint32_t* col_bits, uint64_t* pbs,
-                                 uint64_t* levels, uint32_t* level_sizes, size_t cap, uint32_t* folds,
-                                 uint64_t* fingerprint) {
-    const bool then_fold = (mode & FHE_HOST_MUL_THEN_FOLD) != 0;
-    mode &= ~FHE_HOST_MUL_THEN_FOLD;
-    if ((la && !a) || (lb && !b) || (lk && !k) || !c_words || !nc || (sim && !out) ||
-        (mode != kCompat && mode != kFast && mode != FHE_SIGN_PUBLIC_OPERANDS) ||
-        (then_fold && mode != FHE_SIGN_PUBLIC_OPERANDS))
-        return FHE_ERR_INVALID;
-    const BigConst cc = words_of(c_words, nc);
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, sim ? Engine::kSim : Engine::kDry);
-        auto enc = [&](uint32_t v) { return sim ? e.sim_block(v, 3) : e.dry_block(3); };
-        auto make = [&](const uint32_t* v, size_t n) {
-            BigUint r;
-            for (size_t i = 0; i < n; ++i) {
-                Radix d;
-                for (uint32_t q = 0; q < kLimbBlocks; ++q) d.blocks.push_back(enc((v[i] >> (2 * q)) & 3u));
-                r.digits.push_back(std::move(d));
-            }
-            return r;
-        };
-        auto words = [](const uint32_t* v, size_t n) {
-            BigConst w((n + 1) / 2, 0);
-            for (size_t i = 0; i < n; ++i) w[i / 2] |= (uint64_t)v[i] << (32 * (i % 2));
-            return w;
-        };
-        auto col_value = [&](const std::vector<Blocks>& cols, uint32_t nb) {
-            if (col_bits) *col_bits = 2 * nb;
-            if (!sim || !cols_out) return;
-            engine_check(ncols * 64 >= 2 * (size_t)nb, "sim columns: word buffer too small");
-            column_value(cols, nb, [&](const Block& x) {
-                const int64_t h2 = e.sim_half2(x);
-                engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 32, "sim columns: a block off its message range");
-                return h2 / 2;
-            }, cols_out, ncols);
-        };
-        Radix R;
-        if (mode == FHE_SIGN_PUBLIC_OPERANDS) {
-            const BigUint B = make(b, lb);
-            Radix d;
-            for (const Radix& x : B.digits) d.blocks.insert(d.blocks.end(), x.blocks.begin(), x.blocks.end());
-            if (then_fold) {
-                const uint32_t nb = (uint32_t)(16 * lb + 16 * std::max(la, lk) + 1);
-                engine_check(2 * (uint64_t)nb <= FHE_RADIX_MAX_BITS, "operand width out of range");
-                const Radix dw = radix_resize(d, nb);
-                const std::vector<Blocks> cols =
-                    radix_mul_add_columns(e, dw, radix_trivial(words(a, la), nb), radix_trivial(words(k, lk), nb), nb);
-                R = radix_rem_pseudo_mersenne_columns(e, cols, nb, k_bits, cc, folds);
-                e.flush();
-                col_value(cols, nb);
-            } else {
-                R = radix_scalar_mul_add_rem_pseudo_mersenne(e, d, words(a, la), words(k, lk), k_bits, cc, folds);
-                e.flush();
-            }
-        } else {
-            const BigUint A = make(a, la), B = make(b, lb), K = make(k, lk);
-            uint32_t nb = 0;
-            const std::vector<Blocks> cols = biguint_mul_add_columns(e, A, B, K, mode, &nb);
-            R = radix_rem_pseudo_mersenne_columns(e, cols, nb, k_bits, cc, folds);
-            e.flush();
-            col_value(cols, nb);
-        }
-        if (sim) put_radix_words(e, R, out, nout);
-        put_schedule(e, pbs, levels, level_sizes, cap);
-        if (fingerprint) *fingerprint = e.fingerprint;
-        return FHE_OK;
-    });
-}
-
-// Simulated runs (no GPU, no key; Engine kSim): the operands are "encrypted" blocks whose plaintext
-// the engine shadows on the host, so the algorithms take every encrypted path (no trivial folding)
-// while each bootstrap is evaluated from its LUT and range-checked -- the end-to-end results of the
-// radix algorithms on the CPU.  *pbs / *levels (optional): the op's schedule, as fhe_host_*_stats.
-int fhe_host_sim_biguint_mul(const uint32_t* a, size_t la, const uint32_t* b, size_t lb, const uint32_t* k, size_t lk,
-                             int mode, uint32_t* out, size_t cap, size_t* n, uint64_t* pbs, uint64_t* levels) {
-    const bool callsite = (mode & FHE_HOST_CALL_SITE) != 0;
-    const bool dec = (mode & FHE_HOST_DECRYPT_SUM) != 0;
-    mode &= ~(FHE_HOST_CALL_SITE | FHE_HOST_DECRYPT_SUM);
-    if ((la && !a) || (lb && !b) || (lk && !k) || !n || (mode != kCompat && mode != kFast)) return FHE_ERR_INVALID;
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kSim);
-        auto make = [&](const uint32_t* v, size_t n) {
-            BigUint r;
-            for (size_t i = 0; i < n; ++i) {
-                Radix d;
-                for (uint32_t q = 0; q < kLimbBlocks; ++q) d.blocks.push_back(e.sim_block((v[i] >> (2 * q)) & 3u, 3));
-                r.digits.push_back(std::move(d));
-            }
-            return r;
-        };
-        const BigUint A = make(a, la), B = make(b, lb);
-        const BigUint R = k ? (callsite ? biguint_add(e, make(k, lk), biguint_mul(e, A, B, mode), mode)
-                                        : biguint_mul_add(e, A, B, make(k, lk), mode))
-                            : biguint_mul(e, A, B, mode);
-        if (dec && R.sum_cols) {
-            // what fhe_biguint_decrypt launches for a sum: its columns' closure; their value (the
-            // columns' plaintext shadows) must be the digits' (whose carry propagation stays pending)
-            e.flush_for(col_blocks(*R.sum_cols));
-            const uint32_t nb = (uint32_t)R.digits.size() * kLimbBlocks;
-            std::vector<uint64_t> w((2 * (size_t)nb + 63) / 64), d(w.size(), 0);
-            column_value(*R.sum_cols, nb, [&](const Block& b) { return e.sim_half2(b) / 2; }, w.data(), w.size());
-            for (size_t i = 0; i < R.digits.size(); ++i)
-                for (uint32_t q = 0; q < kLimbBlocks; ++q) {
-                    const uint32_t bit = (uint32_t)(i * 32 + 2 * q);
-                    d[bit / 64] |= (uint64_t)(e.sim_half2(R.digits[i].blocks[q]) / 2) << (bit % 64);
-                }
-            engine_check(w == d, "sim: the sum's column form and its digits differ");
-        } else {
-            e.flush();
-        }
-        *n = R.digits.size();
-        engine_check(R.digits.size() <= cap || !out, "output buffer too small");
-        for (size_t i = 0; out && i < R.digits.size(); ++i) {
-            uint64_t v = 0;
-            for (uint32_t q = 0; q < R.digits[i].nblocks(); ++q) {
-                const int64_t h2 = e.sim_half2(R.digits[i].blocks[q]);
-                engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 8, "sim mul: an output block off its digit range");
-                v |= (uint64_t)(h2 / 2) << (2 * q);
-            }
-            out[i] = (uint32_t)v;
-        }
-        if (pbs) *pbs = e.pbs_count;
-        if (levels) *levels = e.levels;
-        return FHE_OK;
-    });
-}
-
-// biguint_mul_add_columns on simulated limbs: the column form's value (words LSB first, nwords >=
-// its bits / 64) -- what fhe_columns_decrypt returns
-int fhe_host_sim_biguint_mul_add_columns(const uint32_t* a, size_t la, const uint32_t* b, size_t lb, const uint32_t* k,
-                                         size_t lk, int mode, uint64_t* words, size_t nwords, uint32_t* bits,
-                                         uint64_t* pbs, uint64_t* levels) {
-    if ((la && !a) || (lb && !b) || (lk && !k) || !words || !bits || (mode != kCompat && mode != kFast))
-        return FHE_ERR_INVALID;
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kSim);
-        auto make = [&](const uint32_t* v, size_t n) {
-            BigUint r;
-            for (size_t i = 0; i < n; ++i) {
-                Radix d;
-                for (uint32_t q = 0; q < kLimbBlocks; ++q) d.blocks.push_back(e.sim_block((v[i] >> (2 * q)) & 3u, 3));
-                r.digits.push_back(std::move(d));
-            }
-            return r;
-        };
-        const BigUint A = make(a, la), B = make(b, lb), K = make(k, lk);
-        uint32_t nb = 0;
-        const std::vector<Blocks> cols = biguint_mul_add_columns(e, A, B, K, mode, &nb);
-        e.flush();
-        *bits = 2 * nb;
-        engine_check(nwords * 64 >= 2 * (size_t)nb, "sim columns: word buffer too small");
-        column_value(cols, nb, [&](const Block& x) {
-            const int64_t h2 = e.sim_half2(x);
-            engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 32, "sim columns: a block off its message range");
-            return h2 / 2;
-        }, words, nwords);
-        if (pbs) *pbs = e.pbs_count;
-        if (levels) *levels = e.levels;
-        return FHE_OK;
-    });
-}
-
-int fhe_host_sim_chain_g(const uint8_t* vals, size_t nprefix, uint32_t* g, uint64_t* pbs, uint64_t* levels) {
-    if ((nprefix && (!vals || !g))) return FHE_ERR_INVALID;
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kSim);
-        std::vector<std::vector<Blocks>> P(nprefix, std::vector<Blocks>(kLimbBlocks));
-        for (size_t k = 0; k < nprefix; ++k) {
-            const uint8_t* v = vals + 31 * k;
-            for (int q = 0; q < 31; ++q) engine_check(v[q] <= 3, "sim chain g: a block value above 3");
-            P[k][0].push_back(e.sim_block(v[0], 3));
-            for (uint32_t m = 1; m < kLimbBlocks; ++m)
-                for (int q = 0; q < 2; ++q) P[k][m].push_back(e.sim_block(v[1 + 2 * (m - 1) + q], 3));
-        }
-        std::vector<const std::vector<Blocks>*> ptrs;
-        for (auto& x : P) ptrs.push_back(&x);
-        const Blocks out = compat_chain_g(e, ptrs);
-        e.flush();
-        for (size_t k = 0; k < nprefix; ++k) {
-            const int64_t h2 = e.sim_half2(out[k]);
-            engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 32, "sim chain g: g off its range");
-            g[k] = (uint32_t)(h2 / 2);
-        }
-        if (pbs) *pbs = e.pbs_count;
-        if (levels) *levels = e.levels;
-        return FHE_OK;
-    });
-}
-
-// One radix op (FHE_HOST_OP_*) on simulated operands a, b of `bits` (words LSB first, ceil(bits / 64)
-// each); out gets the result (MUL_FULL: 2 bits wide; LT / the comparison: 0 or 1 in out[0]); out2 the
-// remainder of DIVREM.
-int fhe_host_sim_radix(int op, uint32_t bits, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t* out2,
-                       uint64_t* pbs, uint64_t* levels) {
-    if (!a || !b || !out || bits < 2 || bits % 2 || bits > FHE_RADIX_MAX_BITS) return FHE_ERR_INVALID;
-    const bool two = op == FHE_HOST_OP_DIVREM || op == FHE_HOST_OP_DIVREM_CLEAR || op == FHE_HOST_OP_DIVREM_CLEAR_MIXED;
-    if (two && !out2) return FHE_ERR_INVALID;
-    return guarded([&] {
-        fhe_ctx c;
-        Engine e(&c, Engine::kSim);
-        const uint32_t nb = bits / 2;
-        auto make = [&](const uint64_t* w, bool odd_trivial) {
-            Radix r;
-            for (uint32_t q = 0; q < nb; ++q) {
-                const uint32_t v = (uint32_t)(w[q / 32] >> (2 * (q % 32))) & 3u;
-                r.blocks.push_back(odd_trivial && (q & 1) ? Block::make_trivial(v) : e.sim_block(v, 3));
-            }
-            return r;
-        };
-        const Radix A = make(a, op == FHE_HOST_OP_DIVREM_CLEAR_MIXED), B = make(b, false);
-        std::vector<Radix> keep;
-        std::vector<Blocks> cols;
-        switch (op) {
-        case FHE_HOST_OP_DIVREM: {
-            auto qr = radix_divrem(e, A, B);
-            keep = {qr.first, qr.second};
-            break;
-        }
-        case FHE_HOST_OP_MUL: keep = {radix_mul(e, A, B, nb)}; break;
-        case FHE_HOST_OP_ADD: keep = {radix_sum(e, {&A, &B}, nb)}; break;
-        case FHE_HOST_OP_SUB: keep = {radix_sub(e, A, B)}; break;
-        case FHE_HOST_OP_SHR: keep = {radix_shr(e, A, B)}; break;
-        case FHE_HOST_OP_LT: keep = {Radix{{radix_lt(e, A, B)}}}; break;
-        case FHE_HOST_OP_DIV_SCALAR: keep = {radix_scalar_div(e, A, BigConst{0xC0FFEE01u})}; break;
-        case FHE_HOST_OP_SHL: keep = {radix_shl(e, A, B)}; break;
-        case FHE_HOST_OP_MUL_FULL: keep = {radix_mul(e, A, B, 2 * nb)}; break;
-        case FHE_HOST_OP_AND: keep = {radix_bitand(e, A, B)}; break;
-        case FHE_HOST_OP_MIN: keep = {radix_min(e, A, B)}; break;
-        case FHE_HOST_OP_DIVREM_CLEAR:
-        case FHE_HOST_OP_DIVREM_CLEAR_MIXED: {  // a / b, a % b with b public (sim only)
-            BigConst d((bits + 63) / 64);
-            for (size_t w = 0; w < d.size(); ++w) d[w] = b[w];
-            keep = {radix_scalar_div(e, A, d), radix_scalar_rem(e, A, d)};
-            break;
-        }
-        case FHE_HOST_OP_SCALAR_MAC_COLUMNS: {  // a * m + m, m = b public: the public signer's column form
-            BigConst m((bits + 63) / 64);
-            for (size_t w = 0; w < m.size(); ++w) m[w] = b[w];
-            cols = radix_mul_add_columns(e, A, radix_trivial(m, nb), radix_trivial(m, nb), nb);
-            break;
-        }
-        default: engine_check(false, "unknown host op");
-        }
-        e.flush();
-        if (op == FHE_HOST_OP_SCALAR_MAC_COLUMNS) {
-            column_value(cols, nb, [&](const Block& x) {
-                const int64_t h2 = e.sim_half2(x);
-                engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 32, "sim columns: a block off its message range");
-                return h2 / 2;
-            }, out, (bits + 63) / 64);
-            if (pbs) *pbs = e.pbs_count;
-            if (levels) *levels = e.levels;
-            return FHE_OK;
-        }
-        auto put = [&](const Radix& r, uint64_t* w) {
-            const size_t words = (r.nblocks() + 31) / 32;
-            for (size_t i = 0; i < words; ++i) w[i] = 0;
-            for (uint32_t q = 0; q < r.nblocks(); ++q) {
-                const int64_t h2 = e.sim_half2(r.blocks[q]);
-                engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 8, "sim radix: an output block off its digit range");
-                w[q / 32] |= (uint64_t)(h2 / 2) << (2 * (q % 32));
-            }
-        };
-        put(keep[0], out);
-        if (two) put(keep[1], out2);
-        if (pbs) *pbs = e.pbs_count;
-        if (levels) *levels = e.levels;
         return FHE_OK;
     });
 }
@@ -2090,11 +1482,6 @@ Radix radix_random(Engine& e, const uint8_t seed[32], uint32_t nblocks, uint32_t
     r.blocks.resize(nblocks, Block::make_trivial(0));
     return r;
 }
-uint32_t bit_length(const BigConst& v) {
-    for (size_t i = v.size(); i-- > 0;)
-        if (v[i]) return (uint32_t)(64 * i) + 64 - (uint32_t)__builtin_clzll(v[i]);
-    return 0;
-}
 }  // namespace
 
 extern "C" {
@@ -2120,13 +1507,13 @@ int fhe_radix_random_below(fhe_ctx* c, const uint8_t* seed, uint32_t width_bits,
     if (!valid_bits(width_bits))
         return invalid("fhe_radix_random_below: the width must be even and 2 .. " + std::to_string(FHE_RADIX_MAX_BITS));
     BigConst b = words_of(bound, nwords);
-    const uint32_t blen = bit_length(b);
+    const uint32_t blen = big_bitlen(b);
     if (blen == 0) return invalid("fhe_radix_random_below: the bound must be positive");
     // bit_length(bound - 1)
     BigConst b1 = b;
     for (size_t i = 0; i < b1.size(); ++i)
         if (b1[i]-- != 0) break;
-    const uint32_t range_bits = bit_length(b1);
+    const uint32_t range_bits = big_bitlen(b1);
     if (range_bits > width_bits) return invalid("fhe_radix_random_below: values below the bound do not fit the width");
     // (r bound) >> m of an m-bit r, computed at m + bit_length(bound) bits: the product does not wrap
     const uint64_t m = (uint64_t)range_bits + extra_bits, wide = (m + blen + 1) / 2 * 2;

@@ -20,7 +20,7 @@
 // wave (36 waves).  The final limb is (K_l(last) + k_l(final)) mod 2^32.  Integer model, checked
 // against the reference's limb loop: tools/compat_chain_sim.py.
 //
-// Encodings (raw PbsItems, radix.h): beta is produced by a sign lookup -- a constant +1/2-step LUT,
+// Encodings (raw PbsItems, engine.h): beta is produced by a sign lookup -- a constant +1/2-step LUT,
 // whose negacyclic half gives -1/2 for inputs in [-16, 0) -- so the block holds s = beta - 1/2 and
 // every linear use of it adds the 1/2 back as a half-step constant.  The sign input k - g - 1 lies in
 // [-16, 14].

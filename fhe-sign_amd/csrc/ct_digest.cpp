@@ -1,6 +1,6 @@
 // ct_digest.cpp -- host side of the ciphertext digests (ct_digest.h): the definition of
 // ct_digest.hip's kernel, the value digest, the re-randomization context and their C entry points (no context,
-// no GPU), and the kernel's measurement hook.  Engine::digest (radix.cpp) is the device path.
+// no GPU), and the kernel's measurement hook.  Engine::digest (engine_ops.cpp) is the device path.
 #include <cstring>
 #include <memory>
 #include <string>

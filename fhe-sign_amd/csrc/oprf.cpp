@@ -1,7 +1,7 @@
 // oprf.cpp -- host side of the oblivious pseudo-random values (oprf.h): the word-for-word
 // definitions of the rows and of the accumulator (no context, no GPU), the accumulator's place in the context's
 // LUT registry, and the test and measurement entries that run the row kernel over a scratch buffer or hand
-// back raw blocks.  Engine::oprf (radix.cpp) is the device path; the radix entries are in capi_radix.cpp.
+// back raw blocks.  Engine::oprf (engine_ops.cpp) is the device path; the radix entries are in capi_radix.cpp.
 #include <algorithm>
 #include <cstring>
 

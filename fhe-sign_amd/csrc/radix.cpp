@@ -1,5 +1,7 @@
-// radix.cpp -- radix-integer layer: level executor + integer algorithms (host orchestration;
-// all ciphertext arithmetic runs in the gfx950 kernels of pbs_kernels.hip).
+// radix.cpp -- radix-integer layer: the integer algorithms over the engine (engine.h; host orchestration,
+// all ciphertext arithmetic runs in the gfx950 kernels of pbs_kernels.hip).  The block pool, the deferred
+// graph and the level scheduler are engine.cpp, the eager device operations engine_ops.cpp, the clear
+// multi-word arithmetic on public constants bigconst.cpp.
 //
 // Algorithms (published TFHE radix techniques, restated; tfhe 0.10.0 integer layer [ext]):
 //   * carry propagation: block states (generate/propagate/kill) + a radix-3 chain prefix (up to
@@ -10,13 +12,10 @@
 //   * scalar division: Granlund-Montgomery multiply-high by a public magic constant
 //   * comparison: borrow-out of a + ~b + 1 via the same prefix machinery
 //   * encrypted shift: barrel shifter, one bivariate "select" level per amount bit
+//   * pseudo-Mersenne reduction: linear folds of the high part, then one select among T - j n
 // Public structure only (degrees, trivial blocks) drives the schedule; no decision ever depends
 // on encrypted data.
 #include "radix.h"
-#include "compress_kernels.h"
-#include "ct_digest.h"
-#include "keygen.h"
-#include "oprf.h"
 
 #include <algorithm>
 #include <array>
@@ -31,1456 +30,6 @@
 #include <stdexcept>
 
 namespace fhe {
-
-Tuning& tuning() {
-    static Tuning t;
-    return t;
-}
-
-const Debug& debug() {
-    static const Debug d = [] {
-        Debug x;
-        const char* v = getenv("FHE_DEBUG");
-        const std::string s = v ? std::string(",") + v + "," : std::string();
-        auto has = [&](const char* k) { return s.find(std::string(",") + k + ",") != std::string::npos; };
-        x.levels = has("levels");
-        x.graph = has("graph");
-        x.chain = has("chain");
-        x.chain_host = has("chain-host");
-        x.residue = has("residue");
-        x.nodes = has("nodes");
-        return x;
-    }();
-    return d;
-}
-
-void engine_check(bool ok, const char* what) {
-    if (!ok) throw std::runtime_error(what);
-}
-
-static void hip_check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw EngineError(FHE_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-static void wait_check(fhe_ctx* c, const char* what) {
-    const int rc = c->wait_stream(what);
-    if (rc != FHE_OK) throw EngineError(rc, last_error());
-}
-
-// ============================================================================ block pool
-Slot::~Slot() {
-    if (pool && p) pool->release(p);
-}
-
-BlockPool::~BlockPool() {
-    if (dry_ || chunks_.empty()) return;  // a host-only engine never touches the HIP runtime
-    (void)hipSetDevice(device_);            // the chunks free themselves
-}
-
-// pool growth (FHE_TRACE_LEVELS prints it with the host time of run())
-static double g_pool_grow_ns = 0.0;
-static size_t g_pool_grows = 0;
-
-std::shared_ptr<Slot> BlockPool::alloc() {
-    if (dry_) {
-        auto s = std::make_shared<Slot>();
-        s->p = reinterpret_cast<uint64_t*>(dry_next_);
-        dry_next_ += kBigCt * 8;
-        return s;  // no pool: nothing to release
-    }
-    if (free_.empty()) {
-        const size_t per = 1024;  // 16 MiB chunks
-        DeviceBuf<uint64_t> chunk;
-        const auto t0 = std::chrono::steady_clock::now();
-        hip_check(chunk.grow(per * kBigCt), "block pool allocation");
-        g_pool_grow_ns += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count();
-        ++g_pool_grows;
-        uint64_t* const c = chunk;
-        chunks_.push_back(std::move(chunk));
-        for (size_t i = 0; i < per; ++i) free_.push_back(c + (per - 1 - i) * kBigCt);
-        total_ += per;
-    }
-    auto s = std::make_shared<Slot>();
-    s->p = free_.back();
-    free_.pop_back();
-    s->pool = shared_from_this();
-    return s;
-}
-
-// ============================================================================ engine
-Engine::Engine(fhe_ctx* ctx, int host_mode) : ctx_(ctx), host_mode_(host_mode) {
-    pool_ = std::make_shared<BlockPool>(ctx->device, host_mode_ != kDevice);  // host modes allocate no device slots
-    if (host_mode_ == kDevice)
-        for (auto& ev : desc_ev_) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "event");
-    trace_ = debug().levels;
-    gstats_ = debug().graph;
-}
-
-int32_t Engine::depth_of(const Block& b) const {
-    int32_t d = 0;
-    auto one = [&](const Block& x) {
-        if (x.slot && x.slot->node >= 0 && (size_t)x.slot->node < pending_.size())
-            d = std::max(d, pending_[x.slot->node].depth);
-    };
-    if (b.lazy())
-        for (const Term& t : *b.lin) one(t.b);
-    else
-        one(b);
-    return d;
-}
-
-Block Engine::sim_block(uint32_t value, uint32_t degree) {
-    engine_check(host_mode_ == kSim && value <= degree, "sim_block outside a simulating engine");
-    Block b = dry_block(degree);
-    sim_[b.ptr()] = 2 * (int64_t)value;
-    return b;
-}
-
-int64_t Engine::sim_half2(const Block& b) const {
-    if (b.trivial()) return trivial_half2(b);
-    if (b.lazy()) {
-        int64_t v = 2 * (int64_t)b.lin_cst;
-        for (const Term& t : *b.lin) v += (int64_t)t.coef * sim_half2(t.b);
-        return v;
-    }
-    auto it = sim_.find(b.ptr());
-    engine_check(it != sim_.end(), "sim: a block without a plaintext shadow");
-    return it->second;
-}
-
-Block Engine::dry_block(uint32_t degree) {
-    engine_check(host_mode_ == kDry || host_mode_ == kSim, "dry_block outside a dry engine");
-    Block b;
-    b.slot = pool_->alloc();
-    b.degree = degree;
-    b.noise = 1;
-    return b;
-}
-
-Engine::~Engine() {
-    if (host_mode_ != kDevice) return;
-    (void)hipSetDevice(ctx_->device);
-    (void)hipStreamSynchronize(ctx_->stream);
-    for (auto ev : desc_ev_)
-        if (ev) (void)hipEventDestroy(ev);
-}
-
-// The upload / download staging, at least `words` u64: grown to exactly that, behind the stream, when short.
-uint64_t* Engine::staging(size_t words) {
-    if (!d_up_.fits(words)) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "staging sync");
-        hip_check(d_up_.grow(words), "staging allocation");
-    }
-    return d_up_;
-}
-
-void Engine::ensure_desc(size_t n) {
-    if (n > desc_cap_) {
-        const size_t cap = std::max<size_t>(n, 4096);
-        desc_cap_ = 0;
-        for (int i = 0; i < 2; ++i) {
-            if (h_desc_[i]) hip_check(hipEventSynchronize(desc_ev_[i]), "desc event");
-            hip_check(h_desc_[i].grow(cap), "pinned descriptors");
-        }
-        desc_cap_ = cap;
-    }
-    if (!d_desc_.fits(n)) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "sync");
-        hip_check(d_desc_.grow(std::max<size_t>(n, 4096)), "device descriptors");
-    }
-}
-
-// Host staging buffer for n descriptors (double-buffered: wait until its previous copy is done).
-PbsDesc* Engine::stage_desc(size_t n, PbsDesc** dev) {
-    ensure_desc(n);
-    desc_turn_ ^= 1;
-    hip_check(hipEventSynchronize(desc_ev_[desc_turn_]), "desc event");
-    *dev = d_desc_;
-    return h_desc_[desc_turn_];
-}
-
-namespace {
-// reachable plaintexts of sum coef*x_t + cst (x_t in [0, degree_t]) as a bitmask over [0, 64)
-uint64_t reachable(const std::vector<Term>& terms, int64_t cst, bool* ok) {
-    *ok = true;
-    if (cst < 0 || cst >= 64) {
-        *ok = false;
-        return 0;
-    }
-    uint64_t set = 1ull << cst;
-    for (const Term& t : terms) {
-        // the set shifted by coef * x for every x in [0, degree]; a bit leaving [0, 64) is an input
-        // outside the message space
-        uint64_t nxt = 0;
-        for (uint32_t x = 0; x <= t.b.degree; ++x) {
-            const int64_t sh = (int64_t)t.coef * x;
-            if (sh >= 0) {
-                if (sh >= 64 || (sh > 0 && (set >> (64 - sh)) != 0)) {
-                    *ok = false;
-                    return 0;
-                }
-                nxt |= set << sh;
-            } else {
-                if (-sh >= 64 || (set & ((1ull << -sh) - 1)) != 0) {
-                    *ok = false;
-                    return 0;
-                }
-                nxt |= set >> -sh;
-            }
-        }
-        set = nxt;
-    }
-    return set;
-}
-}  // namespace
-
-Blocks Engine::run(std::vector<PbsItem>& items) {
-    struct Clock {  // host time inside run() (FHE_TRACE_LEVELS: printed at the next flush)
-        Engine* e;
-        std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-        ~Clock() { e->run_ns_ += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count(); }
-    } clock{this};
-    ++run_calls_;
-    const Params& p = ctx_->p;
-    const uint32_t mc = p.msg_carry();
-    Blocks out(items.size());
-    std::vector<size_t> gpu;
-    std::vector<std::vector<Term>> live(items.size());
-    std::vector<int64_t> csts(items.size());
-    for (size_t i = 0; i < items.size(); ++i) {
-        PbsItem& it = items[i];
-        if (it.raw) {  // caller-guaranteed range (radix.h): no folding, no degree check
-            engine_check(it.half_table.size() == mc, "raw LUT table size");
-            int64_t cst2 = 2 * (int64_t)it.cst + it.half_cst;  // half steps
-            uint32_t noise = 0;
-            int64_t lo2 = 0, hi2 = 0;  // worst-case interval of the live terms (half steps, from degrees)
-            for (const Term& t : it.terms) {
-                if (t.coef == 0) continue;
-                if (t.b.trivial())
-                    cst2 += (int64_t)t.coef * trivial_half2(t.b);
-                else {
-                    live[i].push_back(t);
-                    noise += (uint32_t)(t.coef * t.coef) * t.b.noise;
-                    const int64_t bl = t.b.half_neg ? -1 : 0, bh = 2 * (int64_t)t.b.degree - (t.b.half_neg ? 1 : 0);
-                    lo2 += t.coef > 0 ? t.coef * bl : t.coef * bh;
-                    hi2 += t.coef > 0 ? t.coef * bh : t.coef * bl;
-                }
-            }
-            engine_check(noise <= kMaxNoise, "raw PBS input noise above the budget");
-            // the caller guarantees the actual input lies in [-16, 16) (kSim checks every sampled one); the
-            // degrees alone must keep it inside one period of the negacyclic domain, [-32, 32) units (the
-            // widest raw item of the test suite reaches [-22.5, 21.5)), or a misuse could alias unseen
-            engine_check(cst2 + lo2 >= -64 && cst2 + hi2 < 64, "raw PBS item: input interval beyond one negacyclic period");
-            if (live[i].empty()) {  // a known input: evaluate on the host
-                engine_check(cst2 % 2 == 0 && cst2 >= -32 && cst2 < 32, "raw PBS item: known input off the grid");
-                const int64_t v = cst2 / 2;
-                const int32_t h = v >= 0 ? it.half_table[v] : -it.half_table[v + 16];
-                // an integer output, or a sign lookup's +-1/2 (kept as value - 1/2)
-                engine_check(h % 2 == 0 ? h >= 0 : (h == 1 || h == -1), "raw PBS item: known output off the grid");
-                out[i] = Block::make_trivial((uint32_t)((h + 1) / 2));
-                out[i].half_neg = h % 2 != 0;
-                continue;
-            }
-            out[i].degree = it.raw_degree;
-            out[i].noise = 1;
-            csts[i] = cst2;  // half steps (raw)
-            gpu.push_back(i);
-            continue;
-        }
-        engine_check(it.table.size() == mc, "LUT table size");
-        int64_t cst = it.cst;
-        uint32_t noise = 0;
-        for (const Term& t : it.terms) {
-            if (t.coef == 0) continue;
-            engine_check(!t.b.half_neg, "a sign lookup output in an ordinary item");
-            if (t.b.trivial())
-                cst += (int64_t)t.coef * t.b.value;
-            else {
-                live[i].push_back(t);
-                noise += (uint32_t)(t.coef * t.coef) * t.b.noise;
-            }
-        }
-        bool ok;
-        const uint64_t reach = reachable(live[i], cst, &ok);
-        engine_check(ok && (reach >> mc) == 0, "PBS input out of the message space (degree overflow)");
-        engine_check(noise <= kMaxNoise, "PBS input noise above the budget");
-        uint32_t lo = 0xffffffffu, hi = 0;
-        bool identity = live[i].size() == 1 && live[i][0].coef == 1 && cst == 0 && live[i][0].b.noise <= 1 &&
-                        !live[i][0].b.lazy();
-        for (uint32_t v = 0; v < mc; ++v) {
-            if (!(reach >> v & 1)) continue;
-            const uint32_t f = it.table[v] % mc;
-            lo = std::min(lo, f);
-            hi = std::max(hi, f);
-            if (f != v) identity = false;
-        }
-        if (lo == hi) {
-            out[i] = Block::make_trivial(lo);
-        } else if (identity) {
-            out[i] = live[i][0].b;  // LUT is the identity on every reachable input: alias
-            out[i].degree = hi;
-        } else {
-            out[i].degree = hi;
-            out[i].noise = 1;
-            csts[i] = cst;
-            gpu.push_back(i);
-        }
-    }
-    if (gpu.empty()) return out;
-    engine_check(host_mode_ != kHostFold, "host-only engine: an item needs a bootstrap (encrypted input)");
-
-    settle();  // nodes a partial flush left behind that were released since (flush_for)
-    // register LUTs, allocate destinations, record pending nodes
-    const uint64_t delta = p.delta();
-    std::vector<TermExt> terms;
-    const size_t n_before = pending_.size();
-    bool all_independent = true;  // no new node reads a pending one
-    for (size_t i : gpu) {
-        uint32_t lut = 0;
-        const bool raw = items[i].raw;
-        if (raw)
-            engine_check(ctx_->register_lut_half(items[i].half_table.data(), &lut) == FHE_OK, "LUT registration");
-        else
-            engine_check(ctx_->register_lut(items[i].table.data(), &lut) == FHE_OK, "LUT registration");
-        out[i].slot = pool_->alloc();
-        if (host_mode_ == kSim) {  // the plaintext shadow of this bootstrap
-            int64_t v2 = raw ? csts[i] : 2 * csts[i];
-            for (const Term& t : live[i]) v2 += (int64_t)t.coef * sim_half2(t.b);
-            int64_t o2;
-            if (raw) {
-                engine_check(v2 % 2 == 0 && v2 >= -32 && v2 < 32, "sim: raw PBS input outside [-16, 16)");
-                const int64_t v = v2 / 2;
-                o2 = v >= 0 ? items[i].half_table[v] : -items[i].half_table[v + 16];
-            } else {
-                engine_check(v2 % 2 == 0 && v2 >= 0 && v2 < 2 * (int64_t)mc, "sim: PBS input outside the message space");
-                o2 = 2 * (int64_t)(items[i].table[v2 / 2] % mc);
-            }
-            sim_[out[i].ptr()] = o2;
-        }
-        Pending n;
-        PbsDesc& d = n.d;
-        std::memset(&d, 0, sizeof d);
-        n.hold.push_back(out[i].slot);
-        // flatten lazy terms into their slot blocks (merging repeats); dcst in half steps for raw items
-        int64_t dcst = csts[i];
-        const int64_t unit = raw ? 2 : 1;
-        terms.clear();
-        const size_t cap = (size_t)kMaxWideTerms;  // > kMaxTerms: staged as a wide combination
-        auto put = [&](const Block& b, int32_t coef) {
-            for (TermExt& u : terms)
-                if (u.src == b.ptr()) {
-                    u.coef += coef;
-                    return;
-                }
-            engine_check(terms.size() < cap, "too many terms in one PBS input");
-            terms.push_back({b.ptr(), coef});
-            n.hold.push_back(b.slot);
-            if (b.slot->node >= 0) n.deps.push_back((int32_t)b.slot->node);
-        };
-        for (const Term& t : live[i]) {
-            if (!t.b.lazy()) {
-                put(t.b, t.coef);
-                continue;
-            }
-            dcst += unit * (int64_t)t.coef * t.b.lin_cst;
-            for (const Term& u : *t.b.lin) put(u.b, t.coef * u.coef);
-        }
-        const uint32_t nt = (uint32_t)terms.size();
-        if (nt <= (uint32_t)kMaxTerms) {
-            for (uint32_t u = 0; u < nt; ++u) {
-                d.src[u] = terms[u].src;
-                d.coef[u] = (int32_t)terms[u].coef;
-            }
-        } else {
-            n.ext = terms;  // d.src[0] is set to their staged copy at flush
-        }
-        d.nterms = nt;
-        d.lut = lut;
-        d.cst = raw ? (uint64_t)dcst * (delta / 2) : (uint64_t)dcst * delta;
-        if (gstats_) {
-            std::vector<std::pair<const uint64_t*, int64_t>> tk;
-            for (uint32_t u = 0; u < nt; ++u) tk.push_back({terms[u].src, terms[u].coef});
-            std::sort(tk.begin(), tk.end());
-            std::string key(reinterpret_cast<const char*>(tk.data()), tk.size() * sizeof(tk[0]));
-            key.append(reinterpret_cast<const char*>(&dcst), sizeof dcst);
-            in_key_.push_back(std::move(key));
-            bool okr;
-            const uint64_t rr = raw ? 0xFFFFull : reachable(live[i], csts[i], &okr);
-            in_deg_.push_back((uint8_t)(raw ? 16 : 63 - __builtin_clzll(rr | 1)));
-        }
-        d.dst = out[i].slot->p;
-        for (int32_t dep : n.deps) n.depth = std::max(n.depth, pending_[dep].depth + 1);
-        out[i].slot->node = (int64_t)pending_.size();
-        if (!n.deps.empty()) {
-            ++pending_dependent_;
-            all_independent = false;
-        }
-        pending_depth_ = std::max(pending_depth_, n.depth);
-        pending_.push_back(std::move(n));
-    }
-    if (pending_.size() >= (size_t)1 << 20) flush();  // bound the deferred graph (host memory)
-    // a deep graph (a long dependent chain: the encrypted division's 660 levels) is launched in slices
-    // of flush_depth levels, so the GPU runs one slice while the host records the next instead of
-    // waiting for the whole graph (the 256-bit division's ~150 ms of host recording); the slice's
-    // levels are scheduled on their own (a boundary can cost a fill opportunity, not a level)
-    if (tuning().flush_depth && pending_depth_ >= (int32_t)tuning().flush_depth) flush();
-    // the first large batch with nothing pending before it (e.g. a wide multiplication's block
-    // products) is one throughput level under any schedule: launch it now, so the GPU works while
-    // the host builds the rest of the graph (once per explicit flush: later independent batches,
-    // e.g. the compressions that follow, stay in the graph to be spread over idle capacity)
-    if (eager_ok_ && pending_.size() >= kEagerBatch && pending_dependent_ == 0) {
-        flush();
-        eager_ok_ = false;
-        eager_batch_next_ = false;
-    } else if (eager_batch_next_ && n_before > 0 && all_independent && pending_.size() - n_before >= kEagerBatch &&
-               !gstats_) {
-        // (a batch of independent programs, eager_next_batch) the program's first large batch that reads
-        // nothing pending, recorded behind the earlier programs' pending work -- the next signature's
-        // block products -- is launched now on its own, so the GPU runs it while the host records the
-        // rest; everything else stays deferred and is scheduled together (the programs share their
-        // latency levels)
-        eager_batch_next_ = false;
-        flush_tail(n_before);
-    }
-    return out;
-}
-
-// flush() of the nodes recorded from index k0 on (none of which reads an earlier pending node); the
-// nodes before k0 stay pending, with their indices
-void Engine::flush_tail(size_t k0) {
-    std::vector<Pending> keep(std::make_move_iterator(pending_.begin()), std::make_move_iterator(pending_.begin() + k0));
-    pending_.erase(pending_.begin(), pending_.begin() + k0);
-    for (size_t i = 0; i < pending_.size(); ++i) {
-        engine_check(pending_[i].deps.empty(), "tail flush of a node with pending producers");
-        pending_[i].hold[0]->node = (int64_t)i;
-    }
-    const size_t dependent = pending_dependent_;
-    const int32_t depth = pending_depth_;
-    const bool eager = eager_ok_;
-    pending_dependent_ = 0;
-    pending_depth_ = 1;
-    auto restore = [&] {
-        pending_ = std::move(keep);
-        pending_dependent_ = dependent;
-        pending_depth_ = depth;
-        eager_ok_ = eager;
-    };
-    try {
-        flush();
-    } catch (...) {
-        for (auto& n : pending_) n.hold[0]->node = -1;  // the tail is abandoned with the error
-        restore();  // the earlier graph stays consistent for the caller's error path
-        throw;
-    }
-    restore();
-}
-
-// flush() of the pending nodes `blocks` depend on (their ancestor closure); the others stay pending,
-// their reads of launched nodes resolved.  Dead nodes are swept first (over the whole graph: a value
-// released since the last flush); a closure that is the whole graph is a plain flush.  One rank only:
-// under a communicator (or emulated ranks) it is a plain flush -- what it leaves pending could only be
-// swept by a collective, and a rank-local read (a broadcast's root, one rank's decryption) that found
-// pending work would then run one collective on its own rank.
-void Engine::flush_for(const std::vector<const Block*>& blocks) {
-    if (pending_.empty() || gstats_ || ctx_->fanout_world() > 1 || (ctx_->attached() && ctx_->nranks > 1))
-        return flush();
-    sweep_dead();
-    const size_t N = pending_.size();
-    std::vector<uint8_t> need(N, 0);
-    std::vector<int32_t> stack;
-    auto mark = [&](const Block& b) {
-        if (b.slot && b.slot->node >= 0 && (size_t)b.slot->node < N && !need[b.slot->node]) {
-            need[b.slot->node] = 1;
-            stack.push_back((int32_t)b.slot->node);
-        }
-    };
-    for (const Block* b : blocks) {
-        if (b->lazy())
-            for (const Term& t : *b->lin) mark(t.b);
-        else
-            mark(*b);
-    }
-    size_t n_need = stack.size();
-    while (!stack.empty()) {
-        const int32_t k = stack.back();
-        stack.pop_back();
-        for (int32_t d : pending_[k].deps)
-            if (!need[d]) {
-                need[d] = 1;
-                ++n_need;
-                stack.push_back(d);
-            }
-    }
-    if (n_need == N) return flush();
-    if (n_need == 0) return run_before_launch();
-    // split in recording order; the closure reads nothing outside itself
-    std::vector<int32_t> idx(N);
-    std::vector<Pending> sub, keep;
-    sub.reserve(n_need);
-    keep.reserve(N - n_need);
-    int32_t ns = 0, nk = 0;
-    for (size_t k = 0; k < N; ++k) idx[k] = need[k] ? ns++ : nk++;
-    for (size_t k = 0; k < N; ++k) {
-        Pending& n = pending_[k];
-        std::vector<int32_t> deps;
-        for (int32_t d : n.deps) {
-            if (need[k]) {
-                engine_check(need[d], "closure reads a node outside it");
-                deps.push_back(idx[d]);
-            } else if (!need[d]) {
-                deps.push_back(idx[d]);  // a launched producer's output is ready: no dependency
-            }
-        }
-        n.deps = std::move(deps);
-        n.hold[0]->node = idx[k];
-        (need[k] ? sub : keep).push_back(std::move(n));
-    }
-    pending_ = std::move(sub);
-    try {
-        flush();  // a host read, like a full flush: the next program's first large batch may launch
-                  // eagerly (eager_ok_), once whatever stays pending has been swept as dead
-    } catch (...) {
-        for (auto& n : keep) n.hold[0]->node = -1;  // abandoned with the error (they read the closure)
-        throw;
-    }
-    pending_ = std::move(keep);
-    sweep_next_ = true;
-    recount();
-}
-
-// Level schedule of a dependency graph (deps[i]: earlier nodes node i reads).  Returns the nodes of
-// each launch level, in order; the level count is the critical path.  mode 0: backward list
-// scheduling (default), 1: forward deadline-driven; levels are filled to multiples of `round`
-// (one latency-kernel round: 256 bootstraps per GPU).  See Engine (radix.h).
-std::vector<std::vector<int32_t>> schedule_levels(const std::vector<std::vector<int32_t>>& deps, int mode,
-                                                  size_t round) {
-    const size_t N = deps.size();
-    std::vector<std::vector<int32_t>> lv;
-    if (N == 0) return lv;
-    // ASAP depth, critical path, ALAP deadlines
-    std::vector<int32_t> asap(N, 1), alap(N), ndeps(N, 0);
-    std::vector<std::vector<int32_t>> users(N);
-    int32_t L = 0;
-    for (size_t i = 0; i < N; ++i) {
-        for (int32_t d : deps[i]) {
-            asap[i] = std::max(asap[i], asap[d] + 1);
-            users[d].push_back((int32_t)i);
-        }
-        ndeps[i] = (int32_t)deps[i].size();
-        L = std::max(L, asap[i]);
-    }
-    for (size_t k = N; k-- > 0;) {
-        alap[k] = L;
-        for (int32_t u : users[k]) alap[k] = std::min(alap[k], alap[u] - 1);
-    }
-    const size_t kRound = std::max<size_t>(1, round);
-    using Key = std::pair<int32_t, int32_t>;
-    if (mode == 0) {
-        // backward list scheduling from the last level: a level takes every candidate (all users
-        // placed later) that cannot go any earlier (asap == t), then fills up to a whole round with
-        // the least flexible other candidates; what does not fit lands at its earliest level, where
-        // the unabsorbed throughput work forms large batches
-        std::vector<int32_t> nusers(N);
-        std::priority_queue<Key> cand;  // (asap, node), largest asap first
-        for (size_t i = 0; i < N; ++i) {
-            nusers[i] = (int32_t)users[i].size();
-            if (!nusers[i]) cand.push({asap[i], (int32_t)i});
-        }
-        for (int32_t t = L; t >= 1; --t) {
-            std::vector<int32_t> cur;
-            while (!cand.empty() && cand.top().first >= t) {
-                cur.push_back(cand.top().second);
-                cand.pop();
-            }
-            const size_t cap = std::max<size_t>(1, (cur.size() + kRound - 1) / kRound) * kRound;
-            while (!cand.empty() && cur.size() < cap) {
-                cur.push_back(cand.top().second);
-                cand.pop();
-            }
-            for (int32_t i : cur)
-                for (int32_t d : deps[i])
-                    if (--nusers[d] == 0) cand.push({asap[d], d});
-            lv.push_back(std::move(cur));
-        }
-        engine_check(cand.empty(), "scheduler left nodes unplaced");
-        std::reverse(lv.begin(), lv.end());
-    } else {
-        // forward list scheduling: deadline nodes always, then the most urgent ready ones up to a
-        // whole round
-        std::priority_queue<Key, std::vector<Key>, std::greater<Key>> ready;  // (deadline, node)
-        for (size_t i = 0; i < N; ++i)
-            if (!ndeps[i]) ready.push({alap[i], (int32_t)i});
-        for (int32_t t = 1; !ready.empty(); ++t) {
-            std::vector<int32_t> cur;
-            while (!ready.empty() && ready.top().first <= t) {
-                cur.push_back(ready.top().second);
-                ready.pop();
-            }
-            const size_t cap = std::max<size_t>(1, (cur.size() + kRound - 1) / kRound) * kRound;
-            while (!ready.empty() && cur.size() < cap) {
-                cur.push_back(ready.top().second);
-                ready.pop();
-            }
-            for (int32_t i : cur)
-                for (int32_t u : users[i])
-                    if (--ndeps[u] == 0) ready.push({alap[u], u});
-            lv.push_back(std::move(cur));
-        }
-    }
-    return lv;
-}
-
-void Engine::run_before_launch() {
-    if (!before_launch_) return;
-    auto f = std::move(before_launch_);
-    before_launch_ = nullptr;
-    f();
-}
-
-void Engine::recount() {
-    pending_dependent_ = 0;
-    pending_depth_ = 0;
-    for (Pending& n : pending_) {
-        n.depth = 1;
-        for (int32_t d : n.deps) n.depth = std::max(n.depth, pending_[d].depth + 1);
-        if (!n.deps.empty()) ++pending_dependent_;
-        pending_depth_ = std::max(pending_depth_, n.depth);
-    }
-}
-
-void Engine::sweep_dead() {
-    // Dead nodes: an output slot referenced by nothing but its own node (no later node reads it, no
-    // block of the program holds it -- e.g. a carry-chain state whose every consumer folded to a
-    // constant on the host) can never be read, so the node is dropped; newest first, so dropping a
-    // node releases its inputs and can make their producers dead in turn.
-    // The output counts come from host reference counts, i.e. from how long the caller keeps its
-    // handles: under a real communicator the ranks could disagree (one rank still holding an
-    // intermediate), and every rank must schedule the same levels (the split, the chunk and the
-    // all-gather size all follow from them).  So the ranks agree first: a node is dropped only if it
-    // is dead on EVERY rank (one byte-wise min all-reduce).  The result is closed under the cascade --
-    // a node kept on some rank keeps its producers' outputs referenced on that rank.
-    const size_t N0 = pending_.size();
-    std::vector<int32_t> remap(N0, -1);
-    std::vector<uint8_t> dead(N0, 0);
-    {
-        // count the references without releasing any: refs[k] = holders of node k's output slot
-        std::vector<long> refs(N0);
-        for (size_t k = 0; k < N0; ++k) refs[k] = pending_[k].hold[0].use_count();
-        for (size_t k = N0; k-- > 0;) {
-            if (refs[k] != 1) continue;
-            dead[k] = 1;
-            for (size_t h = 1; h < pending_[k].hold.size(); ++h) {
-                const int64_t prod = pending_[k].hold[h]->node;
-                if (prod >= 0) --refs[prod];
-            }
-        }
-    }
-    // Only a real multi-rank communicator needs the agreement (the collective is rank-uniform: every
-    // rank takes this branch or none does); at world size 1 it would only drain the stream.
-    if (ctx_->attached() && ctx_->nranks > 1) {
-        const int rc = ctx_->allreduce_min_u8(dead.data(), N0);
-        if (rc != FHE_OK) throw EngineError(rc, std::string("dead-node agreement: ") + last_error());
-    }
-    for (size_t k = N0; k-- > 0;)
-        if (dead[k]) pending_[k].hold.clear();
-    size_t live = 0;
-    for (size_t k = 0; k < N0; ++k)
-        if (!dead[k]) remap[k] = (int32_t)live++;
-    if (live < N0) {
-        dead_nodes += N0 - live;
-        std::vector<Pending> kept;
-        kept.reserve(live);
-        if (gstats_ && in_key_.size() == N0) {
-            size_t o = 0;
-            for (size_t k = 0; k < N0; ++k)
-                if (!dead[k]) {
-                    in_key_[o] = std::move(in_key_[k]);
-                    in_deg_[o++] = in_deg_[k];
-                }
-            in_key_.resize(o);
-            in_deg_.resize(o);
-        }
-        for (size_t k = 0; k < N0; ++k) {
-            if (dead[k]) continue;
-            Pending& n = pending_[k];
-            for (int32_t& d : n.deps) {
-                engine_check(remap[d] >= 0, "live node reads a dropped node");
-                d = remap[d];
-            }
-            n.hold[0]->node = remap[k];
-            kept.push_back(std::move(n));
-        }
-        pending_.swap(kept);
-    }
-    recount();  // the survivors' counters (their producers may have been launched by flush_for)
-}
-
-void Engine::flush() {
-    run_before_launch();  // a deferred upload lands before anything that could read it is launched
-    if (pending_.empty()) return;
-    const auto f0 = std::chrono::steady_clock::now();
-    if (trace_) {
-        fprintf(stderr, "[host] %zu run() calls, %.3f ms inside run() since the last flush (pool grown %zu x, %.3f ms)\n",
-                run_calls_, run_ns_ * 1e-6, g_pool_grows, g_pool_grow_ns * 1e-6);
-        run_ns_ = 0.0;
-        run_calls_ = 0;
-        g_pool_grows = 0;
-        g_pool_grow_ns = 0.0;
-    }
-    sweep_next_ = false;
-    sweep_dead();
-    if (pending_.empty()) {
-        pending_dependent_ = 0;
-        pending_depth_ = 0;
-        eager_ok_ = true;
-        return;
-    }
-    const size_t N = pending_.size();
-    std::vector<std::vector<int32_t>> deps(N);
-    for (size_t k = 0; k < N; ++k) deps[k] = pending_[k].deps;
-    if (gstats_) graph_stats(deps);
-    // a fanned-out level's round is one latency-kernel round on every rank
-    const size_t round = (size_t)kRound * (size_t)std::max(1, ctx_->fanout_world());
-    std::vector<std::vector<int32_t>> lv = schedule_levels(deps, 0, round);
-    if (host_mode_ == kDry || host_mode_ == kSim) {  // the schedule's statistics, nothing launched
-        auto mix = [&](uint64_t v) { fingerprint = (fingerprint ^ v) * 1099511628211ull; };
-        for (auto& l : lv) {
-            mix(l.size());
-            for (int32_t k : l) {
-                const Pending& pn = pending_[k];
-                mix((uint64_t)k);
-                mix(pn.d.lut);
-                mix(pn.d.nterms);
-                mix(pn.d.cst);
-                if (pn.ext.empty())
-                    for (uint32_t u = 0; u < pn.d.nterms && u < (uint32_t)kMaxTerms; ++u) mix((uint64_t)(int64_t)pn.d.coef[u]);
-                else
-                    for (const TermExt& t : pn.ext) mix((uint64_t)(int64_t)t.coef);
-                for (int32_t dp : pn.deps) mix((uint64_t)(int64_t)dp);
-            }
-        }
-        for (auto& l : lv) {
-            pbs_count += l.size();
-            levels += 1;
-            rank_pbs += l.size();
-            if (level_log.size() < kLevelLogCap) level_log.push_back((uint32_t)l.size());
-        }
-        for (auto& n : pending_) n.hold[0]->node = -1;
-        pending_.clear();
-        pending_dependent_ = 0;
-        pending_depth_ = 0;
-        eager_ok_ = true;
-        return;
-    }
-    // one staging copy of every level's descriptors (+ fanned-out levels' destination tables)
-    const int W = ctx_->fanout_world();
-    size_t ndesc = 0, maxchunk = 0, maxgather = 0;
-    for (auto& l : lv) {
-        const size_t G = l.size();
-        const bool split = W > 1 && G >= ctx_->fanout_min;
-        const size_t chunk = split ? (G + W - 1) / W : G;
-        ndesc += G + (split ? (G * sizeof(uint64_t*) + sizeof(PbsDesc) - 1) / sizeof(PbsDesc) : 0);
-        maxchunk = std::max(maxchunk, chunk);
-        if (split) maxgather = std::max(maxgather, chunk * W);
-    }
-    // wide combinations' term tables, staged after the level descriptors (PbsDesc-sized units)
-    size_t next = 0;
-    for (const Pending& n : pending_) next += n.ext.size();
-    const size_t ext_at = ndesc;
-    ndesc += (next * sizeof(TermExt) + sizeof(PbsDesc) - 1) / sizeof(PbsDesc);
-    if (maxgather) engine_check(ctx_->ensure_gather(maxgather) == FHE_OK, "gather workspace");
-    engine_check(ctx_->ensure_ms(maxchunk) == FHE_OK, "workspace");
-    engine_check(ctx_->sync_luts() == FHE_OK, "LUT upload");
-    PbsDesc* dev = nullptr;
-    PbsDesc* h = stage_desc(ndesc, &dev);
-    std::vector<size_t> at(lv.size());
-    size_t o = 0;
-    TermExt* h_ext = reinterpret_cast<TermExt*>(h + ext_at);
-    const TermExt* d_ext = reinterpret_cast<const TermExt*>(dev + ext_at);
-    size_t eo = 0;
-    for (size_t li = 0; li < lv.size(); ++li) {
-        const size_t G = lv[li].size();
-        const bool split = W > 1 && G >= ctx_->fanout_min;
-        at[li] = o;
-        uint64_t** h_scat = reinterpret_cast<uint64_t**>(h + o + G);
-        for (size_t g = 0; g < G; ++g) {
-            const Pending& pn = pending_[lv[li][g]];
-            PbsDesc d = pn.d;
-            if (!pn.ext.empty()) {
-                std::copy(pn.ext.begin(), pn.ext.end(), h_ext + eo);
-                d.src[0] = reinterpret_cast<const uint64_t*>(d_ext + eo);
-                eo += pn.ext.size();
-            }
-            if (split) {
-                // fanned-out levels bootstrap into the gather buffer (segment = owning rank), then scatter
-                h_scat[g] = d.dst;
-                d.dst = ctx_->d_gather + g * kBigCt;
-            }
-            h[o + g] = d;
-        }
-        o += G + (split ? (G * sizeof(uint64_t*) + sizeof(PbsDesc) - 1) / sizeof(PbsDesc) : 0);
-    }
-    hip_check(hipMemcpyAsync(dev, h, ndesc * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream), "desc copy");
-    hip_check(hipEventRecord(desc_ev_[desc_turn_], ctx_->stream), "desc event");
-    if (trace_)
-        fprintf(stderr, "[flush] %zu nodes (%llu dropped so far), %zu levels, scheduled in %.3f ms\n", N,
-                (unsigned long long)dead_nodes, lv.size(),
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count());
-    for (size_t li = 0; li < lv.size(); ++li) {
-        const size_t G = lv[li].size();
-        const bool split = W > 1 && G >= ctx_->fanout_min;
-        const size_t chunk = split ? (G + W - 1) / W : G;
-        PbsDesc* ld = dev + at[li];
-        auto pbs = [&](size_t lo, size_t hi) {
-            if (hi <= lo) return;
-            hip_check(ctx_->keyswitch(nullptr, ld + lo, hi - lo), "keyswitch");
-            hip_check(ctx_->blind_rotate(ld + lo, nullptr, nullptr, hi - lo), "blind rotate");
-        };
-        const auto t0 = std::chrono::steady_clock::now();
-        if (!split) {
-            pbs(0, G);
-        } else {
-            // own slice (every slice when ranks are emulated on one GPU)
-            for (int r = 0; r < W; ++r)
-                if (!ctx_->attached() || r == ctx_->rank) pbs(r * chunk, std::min(G, (r + 1) * chunk));
-            if (const int rc = ctx_->allgather(ctx_->d_gather, chunk * kBigCt); rc != FHE_OK)
-                throw EngineError(rc, std::string("all-gather: ") + last_error());
-            hip_check(launch_scatter_blocks(ctx_->d_gather, reinterpret_cast<uint64_t* const*>(ld + G), (int)G,
-                                            ctx_->stream),
-                      "scatter");
-            fanout_levels += 1;
-        }
-        ctx_->mark_progress();
-        pbs_count += G;
-        levels += 1;
-        // this rank's bootstraps: its slice of a fanned-out level (rank 0's when ranks are emulated), else all
-        const size_t r0 = ctx_->attached() ? (size_t)ctx_->rank : 0;
-        rank_pbs += split ? std::min(G, (r0 + 1) * chunk) - std::min(G, r0 * chunk) : G;
-        if (level_log.size() < kLevelLogCap) level_log.push_back((uint32_t)G | (split ? kLevelSplit : 0u));
-        if (trace_) {
-            hip_check(hipStreamSynchronize(ctx_->stream), "trace sync");
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            fprintf(stderr, "[level %llu] %zu PBS %.3f ms\n", (unsigned long long)levels, G, ms);
-        }
-        if (debug().nodes) {  // FHE_DEBUG=nodes: FNV-1a of every output of this level, in level order
-            hip_check(hipStreamSynchronize(ctx_->stream), "nodes sync");
-            std::vector<uint64_t> w(kBigCt);
-            for (size_t g = 0; g < G; ++g) {
-                const PbsDesc& d = h[at[li] + g];
-                const uint64_t* dst = split ? reinterpret_cast<uint64_t* const*>(h + at[li] + G)[g] : d.dst;
-                hip_check(hipMemcpy(w.data(), dst, kBigCt * 8, hipMemcpyDeviceToHost), "nodes copy");
-                uint64_t x = 1469598103934665603ull;
-                for (uint64_t v : w) x = (x ^ v) * 1099511628211ull;
-                fprintf(stderr, "[node] %llu %zu %u %u %llu %016llx\n", (unsigned long long)levels, g, d.lut, d.nterms,
-                        (unsigned long long)d.cst, (unsigned long long)x);
-            }
-        }
-    }
-    for (auto& n : pending_) n.hold[0]->node = -1;
-    pending_.clear();  // the stream orders any later reuse of the held slots behind these launches
-    pending_dependent_ = 0;
-    pending_depth_ = 0;
-    eager_ok_ = true;
-}
-
-// FHE_GRAPH_STATS: critical-path width (nodes with zero slack, asap == alap) and two-output candidates
-// (bootstraps whose input -- the same blocks, coefficients and constant -- another one also has, with
-// input degree <= 7, so that a half-box LUT pair could serve both from one blind rotation)
-void Engine::graph_stats(const std::vector<std::vector<int32_t>>& deps) {
-    const size_t N = deps.size();
-    if (in_key_.size() != N) {  // dropped dead nodes: their keys are gone from the count
-        fprintf(stderr, "[graph] %zu nodes (key bookkeeping skipped after dead-node removal)\n", N);
-        in_key_.clear();
-        in_deg_.clear();
-        return;
-    }
-    std::vector<int32_t> asap(N, 1), alap(N);
-    std::vector<std::vector<int32_t>> users(N);
-    int32_t L = 0;
-    for (size_t i = 0; i < N; ++i) {
-        for (int32_t d : deps[i]) {
-            asap[i] = std::max(asap[i], asap[d] + 1);
-            users[d].push_back((int32_t)i);
-        }
-        L = std::max(L, asap[i]);
-    }
-    std::vector<size_t> crit(L + 1, 0);
-    for (size_t k = N; k-- > 0;) {
-        alap[k] = L;
-        for (int32_t u : users[k]) alap[k] = std::min(alap[k], alap[u] - 1);
-        if (alap[k] == asap[k]) ++crit[asap[k]];
-    }
-    size_t ncrit = 0, maxc = 0;
-    for (size_t c : crit) {
-        ncrit += c;
-        maxc = std::max(maxc, c);
-    }
-    std::map<std::string, std::pair<size_t, size_t>> groups;  // key -> (count, count with degree <= 7)
-    for (size_t k = 0; k < N; ++k) {
-        auto& g = groups[in_key_[k]];
-        ++g.first;
-        if (in_deg_[k] <= 7) ++g.second;
-    }
-    size_t shared = 0, pairs7 = 0;
-    for (auto& kv : groups) {
-        if (kv.second.first > 1) shared += kv.second.first;
-        pairs7 += kv.second.second / 2;
-    }
-    fprintf(stderr, "[graph] %zu nodes, %d levels, critical %zu (max %zu per level), shared-input nodes %zu, "
-                    "degree<=7 pairs %zu (%.1f %% of the nodes saved by two-output blind rotations)\n",
-            N, L, ncrit, maxc, shared, pairs7, 100.0 * pairs7 / std::max<size_t>(1, N));
-    in_key_.clear();
-    in_deg_.clear();
-}
-
-Block Engine::lincomb(const std::vector<Term>& terms, uint32_t cst) {
-    for (const Term& t : terms) engine_check(!t.b.lazy(), "lincomb of a lazy block");
-    flush();
-    int64_t c = cst;
-    uint32_t noise = 0;
-    std::vector<Term> live;
-    for (const Term& t : terms) {
-        if (t.b.trivial())
-            c += (int64_t)t.coef * t.b.value;
-        else if (t.coef) {
-            live.push_back(t);
-            noise += (uint32_t)(t.coef * t.coef) * t.b.noise;
-        }
-    }
-    bool ok;
-    const uint64_t reach = reachable(live, c, &ok);
-    engine_check(ok && (reach >> ctx_->p.msg_carry()) == 0, "linear combination out of range");
-    uint32_t hi = 63 - __builtin_clzll(reach);
-    if (live.empty()) return Block::make_trivial((uint32_t)c);
-    Block b;
-    b.degree = hi;
-    b.noise = noise;
-    b.slot = pool_->alloc();
-    PbsDesc* dev = nullptr;
-    PbsDesc* h = stage_desc(1, &dev);
-    PbsDesc d;
-    std::memset(&d, 0, sizeof d);
-    for (size_t t = 0; t < live.size(); ++t) {
-        d.src[t] = live[t].b.ptr();
-        d.coef[t] = live[t].coef;
-    }
-    d.nterms = (uint32_t)live.size();
-    d.cst = (uint64_t)c * ctx_->p.delta();
-    d.dst = b.slot->p;
-    h[0] = d;
-    hip_check(hipMemcpyAsync(dev, h, sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream), "desc copy");
-    hip_check(hipEventRecord(desc_ev_[desc_turn_], ctx_->stream), "desc event");
-    hip_check(launch_lincomb(dev, 1, ctx_->stream), "lincomb");
-    return b;
-}
-
-Block Engine::upload(const uint64_t* ct, uint32_t degree) {
-    Block b;
-    b.slot = pool_->alloc();
-    b.degree = degree;
-    b.noise = 1;
-    hip_check(hipMemcpyAsync(b.slot->p, ct, kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "upload");
-    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
-    return b;
-}
-
-Blocks Engine::upload_many(const uint64_t* cts, size_t n, uint32_t degree) {
-    Blocks out(n);
-    if (n == 0) return out;
-    const size_t words = n * kBigCt + n;  // ciphertexts, then the slot pointers
-    uint64_t* const d_up = staging(words);
-    std::vector<uint64_t*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        out[i].slot = pool_->alloc();
-        out[i].degree = degree;
-        out[i].noise = 1;
-        dst[i] = out[i].slot->p;
-    }
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up + n * kBigCt);
-    hip_check(hipMemcpyAsync(d_up, cts, n * kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "upload");
-    hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "upload");
-    hip_check(launch_scatter_blocks(d_up, d_dst, (int)n, ctx_->stream), "upload scatter");
-    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go
-    return out;
-}
-
-Blocks Engine::expand_seeded(const uint8_t seed[32], const uint64_t* bodies, size_t n) {
-    engine_check(host_mode_ == kDevice, "expand_seeded on a host-only engine");
-    engine_check(n <= kSeededMaxBlocks, "seeded object of more than 2^24 blocks");
-    Blocks out(n);
-    if (n == 0) return out;
-    const size_t words = 2 * n;  // the bodies, then the slot pointers
-    uint64_t* const d_up = staging(words);
-    std::vector<uint64_t*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        out[i].slot = pool_->alloc();
-        out[i].degree = 3;
-        out[i].noise = 1;
-        dst[i] = out[i].slot->p;
-    }
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up + n);
-    hip_check(hipMemcpyAsync(d_up, bodies, n * 8, hipMemcpyHostToDevice, ctx_->stream), "seeded bodies");
-    hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
-              "seeded slots");
-    const KeyWords key = bytes_key(seed);
-    hip_check(launch_expand_seeded(chacha_stream_key(key.data(), kStreamSeededMask), d_dst, d_up, (int)n, ctx_->stream),
-              "seeded expansion");
-    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
-    return out;
-}
-
-// ------------------------------------------------------------------ compressed computed ciphertexts
-namespace {
-void need_compression(const fhe_ctx* c) {
-    if (!c->has_comp) throw EngineError(FHE_ERR_NO_KEY, "no compression key installed (fhe_set_compression_key)");
-}
-}  // namespace
-
-void Engine::compress(const std::vector<const Block*>& blocks, uint8_t* packed) {
-    engine_check(host_mode_ == kDevice, "compress on a host-only engine");
-    need_compression(ctx_);
-    const size_t n = blocks.size();
-    engine_check(n <= kCompressedMaxBlocks, "compressed list of more than 2^24 blocks");
-    if (n == 0) return;
-    const CompParams& cp = ctx_->cp;
-    // trivial blocks become ciphertexts (0, b) in slots of their own: the kernels see no special case
-    std::vector<size_t> triv;
-    for (size_t i = 0; i < n; ++i) {
-        engine_check(!blocks[i]->lazy(), "compress of a lazy block");
-        if (blocks[i]->trivial()) triv.push_back(i);
-    }
-    Blocks tmp;
-    if (!triv.empty()) {
-        std::vector<uint64_t> cts(triv.size() * kBigCt, 0ull);
-        for (size_t q = 0; q < triv.size(); ++q)
-            cts[q * kBigCt + kBigDim] = (uint64_t)blocks[triv[q]]->value * ctx_->p.delta();
-        tmp = upload_many(cts.data(), triv.size(), 0);
-    }
-    flush();
-    engine_check(ctx_->ensure_pk(n) == FHE_OK, "compression workspace");
-    std::vector<const uint64_t*> src(n);
-    for (size_t i = 0, q = 0; i < n; ++i) src[i] = blocks[i]->trivial() ? tmp[q++].slot->p : blocks[i]->slot->p;
-    hip_check(hipMemcpyAsync(ctx_->d_pk_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
-              "compress slots");
-    hip_check(launch_pack_keyswitch(ctx_->d_pk_src, (int)n, (int)cp.beta, (int)cp.ell, (int)cp.k, (int)cp.N, (int)cp.L,
-                                    ctx_->d_pk_planes, ctx_->d_pk_digits, ctx_->d_pk_body, ctx_->d_pk_P, ctx_->d_pk_out,
-                                    ctx_->stream),
-              "packing keyswitch");
-    const size_t G = cp.glwes(n), stride = (size_t)pk_out_stride((int)cp.k, (int)cp.N);
-    std::vector<uint8_t> stage(G * stride);
-    hip_check(hipMemcpyAsync(stage.data(), ctx_->d_pk_out, stage.size(), hipMemcpyDeviceToHost, ctx_->stream),
-              "compress download");
-    wait_check(ctx_, "compress");
-    // the device keeps every polynomial on a 32-bit word; the wire starts a GLWE on the next byte
-    uint8_t* out = packed;
-    for (size_t g = 0; g < G; ++g) {
-        const size_t bytes = cp.glwe_bytes(cp.bodies(n, g));
-        std::memcpy(out, stage.data() + g * stride, bytes);
-        out += bytes;
-    }
-}
-
-void Engine::pack_keyswitch_words(const uint64_t* cts, size_t n, uint64_t* P, uint64_t* body) {
-    engine_check(host_mode_ == kDevice, "compress on a host-only engine");
-    need_compression(ctx_);
-    engine_check(n <= kCompressedMaxBlocks, "compressed list of more than 2^24 blocks");
-    if (n == 0) return;
-    const CompParams& cp = ctx_->cp;
-    flush();
-    engine_check(ctx_->ensure_stage(n) == FHE_OK, "staging buffer");
-    engine_check(ctx_->ensure_pk(n) == FHE_OK, "compression workspace");
-    std::vector<const uint64_t*> src(n);
-    for (size_t i = 0; i < n; ++i) src[i] = ctx_->d_stage_in + i * kBigCt;
-    hip_check(hipMemcpyAsync(ctx_->d_stage_in, cts, n * kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "rows upload");
-    hip_check(hipMemcpyAsync(ctx_->d_pk_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
-              "compress slots");
-    hip_check(launch_pack_keyswitch(ctx_->d_pk_src, (int)n, (int)cp.beta, (int)cp.ell, (int)cp.k, (int)cp.N, (int)cp.L,
-                                    ctx_->d_pk_planes, ctx_->d_pk_digits, ctx_->d_pk_body, ctx_->d_pk_P, ctx_->d_pk_out,
-                                    ctx_->stream),
-              "packing keyswitch");
-    hip_check(hipMemcpyAsync(P, ctx_->d_pk_P, n * cp.cols() * 8, hipMemcpyDeviceToHost, ctx_->stream), "words download");
-    hip_check(hipMemcpyAsync(body, ctx_->d_pk_body, n * 8, hipMemcpyDeviceToHost, ctx_->stream), "bodies download");
-    wait_check(ctx_, "packing keyswitch words");
-}
-
-void Engine::extract_rows(const fhe_compressed_list& x, uint64_t* rows) {
-    engine_check(host_mode_ == kDevice, "decompress on a host-only engine");
-    need_compression(ctx_);
-    const size_t n = x.degrees.size();
-    if (n == 0) return;
-    const CompParams& cp = ctx_->cp;
-    engine_check(ctx_->ensure_cms(n) == FHE_OK, "decompression workspace");
-    hip_check(hipMemcpyAsync(ctx_->d_cpacked, x.packed.data(), x.packed.size(), hipMemcpyHostToDevice, ctx_->stream),
-              "compressed upload");
-    hip_check(launch_pk_unpack(ctx_->d_cpacked, (int)n, (int)cp.glwe_bytes(cp.L), (int)cp.L, (int)cp.N, (int)cp.k,
-                               ctx_->d_cms, ctx_->cms_stride, ctx_->stream),
-              "unpack");
-    if (rows) {
-        const size_t row = ((size_t)cp.lwe_dim() + 1) * 8;
-        hip_check(hipMemcpy2DAsync(rows, row, ctx_->d_cms, (size_t)ctx_->cms_stride * 8, row, n, hipMemcpyDeviceToHost,
-                                   ctx_->stream),
-                  "rows download");
-        hip_check(hipStreamSynchronize(ctx_->stream), "rows sync");
-    }
-}
-
-Blocks Engine::decompress(const fhe_compressed_list& x) {
-    const size_t n = x.degrees.size();
-    engine_check(host_mode_ == kDevice, "decompress on a host-only engine");
-    need_compression(ctx_);
-    Blocks out(n);
-    if (n == 0) return out;
-    std::vector<uint32_t> ident(ctx_->p.msg_carry());
-    for (uint32_t v = 0; v < ident.size(); ++v) ident[v] = v;
-    uint32_t lut = 0;
-    engine_check(ctx_->register_lut(ident.data(), &lut) == FHE_OK && ctx_->sync_luts() == FHE_OK, "identity table");
-    extract_rows(x, nullptr);
-    std::vector<PbsDesc> desc(n);
-    std::memset(desc.data(), 0, n * sizeof(PbsDesc));
-    for (size_t i = 0; i < n; ++i) {
-        out[i].slot = pool_->alloc();
-        out[i].degree = x.degrees[i];
-        out[i].noise = 1;
-        desc[i].lut = lut;
-        desc[i].dst = out[i].slot->p;
-    }
-    hip_check(hipMemcpyAsync(ctx_->d_cdesc, desc.data(), n * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream),
-              "decompress descriptors");
-    hip_check(ctx_->blind_rotate(ctx_->comp_keys(), ctx_->d_cdesc, nullptr, nullptr, n), "decompression blind rotate");
-    hip_check(hipStreamSynchronize(ctx_->stream), "decompress sync");  // host buffers may go, the staging be reused
-    pbs_count += n;
-    return out;
-}
-
-// ------------------------------------------------------------------ oblivious pseudo-random values
-Blocks Engine::oprf(const uint8_t seed[32], size_t count, uint32_t bits, uint32_t tail_bits) {
-    engine_check(host_mode_ == kDevice, "oprf on a host-only engine");
-    const Params& p = ctx_->p;
-    const uint32_t max_bits = oprf_max_bits(p);
-    if (bits < 1 || bits > max_bits || tail_bits > max_bits)
-        throw std::runtime_error("oprf: bits must be 1 .. log2(message_modulus) = " + std::to_string(max_bits));
-    const size_t n = count + (tail_bits ? 1 : 0);
-    engine_check(n <= kOprfMaxRows, "oprf: more than 2^23 rows of one seed");
-    Blocks out(n);
-    if (n == 0) return out;
-    uint32_t lut = 0, tail_lut = 0;
-    engine_check(ctx_->register_lut_oprf(bits, &lut) == FHE_OK && (!tail_bits || ctx_->register_lut_oprf(tail_bits, &tail_lut) == FHE_OK) &&
-                     ctx_->sync_luts() == FHE_OK,
-                 "oprf accumulator");
-    // the workspace as it stands (at least kOprfChunk rows) is the chunk: a large call does not grow it
-    constexpr size_t kOprfChunk = 4096;
-    const size_t chunk = std::min(n, std::max(ctx_->ms_cap, kOprfChunk));
-    engine_check(ctx_->ensure_ms(chunk) == FHE_OK, "bootstrap workspace");
-    if (!d_oprf_desc_.fits(chunk)) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "oprf descriptors sync");
-        hip_check(d_oprf_desc_.grow(std::max<size_t>(chunk, 256)), "oprf descriptors");
-    }
-    std::vector<PbsDesc> desc(n);
-    std::memset(desc.data(), 0, n * sizeof(PbsDesc));
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t b = i < count ? bits : tail_bits;
-        out[i].slot = pool_->alloc();
-        out[i].degree = (1u << b) - 1;
-        out[i].noise = 1;
-        desc[i].lut = i < count ? lut : tail_lut;
-        desc[i].cst = oprf_body_const(p, b);  // the blind rotation ignores it (no terms, no keyswitch): the body add's
-        desc[i].dst = out[i].slot->p;
-    }
-    const KeyWords key = bytes_key(seed);
-    const ChaChaKey ck = chacha_stream_key(key.data(), kStreamOprf);
-    for (size_t at = 0; at < n; at += chunk) {
-        const size_t m = std::min(chunk, n - at);
-        hip_check(launch_oprf_rows(ck, ctx_->d_ms, (uint32_t)at, (uint32_t)m, p.n, ctx_->stream), "oprf rows");
-        hip_check(hipMemcpyAsync(d_oprf_desc_, desc.data() + at, m * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream),
-                  "oprf descriptors");
-        hip_check(ctx_->blind_rotate(ctx_->main_keys(), d_oprf_desc_, nullptr, nullptr, m), "oprf blind rotate");
-        hip_check(launch_oprf_body_add(d_oprf_desc_, (uint32_t)m, ctx_->stream), "oprf body constant");
-    }
-    hip_check(hipStreamSynchronize(ctx_->stream), "oprf sync");  // host buffers may go
-    pbs_count += n;
-    return out;
-}
-
-// ------------------------------------------------------------------ compact ciphertext lists (public key)
-Blocks Engine::compact_extract(const fhe_compact_list& x, size_t first, size_t n, const std::vector<uint32_t>& degrees) {
-    engine_check(host_mode_ == kDevice, "expand_compact on a host-only engine");
-    engine_check(first + n <= x.ncoef() && x.ncoef() <= kCompactMaxCoefs && x.ca.size() == (x.ncoef() + kPolySize - 1) / kPolySize * kPolySize,
-                 "compact list: coefficient range outside the list");
-    Blocks out(n);
-    if (n == 0) return out;
-    const size_t c0 = first / kPolySize, c1 = (first + n - 1) / kPolySize + 1;  // the chunks the range touches
-    const size_t ca_words = (c1 - c0) * kPolySize;
-    const size_t words = ca_words + 2 * n;  // C_A of the chunks, the bodies, then the slot pointers
-    uint64_t* const d_up = staging(words);
-    std::vector<uint64_t*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        out[i].slot = pool_->alloc();
-        out[i].degree = degrees[i];
-        out[i].noise = 1;
-        dst[i] = out[i].slot->p;
-    }
-    uint64_t* d_cb = d_up + ca_words;
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_cb + n);
-    hip_check(hipMemcpyAsync(d_up, x.ca.data() + c0 * kPolySize, ca_words * 8, hipMemcpyHostToDevice, ctx_->stream),
-              "compact masks");
-    hip_check(hipMemcpyAsync(d_cb, x.cb.data() + first, n * 8, hipMemcpyHostToDevice, ctx_->stream), "compact bodies");
-    hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
-              "compact slots");
-    hip_check(launch_compact_extract(d_up, d_cb, d_dst, (uint32_t)(first - c0 * kPolySize), (int)n, ctx_->stream),
-              "compact extraction");
-    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
-    return out;
-}
-
-Blocks Engine::expand_compact(const fhe_compact_list& x, size_t value) {
-    engine_check(value < x.values.size(), "compact list: value index out of range");
-    const fhe_compact_list::Value& v = x.values[value];
-    std::vector<uint32_t> degrees(v.ncoef);
-    for (size_t q = 0; q < v.ncoef; ++q) degrees[q] = compact_degree(x, v, v.first + q);
-    Blocks coefs = compact_extract(x, v.first, v.ncoef, degrees);
-    if (!x.packed) return coefs;
-    // one level: block 2 q = x_q & 3, block 2 q + 1 = x_q >> 2
-    const uint32_t mc = ctx_->p.msg_carry();
-    std::vector<uint32_t> lo(mc), hi(mc);
-    for (uint32_t m = 0; m < mc; ++m) {
-        lo[m] = m & 3;
-        hi[m] = m >> 2;
-    }
-    std::vector<PbsItem> items(v.nblocks);
-    for (size_t k = 0; k < v.nblocks; ++k) {
-        items[k].terms = {{coefs[k / 2], 1}};
-        items[k].table = (k & 1) ? hi : lo;
-    }
-    return run(items);
-}
-
-void Engine::extract_compact_rows(const fhe_compact_list& x, uint64_t* rows) {
-    const size_t n = x.ncoef();
-    if (n == 0) return;
-    const Blocks all = compact_extract(x, 0, n, std::vector<uint32_t>(n, 3));
-    std::vector<const Block*> ptrs(n);
-    for (size_t i = 0; i < n; ++i) ptrs[i] = &all[i];
-    download_many(ptrs, rows);
-}
-
-// ------------------------------------------------------------------ re-randomization (public key)
-Blocks Engine::rerandomize(const std::vector<const Block*>& blocks, const uint8_t seed[32]) {
-    engine_check(host_mode_ == kDevice, "rerandomize on a host-only engine");
-    if (!ctx_->has_pk) throw EngineError(FHE_ERR_NO_KEY, "no public key installed (fhe_set_public_key)");
-    const size_t n = blocks.size();
-    engine_check(n <= kCompactMaxCoefs, "rerandomize of more than 2^24 blocks");
-    Blocks out(n);
-    if (n == 0) return out;
-    // lazy blocks first: their combination into slots of their own (lincomb flushes)
-    Blocks real(n);
-    std::vector<const Block*> in(n);
-    for (size_t i = 0; i < n; ++i) {
-        in[i] = blocks[i];
-        if (!blocks[i]->lazy()) continue;
-        engine_check(blocks[i]->lin_cst >= 0, "rerandomize of a lazy block below zero");
-        const uint32_t degree = blocks[i]->degree;
-        real[i] = lincomb(*blocks[i]->lin, (uint32_t)blocks[i]->lin_cst);
-        real[i].degree = degree;
-        in[i] = &real[i];
-    }
-    flush_for(in);
-    const size_t chunks = (n + kPolySize - 1) / kPolySize;
-    engine_check(ctx_->ensure_rr(chunks) == FHE_OK, "re-randomization workspace");
-    const size_t words = 3 * n;  // the source slots, the trivial bodies, then the fresh slots
-    uint64_t* const d_up = staging(words);
-    std::vector<const uint64_t*> src(n);
-    std::vector<uint64_t> tbody(n, 0);
-    std::vector<uint64_t*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        const Block& b = *in[i];
-        src[i] = b.ptr();
-        if (b.trivial()) {
-            engine_check(!b.half_neg, "rerandomize of a half-step block");
-            tbody[i] = (uint64_t)b.value * ctx_->p.delta();
-        }
-        // a real ciphertext from here on: slot set, no value, no combination, no half step
-        out[i].slot = pool_->alloc();
-        out[i].degree = b.trivial() ? std::max<uint32_t>(b.degree, kMsgMod - 1) : b.degree;
-        out[i].noise = b.noise;
-        dst[i] = out[i].slot->p;
-    }
-    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up);
-    uint64_t* d_tbody = d_up + n;
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up + 2 * n);
-    hip_check(hipMemcpyAsync(d_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "rerandomize slots");
-    hip_check(hipMemcpyAsync(d_tbody, tbody.data(), n * 8, hipMemcpyHostToDevice, ctx_->stream), "rerandomize bodies");
-    hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "rerandomize slots");
-    KeyWords key = bytes_key(seed);
-    ChaChaKey kbin = chacha_stream_key(key.data(), kStreamRerandBinary), knoise = chacha_stream_key(key.data(), kStreamRerandNoise);
-    const hipError_t zrc = launch_rerand_zero(kbin, knoise, ctx_->d_pk_ab, ctx_->d_rr_z, (uint32_t)n, ctx_->p.glwe_noise_log2, ctx_->stream);
-    // the launch has copied its arguments: the seed gives away R, no copy of it stays on the host
-    for (volatile uint32_t& w : key) w = 0;
-    for (ChaChaKey* k : {&kbin, &knoise})
-        for (volatile uint32_t& w : k->key) w = 0;
-    hip_check(zrc, "zero encryptions");
-    hip_check(launch_rerand_add(ctx_->d_rr_z, d_src, d_tbody, d_dst, (uint32_t)n, ctx_->stream), "re-randomization");
-    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
-    return out;
-}
-
-// ------------------------------------------------------------------ ciphertext digests
-void Engine::digest(const std::vector<const Block*>& blocks, uint8_t* out, std::vector<DigestMeta>* meta) {
-    engine_check(host_mode_ == kDevice, "digest on a host-only engine");
-    const size_t n = blocks.size();
-    engine_check(n <= kCtDigestMaxRows, "digest of more than 2^24 blocks");
-    if (meta) meta->assign(n, DigestMeta{0, 0, 0});
-    if (n == 0) return;
-    // lazy blocks first: their combination into slots of their own (lincomb flushes)
-    Blocks real(n);
-    std::vector<const Block*> in(n);
-    for (size_t i = 0; i < n; ++i) {
-        in[i] = blocks[i];
-        if (!blocks[i]->lazy()) continue;
-        engine_check(blocks[i]->lin_cst >= 0, "digest of a lazy block below zero");
-        const uint32_t degree = blocks[i]->degree;
-        real[i] = lincomb(*blocks[i]->lin, (uint32_t)blocks[i]->lin_cst);
-        real[i].degree = degree;
-        in[i] = &real[i];
-    }
-    flush_for(in);
-    const size_t words = 2 * n + 4 * n;  // the entries (16 B each), then the digests (32 B each, 16-byte aligned)
-    uint64_t* const d_up = staging(words);
-    std::vector<CtDigestEntry> entries(n);
-    for (size_t i = 0; i < n; ++i) {
-        const Block& b = *in[i];
-        entries[i].src = b.ptr();
-        entries[i].tbody = 0;
-        if (b.trivial()) {
-            engine_check(!b.half_neg, "digest of a half-step block");
-            entries[i].tbody = (uint64_t)b.value * ctx_->p.delta();
-        }
-        if (meta) (*meta)[i] = b.trivial() ? DigestMeta{0, b.value, 0} : DigestMeta{1, b.degree, b.noise};
-    }
-    CtDigestEntry* d_entries = reinterpret_cast<CtDigestEntry*>(d_up);
-    uint8_t* d_out = reinterpret_cast<uint8_t*>(d_up + 2 * n);
-    hip_check(hipMemcpyAsync(d_entries, entries.data(), n * sizeof(CtDigestEntry), hipMemcpyHostToDevice, ctx_->stream), "digest entries");
-    hip_check(launch_ct_digest(d_entries, d_out, (uint32_t)n, ct_digest_midstates(), ctx_->stream), "ciphertext digest");
-    hip_check(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, ctx_->stream), "digest download");
-    wait_check(ctx_, "digest");
-}
-
-Blocks Engine::upload_deferred(size_t n, uint32_t degree, std::function<std::vector<uint64_t>()> fill) {
-    run_before_launch();  // an earlier deferred upload first (one at a time)
-    Blocks out(n);
-    for (size_t i = 0; i < n; ++i) {
-        out[i].slot = pool_->alloc();
-        out[i].degree = degree;
-        out[i].noise = 1;
-    }
-    if (n == 0 || host_mode_ != kDevice) return out;
-    std::vector<std::shared_ptr<Slot>> held(n);  // alive until the upload, whatever the caller drops
-    for (size_t i = 0; i < n; ++i) held[i] = out[i].slot;
-    before_launch_ = [this, n, held = std::move(held), fill = std::move(fill)]() {
-        std::vector<uint64_t*> dst(n);
-        for (size_t i = 0; i < n; ++i) dst[i] = held[i]->p;
-        const std::vector<uint64_t> cts = fill();
-        engine_check(cts.size() == n * kBigCt, "deferred upload: ciphertext count");
-        const size_t words = n * kBigCt + n;
-        uint64_t* const d_up = staging(words);
-        uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up + n * kBigCt);
-        hip_check(hipMemcpyAsync(d_up, cts.data(), n * kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "upload");
-        hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream),
-                  "upload");
-        hip_check(launch_scatter_blocks(d_up, d_dst, (int)n, ctx_->stream), "upload scatter");
-        hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // cts and dst go out of scope
-    };
-    return out;
-}
-
-void Engine::download(const Block& b, uint64_t* ct) {
-    engine_check(!b.trivial() && !b.lazy(), "download of a trivial or lazy block");
-    flush();
-    hip_check(hipMemcpyAsync(ct, b.slot->p, kBigCt * 8, hipMemcpyDeviceToHost, ctx_->stream), "download");
-    wait_check(ctx_, "download");
-}
-
-void Engine::download_many(const std::vector<const Block*>& blocks, uint64_t* cts, bool only_needed) {
-    const size_t n = blocks.size();
-    if (n == 0) return;
-    if (only_needed)
-        flush_for(blocks);
-    else if (n == 1)
-        return download(*blocks[0], cts);
-    else
-        flush();
-    const size_t words = n * kBigCt + n;  // gathered ciphertexts, then the slot pointers
-    uint64_t* const d_up = staging(words);
-    std::vector<const uint64_t*> src(n);
-    for (size_t i = 0; i < n; ++i) {
-        engine_check(blocks[i]->slot != nullptr && !blocks[i]->lazy(), "download of a trivial or lazy block");
-        src[i] = blocks[i]->slot->p;
-    }
-    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up + n * kBigCt);
-    hip_check(hipMemcpyAsync(d_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "download");
-    hip_check(launch_gather_blocks(d_src, d_up, (int)n, ctx_->stream), "download gather");
-    hip_check(hipMemcpyAsync(cts, d_up, n * kBigCt * 8, hipMemcpyDeviceToHost, ctx_->stream), "download");
-    wait_check(ctx_, "download");
-}
-
-void Engine::sync() {
-    flush();
-    wait_check(ctx_, "sync");
-}
-
-Blocks Engine::adopt_device(const uint64_t* d_cts, size_t n) {
-    Blocks out(n);
-    if (n == 0) return out;
-    uint64_t* const d_up = staging(n);
-    std::vector<uint64_t*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        out[i].slot = pool_->alloc();
-        dst[i] = out[i].slot->p;
-    }
-    uint64_t** d_dst = reinterpret_cast<uint64_t**>(d_up);
-    hip_check(hipMemcpyAsync(d_dst, dst.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "adopt");
-    hip_check(launch_scatter_blocks(d_cts, d_dst, (int)n, ctx_->stream), "adopt scatter");
-    hip_check(hipStreamSynchronize(ctx_->stream), "adopt sync");  // the pointer staging may be reused
-    return out;
-}
-
-void Engine::gather_device(const std::vector<const Block*>& blocks, uint64_t* d_out) {
-    flush();
-    const size_t n = blocks.size();
-    if (n == 0) return;
-    uint64_t* const d_up = staging(n);
-    std::vector<const uint64_t*> src(n);
-    for (size_t i = 0; i < n; ++i) {
-        engine_check(blocks[i]->slot != nullptr && !blocks[i]->lazy(), "gather of a trivial or lazy block");
-        src[i] = blocks[i]->slot->p;
-    }
-    const uint64_t** d_src = reinterpret_cast<const uint64_t**>(d_up);
-    hip_check(hipMemcpyAsync(d_src, src.data(), n * sizeof(uint64_t*), hipMemcpyHostToDevice, ctx_->stream), "gather");
-    hip_check(launch_gather_blocks(d_src, d_out, (int)n, ctx_->stream), "gather");
-    hip_check(hipStreamSynchronize(ctx_->stream), "gather sync");
-}
-
-Block block_lazy(const std::vector<Term>& terms, int32_t cst, uint32_t degree) {
-    auto lin = std::make_shared<std::vector<Term>>();
-    Block b;
-    b.degree = degree;
-    for (const Term& t : terms) {
-        if (t.coef == 0) continue;
-        engine_check(!t.b.lazy(), "nested lazy block");
-        if (t.b.trivial()) {
-            cst += t.coef * (int32_t)t.b.value;
-            continue;
-        }
-        lin->push_back(t);
-        b.noise += (uint32_t)(t.coef * t.coef) * t.b.noise;
-    }
-    if (lin->empty()) {
-        engine_check(cst >= 0 && (uint32_t)cst <= degree, "lazy constant out of its range");
-        return Block::make_trivial((uint32_t)cst);
-    }
-    b.lin = std::move(lin);
-    b.lin_cst = cst;
-    return b;
-}
 
 // ============================================================================ LUT helpers
 namespace {
@@ -2702,76 +1251,6 @@ Radix radix_scalar_mul_add(Engine& e, const Radix& a, const BigConst& m, const B
     return radix_mul_add(e, a, tm, tc, a.nblocks());
 }
 
-// ---- clear multi-word arithmetic for the division constants (host only, a few hundred bits)
-namespace {
-BigConst big_norm(BigConst v) {
-    while (!v.empty() && v.back() == 0) v.pop_back();
-    return v;
-}
-uint32_t big_bitlen(const BigConst& v) {
-    for (size_t w = v.size(); w-- > 0;)
-        if (v[w]) return (uint32_t)(64 * w + 64 - __builtin_clzll(v[w]));
-    return 0;
-}
-bool big_bit(const BigConst& v, uint32_t i) { return i / 64 < v.size() && ((v[i / 64] >> (i % 64)) & 1); }
-int big_cmp(const BigConst& a, const BigConst& b) {
-    const size_t n = std::max(a.size(), b.size());
-    for (size_t w = n; w-- > 0;) {
-        const uint64_t x = w < a.size() ? a[w] : 0, y = w < b.size() ? b[w] : 0;
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return 0;
-}
-BigConst big_pow2(uint32_t e) {
-    BigConst v(e / 64 + 1, 0);
-    v[e / 64] = 1ull << (e % 64);
-    return v;
-}
-BigConst big_add(const BigConst& a, const BigConst& b) {
-    BigConst r(std::max(a.size(), b.size()) + 1, 0);
-    unsigned __int128 c = 0;
-    for (size_t w = 0; w < r.size(); ++w) {
-        c += (unsigned __int128)(w < a.size() ? a[w] : 0) + (w < b.size() ? b[w] : 0);
-        r[w] = (uint64_t)c;
-        c >>= 64;
-    }
-    return big_norm(r);
-}
-void big_sub_inplace(BigConst& a, const BigConst& b) {  // a >= b
-    uint64_t borrow = 0;
-    for (size_t w = 0; w < a.size(); ++w) {
-        const uint64_t y = w < b.size() ? b[w] : 0;
-        const uint64_t d = a[w] - y - borrow;
-        borrow = (a[w] < y || (a[w] == y && borrow)) ? 1 : 0;
-        a[w] = d;
-    }
-}
-BigConst big_shr1(BigConst v) {
-    for (size_t w = 0; w < v.size(); ++w) v[w] = (v[w] >> 1) | (w + 1 < v.size() ? v[w + 1] << 63 : 0);
-    return big_norm(v);
-}
-// floor(num / den), binary long division
-BigConst big_div(const BigConst& num, const BigConst& den) {
-    const uint32_t nb = big_bitlen(num);
-    BigConst q((nb + 63) / 64 + 1, 0), r;
-    for (uint32_t i = nb; i-- > 0;) {
-        uint64_t carry = big_bit(num, i) ? 1 : 0;  // r = 2 r + bit i of num
-        for (size_t w = 0; w < r.size(); ++w) {
-            const uint64_t nc = r[w] >> 63;
-            r[w] = (r[w] << 1) | carry;
-            carry = nc;
-        }
-        if (carry) r.push_back(carry);
-        if (big_cmp(r, den) >= 0) {
-            big_sub_inplace(r, den);
-            r = big_norm(r);
-            q[i / 64] |= 1ull << (i % 64);
-        }
-    }
-    return big_norm(q);
-}
-}  // namespace
-
 // Granlund-Montgomery (PLDI 1994, Fig. 6.2) multiplier for N-bit unsigned division by d
 // (d not a power of two): m = floor((2^(N+l) + 2^l) / d) reduced while m_low/2 < m_high/2.
 static void choose_multiplier(const BigConst& d, uint32_t N, BigConst* m, uint32_t* sh) {
@@ -2867,24 +1346,6 @@ static void const_products(const Radix& a, const std::vector<BigConst>& c, uint3
         if (kc[k]) cols[k].push_back(Block::make_trivial((uint32_t)kc[k]));
     }
     engine_check((recode && !excess) || kc[nblocks] == 0, "scalar division: exact columns overflow their width");
-}
-
-static BigConst big_mul(const BigConst& x, const BigConst& y) {
-    BigConst r(x.size() + y.size() + 1, 0);
-    for (size_t i = 0; i < x.size(); ++i) {
-        unsigned __int128 c = 0;
-        for (size_t j = 0; j < y.size(); ++j) {
-            c += (unsigned __int128)x[i] * y[j] + r[i + j];
-            r[i + j] = (uint64_t)c;
-            c >>= 64;
-        }
-        for (size_t k = i + y.size(); c; ++k) {
-            c += r[k];
-            r[k] = (uint64_t)c;
-            c >>= 64;
-        }
-    }
-    return big_norm(r);
 }
 
 // q (rem == nullptr) or r (into *rem) by the residue split; d >= 3 and not a power of two
@@ -3619,29 +2080,6 @@ Radix radix_scalar_rem(Engine& e, const Radix& a, const BigConst& dd) {
 // Every bootstrap is a column compression, a carry state / prefix or a select of the existing machinery,
 // the clear digits riding in the fused linear prologue; no kernel of its own.
 namespace {
-BigConst big_shr(const BigConst& v, uint32_t s) {
-    BigConst r;
-    for (size_t w = s / 64; w < v.size(); ++w) {
-        uint64_t x = v[w] >> (s % 64);
-        if (s % 64 && w + 1 < v.size()) x |= v[w + 1] << (64 - s % 64);
-        r.push_back(x);
-    }
-    return big_norm(r);
-}
-BigConst big_min(const BigConst& a, const BigConst& b) { return big_cmp(a, b) <= 0 ? a : b; }
-BigConst big_mod(const BigConst& a, const BigConst& n) {
-    if (big_cmp(a, n) < 0) return big_norm(a);
-    BigConst r = a;
-    big_sub_inplace(r, big_mul(big_div(a, n), n));
-    return big_norm(r);
-}
-// sum_q v[q] 4^q for nonnegative v
-BigConst big_from_digits(const std::vector<int64_t>& v) {
-    BigConst D;
-    auto shl2 = [](const BigConst& x) { return big_add(big_add(x, x), big_add(x, x)); };
-    for (size_t q = v.size(); q-- > 0;) D = big_add(shl2(D), BigConst{(uint64_t)v[q]});
-    return big_norm(D);
-}
 // sum_{j in [from, to)} degree(cols[j]) 4^(j - from)
 BigConst degree_bound(const std::vector<Blocks>& cols, uint32_t from, uint32_t to) {
     std::vector<int64_t> d;
@@ -3971,6 +2409,5 @@ Radix radix_scalar_mul_add_rem_pseudo_mersenne(Engine& e, const Radix& d, const 
         if (tk.blocks[j].value) cols[j].push_back(tk.blocks[j]);
     return pm_reduce(e, M, std::move(cols), nb, true, big_mod(E, M.n), folds);
 }
-
 
 }  // namespace fhe

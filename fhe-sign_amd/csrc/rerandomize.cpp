@@ -1,6 +1,6 @@
 // rerandomize.cpp -- host side of the re-randomization under the compact public key (public_key.h, DESIGN.md
 // 6f): the exact-integer definition of rerandomize.hip's two kernels, its C entry points (no context, no GPU),
-// and the install of the public key on a context.  Engine::rerandomize (radix.cpp) is the device path.
+// and the install of the public key on a context.  Engine::rerandomize (engine_ops.cpp) is the device path.
 #include <cstring>
 #include <memory>
 

@@ -267,7 +267,7 @@ def test_biguint_mul_add_columns_value(keys):
 
 
 def test_deferred_graph_lifetimes_and_raw_pbs(keys):
-    """The engine defers bootstraps until a host read (csrc/radix.h Engine): operands and results
+    """The engine defers bootstraps until a host read (csrc/engine.h Engine): operands and results
     dropped before that read keep what the pending graph still needs, raw fhe_pbs_batch calls in
     between (same stream, same workspace) neither see nor disturb pending work, and a graph built
     over several calls runs as one schedule with every value right."""

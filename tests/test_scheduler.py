@@ -1,4 +1,4 @@
-"""The radix engine's level scheduler (csrc/radix.cpp:schedule_levels, C ABI fhe_schedule_levels),
+"""The radix engine's level scheduler (csrc/engine.cpp:schedule_levels, C ABI fhe_schedule_levels),
 host logic only: on random dependency graphs and on the shape of a compat window-add chain, every
 node runs after its inputs, the level count is the critical path, levels are filled to whole
 latency-kernel rounds (256) only with work that could run there, and the backward schedule keeps

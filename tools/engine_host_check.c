@@ -1,0 +1,266 @@
+// engine_host_check.c -- stand-alone driver of the engine's host modes (dry, simulated and host-fold runs of the
+// radix and BigUintFHE algorithms, the level scheduler; no GPU call), with its own main.  It prints one line per
+// case: the dry schedules (bootstraps, levels, an FNV-1a of the level sizes), the recording-order fingerprints
+// where a hook returns one, and the simulated results on inputs from a fixed in-program generator.  Two builds of
+// the library record the same graphs in the same order iff the outputs are equal line for line (the fingerprint
+// covers LUT ids, coefficients, constants and producers of every node in level order).  Plain (each command one
+// line):
+//   make -C fhe-sign_amd
+//   cc -O1 -Iinclude tools/engine_host_check.c -Lfhe-sign_amd/lib -lfhe_rocm
+//      -Wl,-rpath,$PWD/fhe-sign_amd/lib -o engine_host_check
+// Host AddressSanitizer + UndefinedBehaviorSanitizer:
+//   make -C fhe-sign_amd asan
+//   clang -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan -Iinclude
+//         tools/engine_host_check.c -Lfhe-sign_amd/lib_asan -lfhe_rocm -Wl,-rpath,$PWD/fhe-sign_amd/lib_asan
+//         -Wl,-rpath,$(dirname $(clang -print-file-name=libclang_rt.asan-x86_64.so)) -o engine_host_check
+// (clang = the ROCm toolchain's, as for tools/oprf_host_check.c).  A refused case prints its status and message,
+// which are compared like any other line; the exit status is 1 only if a case that must succeed did not.
+#include <inttypes.h>
+#include <stdio.h>
+#include <string.h>
+#include "fhe_rocm.h"
+
+#define CAP 8192
+static uint32_t g_sizes[CAP];
+static int g_failed = 0;
+
+static uint64_t g_state = 0x9E3779B97F4A7C15ull;
+static uint64_t rnd(void) {  // splitmix64
+    uint64_t z = (g_state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+static void limbs(uint32_t* v, size_t n) {
+    for (size_t i = 0; i < n; ++i) v[i] = (uint32_t)rnd();
+}
+
+static uint64_t fnv_sizes(uint64_t levels) {
+    uint64_t x = 1469598103934665603ull;
+    for (uint64_t i = 0; i < levels && i < CAP; ++i) x = (x ^ g_sizes[i]) * 1099511628211ull;
+    return x;
+}
+// the status of a case: "ok", or the code and the message (a case that must succeed counts as failed)
+static int status(const char* name, int rc, int must) {
+    if (rc == FHE_OK) return 1;
+    printf("%s rc=%d (%s)\n", name, rc, fhe_last_error());
+    if (must) g_failed = 1;
+    return 0;
+}
+static void words_out(const uint64_t* w, size_t n) {
+    for (size_t i = 0; i < n; ++i) printf(" %016" PRIx64, w[i]);
+}
+static void limbs_out(const uint32_t* v, size_t n) {
+    for (size_t i = 0; i < n; ++i) printf(" %08" PRIx32, v[i]);
+}
+
+static const uint64_t kSecpC[1] = {0x1000003D1ull};  // secp256k1: p = 2^256 - 2^32 - 977
+static const size_t kShapes[4][3] = {{8, 8, 0}, {2, 8, 0}, {8, 12, 0}, {8, 1, 8}};
+
+static void radix_stats(void) {
+    const uint32_t widths[2] = {32, 256};
+    for (int op = 0; op <= 6; ++op)
+        for (int w = 0; w < 2; ++w) {
+            char name[64];
+            snprintf(name, sizeof name, "radix_stats op=%d bits=%u", op, widths[w]);
+            uint64_t pbs = 0, levels = 0;
+            memset(g_sizes, 0, sizeof g_sizes);
+            if (!status(name, fhe_host_radix_stats(op, widths[w], &pbs, &levels, g_sizes, CAP), 1)) continue;
+            printf("%s pbs=%" PRIu64 " levels=%" PRIu64 " sizes=%016" PRIx64 "\n", name, pbs, levels, fnv_sizes(levels));
+        }
+    uint64_t pbs, levels;
+    status("radix_stats op=7 bits=32", fhe_host_radix_stats(FHE_HOST_OP_SHL, 32, &pbs, &levels, NULL, 0), 0);
+    status("radix_stats op=99 bits=32", fhe_host_radix_stats(99, 32, &pbs, &levels, NULL, 0), 0);
+    status("radix_stats op=1 bits=31", fhe_host_radix_stats(FHE_HOST_OP_MUL, 31, &pbs, &levels, NULL, 0), 0);
+}
+
+static void sim_radix(void) {
+    const uint32_t widths[2] = {32, 64};
+    for (int op = 0; op <= 13; ++op)
+        for (int w = 0; w < 2; ++w) {
+            const uint32_t bits = widths[w];
+            const uint64_t mask = bits == 64 ? ~0ull : (1ull << bits) - 1;
+            uint64_t a[1] = {rnd() & mask}, b[1] = {rnd() & mask}, out[4] = {0}, out2[4] = {0}, pbs = 0, levels = 0;
+            if (op == FHE_HOST_OP_SHR || op == FHE_HOST_OP_SHL) b[0] %= bits;
+            if (b[0] == 0) b[0] = 3;
+            char name[64];
+            snprintf(name, sizeof name, "sim_radix op=%d bits=%u", op, bits);
+            if (!status(name, fhe_host_sim_radix(op, bits, a, b, out, out2, &pbs, &levels), 1)) continue;
+            printf("%s pbs=%" PRIu64 " levels=%" PRIu64 " out=", name, pbs, levels);
+            words_out(out, 2);
+            printf(" out2=");
+            words_out(out2, 1);
+            printf("\n");
+        }
+    uint64_t a[1] = {5}, b[1] = {3}, out[4], out2[4];
+    status("sim_radix op=99 bits=32", fhe_host_sim_radix(99, 32, a, b, out, out2, NULL, NULL), 0);
+    status("sim_radix op=0 bits=32 no out2", fhe_host_sim_radix(FHE_HOST_OP_DIVREM, 32, a, b, out, NULL, NULL, NULL), 0);
+}
+
+static void biguint_dry(void) {
+    const int flags[3] = {0, FHE_HOST_STATS_COLUMNS, FHE_HOST_CALL_SITE | FHE_HOST_DECRYPT_SUM};
+    for (int s = 0; s < 4; ++s)
+        for (int mode = 0; mode <= 1; ++mode) {
+            const size_t la = kShapes[s][0], lb = kShapes[s][1], lk = kShapes[s][2];
+            for (int f = 0; f < 3; ++f) {
+                char name[96];
+                snprintf(name, sizeof name, "biguint_mul_stats %zux%zu+%zu mode=%d flags=%#x", la, lb, lk, mode, flags[f]);
+                uint64_t pbs = 0, levels = 0;
+                memset(g_sizes, 0, sizeof g_sizes);
+                // the column form of a product without an addend is refused by the library: compared, not required
+                if (!status(name, fhe_host_biguint_mul_stats(la, lb, lk, mode | flags[f], &pbs, &levels, g_sizes, CAP), f != 1))
+                    continue;
+                printf("%s pbs=%" PRIu64 " levels=%" PRIu64 " sizes=%016" PRIx64 "\n", name, pbs, levels, fnv_sizes(levels));
+            }
+            char name[96];
+            snprintf(name, sizeof name, "biguint_mul_fingerprint %zux%zu+%zu mode=%d", la, lb, lk, mode);
+            uint64_t fp = 0;
+            if (status(name, fhe_host_biguint_mul_fingerprint(la, lb, lk, mode, &fp), 1)) printf("%s fp=%016" PRIx64 "\n", name, fp);
+        }
+    uint64_t fp;
+    status("biguint_mul_fingerprint mode=2", fhe_host_biguint_mul_fingerprint(8, 8, 0, 2, &fp), 0);
+}
+
+static void biguint_sim(void) {
+    uint32_t a[16], b[16], k[16], out[64];
+    for (int s = 0; s < 4; ++s)
+        for (int mode = 0; mode <= 1; ++mode)
+            for (int site = 0; site <= 1; ++site) {
+                const size_t la = kShapes[s][0], lb = kShapes[s][1], lk = kShapes[s][2];
+                if (site && !lk) continue;
+                limbs(a, la), limbs(b, lb), limbs(k, lk);
+                const int m = mode | (site ? FHE_HOST_CALL_SITE | FHE_HOST_DECRYPT_SUM : 0);
+                char name[96];
+                snprintf(name, sizeof name, "sim_biguint_mul %zux%zu+%zu mode=%#x", la, lb, lk, m);
+                size_t n = 0;
+                uint64_t pbs = 0, levels = 0;
+                if (!status(name, fhe_host_sim_biguint_mul(a, la, b, lb, lk ? k : NULL, lk, m, out, 64, &n, &pbs, &levels), 1))
+                    continue;
+                printf("%s pbs=%" PRIu64 " levels=%" PRIu64 " n=%zu out=", name, pbs, levels, n);
+                limbs_out(out, n);
+                printf("\n");
+                // the same limbs through the host fold
+                snprintf(name, sizeof name, "host_biguint_mul %zux%zu+%zu mode=%d", la, lb, lk, mode);
+                if (!site && status(name, fhe_host_biguint_mul(a, la, b, lb, lk ? k : NULL, lk, mode, out, 64, &n), 1)) {
+                    printf("%s n=%zu out=", name, n);
+                    limbs_out(out, n);
+                    printf("\n");
+                }
+            }
+    const size_t cshapes[3][3] = {{8, 8, 8}, {8, 1, 8}, {2, 8, 4}};
+    for (int s = 0; s < 3; ++s)
+        for (int mode = 0; mode <= 1; ++mode) {
+            const size_t la = cshapes[s][0], lb = cshapes[s][1], lk = cshapes[s][2];
+            limbs(a, la), limbs(b, lb), limbs(k, lk);
+            char name[96];
+            snprintf(name, sizeof name, "sim_biguint_mul_add_columns %zux%zu+%zu mode=%d", la, lb, lk, mode);
+            uint64_t w[16] = {0}, pbs = 0, levels = 0;
+            uint32_t bits = 0;
+            if (!status(name, fhe_host_sim_biguint_mul_add_columns(a, la, b, lb, k, lk, mode, w, 16, &bits, &pbs, &levels), 1))
+                continue;
+            printf("%s pbs=%" PRIu64 " levels=%" PRIu64 " bits=%u words=", name, pbs, levels, bits);
+            words_out(w, (bits + 63) / 64);
+            printf("\n");
+        }
+    uint64_t w[1];
+    uint32_t bits;
+    status("sim_biguint_mul_add_columns short buffer",
+           fhe_host_sim_biguint_mul_add_columns(a, 8, b, 8, k, 8, 1, w, 1, &bits, NULL, NULL), 0);
+}
+
+static void chain_g(void) {
+    uint8_t vals[4 * 31];
+    uint32_t g[4] = {0};
+    uint64_t pbs = 0, levels = 0;
+    for (size_t i = 0; i < sizeof vals; ++i) vals[i] = (uint8_t)(rnd() & 3);
+    memset(vals + 31, 3, 31);  // every block at its largest: K mod 2^32 in the wrap window
+    if (status("sim_chain_g", fhe_host_sim_chain_g(vals, 4, g, &pbs, &levels), 1))
+        printf("sim_chain_g pbs=%" PRIu64 " levels=%" PRIu64 " g= %u %u %u %u\n", pbs, levels, g[0], g[1], g[2], g[3]);
+    vals[5] = 4;
+    status("sim_chain_g value 4", fhe_host_sim_chain_g(vals, 4, g, NULL, NULL), 0);
+}
+
+static void rem_pseudo_mersenne(void) {
+    const uint32_t widths[3] = {256, 320, 512};
+    for (int w = 0; w < 3; ++w) {
+        const uint32_t bits = widths[w];
+        char name[64];
+        snprintf(name, sizeof name, "rem_pseudo_mersenne_stats bits=%u", bits);
+        uint64_t pbs = 0, levels = 0, fp = 0;
+        uint32_t folds = 0;
+        memset(g_sizes, 0, sizeof g_sizes);
+        if (status(name, fhe_host_rem_pseudo_mersenne_stats(bits, 256, kSecpC, 1, &pbs, &levels, g_sizes, CAP, &folds, &fp), 1))
+            printf("%s pbs=%" PRIu64 " levels=%" PRIu64 " sizes=%016" PRIx64 " folds=%u fp=%016" PRIx64 "\n", name, pbs, levels,
+                   fnv_sizes(levels), folds, fp);
+        uint64_t x[8], out[4] = {0};
+        for (int i = 0; i < 8; ++i) x[i] = w == 0 ? ~0ull : rnd();  // 2^256 - 1 >= the modulus at 256 bits
+        snprintf(name, sizeof name, "sim_rem_pseudo_mersenne bits=%u", bits);
+        if (status(name, fhe_host_sim_rem_pseudo_mersenne(bits, x, 256, kSecpC, 1, out, 4, &pbs, &levels, &folds), 1)) {
+            printf("%s pbs=%" PRIu64 " levels=%" PRIu64 " folds=%u out=", name, pbs, levels, folds);
+            words_out(out, 4);
+            printf("\n");
+        }
+    }
+    uint64_t pbs, levels, x[8] = {1}, out[4];
+    status("rem_pseudo_mersenne_stats k=255", fhe_host_rem_pseudo_mersenne_stats(512, 255, kSecpC, 1, &pbs, &levels, NULL, 0, NULL, NULL), 0);
+    status("rem_pseudo_mersenne_stats bits=31", fhe_host_rem_pseudo_mersenne_stats(31, 256, kSecpC, 1, &pbs, &levels, NULL, 0, NULL, NULL), 0);
+    status("sim_rem_pseudo_mersenne short out", fhe_host_sim_rem_pseudo_mersenne(512, x, 256, kSecpC, 1, out, 3, NULL, NULL, NULL), 0);
+}
+
+static void mul_add_rem(void) {
+    const int modes[4] = {FHE_BIGUINT_COMPAT, FHE_BIGUINT_FAST, FHE_SIGN_PUBLIC_OPERANDS,
+                          FHE_SIGN_PUBLIC_OPERANDS | FHE_HOST_MUL_THEN_FOLD};
+    uint32_t a[8], b[8], k[8];
+    limbs(a, 8), limbs(b, 8), limbs(k, 8);
+    a[7] >>= 1, k[7] >>= 1;  // public operands below the modulus
+    for (int m = 0; m < 4; ++m)
+        for (int sim = 0; sim <= 1; ++sim) {
+            char name[64];
+            snprintf(name, sizeof name, "biguint_mul_add_rem mode=%#x sim=%d", modes[m], sim);
+            uint64_t out[4] = {0}, cols[10] = {0}, pbs = 0, levels = 0, fp = 0;
+            uint32_t col_bits = 0, folds = 0;
+            memset(g_sizes, 0, sizeof g_sizes);
+            if (!status(name, fhe_host_biguint_mul_add_rem(sim, a, 8, b, 8, k, 8, modes[m], 256, kSecpC, 1, out, 4, cols, 10, &col_bits,
+                                                           &pbs, &levels, g_sizes, CAP, &folds, &fp), 1))
+                continue;
+            printf("%s pbs=%" PRIu64 " levels=%" PRIu64 " sizes=%016" PRIx64 " folds=%u fp=%016" PRIx64 " col_bits=%u out=", name, pbs,
+                   levels, fnv_sizes(levels), folds, fp, col_bits);
+            words_out(out, 4);
+            printf(" cols=");
+            words_out(cols, 10);
+            printf("\n");
+        }
+    status("biguint_mul_add_rem fold of a compat product",
+           fhe_host_biguint_mul_add_rem(0, a, 8, b, 8, k, 8, FHE_BIGUINT_COMPAT | FHE_HOST_MUL_THEN_FOLD, 256, kSecpC, 1, NULL, 0, NULL,
+                                        0, NULL, NULL, NULL, NULL, 0, NULL, NULL), 0);
+}
+
+// 0..3 roots; 4 reads 0, 1; 5 reads 4; 6 reads 2; 7 reads 5, 6; 8 a late root; 9 reads 8
+static void schedule(void) {
+    const int32_t off[11] = {0, 0, 0, 0, 0, 2, 3, 4, 6, 6, 7}, deps[7] = {0, 1, 4, 2, 5, 6, 8};
+    for (int mode = 0; mode <= 1; ++mode) {
+        int32_t level_of[10] = {0}, nlevels = 0;
+        char name[32];
+        snprintf(name, sizeof name, "schedule_levels mode=%d", mode);
+        if (!status(name, fhe_schedule_levels(off, deps, 10, mode, level_of, &nlevels), 1)) continue;
+        printf("%s levels=%d of=", name, nlevels);
+        for (int i = 0; i < 10; ++i) printf(" %d", level_of[i]);
+        printf("\n");
+    }
+    const int32_t bad[2] = {0, 4};  // node 4 reads itself
+    int32_t level_of[10], nlevels;
+    status("schedule_levels dependency on a later node", fhe_schedule_levels(off, bad, 5, 0, level_of, &nlevels), 0);
+}
+
+int main(void) {
+    radix_stats();
+    sim_radix();
+    biguint_dry();
+    biguint_sim();
+    chain_g();
+    rem_pseudo_mersenne();
+    mul_add_rem();
+    schedule();
+    printf(g_failed ? "engine host modes: a required case failed\n" : "engine host modes: every required case ran\n");
+    return g_failed;
+}

@@ -1,4 +1,4 @@
-"""Engine graph statistics (FHE_GRAPH_STATS=1, csrc/radix.cpp Engine::graph_stats) of the benchmark ops:
+"""Engine graph statistics (FHE_GRAPH_STATS=1, csrc/engine.cpp Engine::graph_stats) of the benchmark ops:
 critical-path width per level and two-output blind-rotation candidates (bootstraps sharing their exact
 input at input degree <= 7).  usage: FHE_GRAPH_STATS=1 python3 tools/graph_stats.py"""
 import json
