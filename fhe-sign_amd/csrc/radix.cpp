@@ -1747,13 +1747,45 @@ static Radix barrel4(Engine& e, const Radix& a, const Radix& amount, bool right)
     return radix_clean(e, Radix{cur});
 }
 
+// The amount the shifters read: the amount's value mod the operand's width W = 2n bits, the amount taken
+// at its own full width.  W = 2^nbits: the shifters' nbits low amount bits ARE that, so those widths never
+// come here (shift below) and record what they always did; an amount too narrow to reach W needs nothing
+// either.  Any other W: the bits above nbits change amount mod W, and 2^nbits > W leaves amounts the shifters
+// would shift out entirely, so the amount is reduced first.  amount = sum_i a_i 4^i == S = sum_i a_i (4^i
+// mod W) (mod W), the residue form of the clear-divisor remainder: clear multiples below W of the amount's
+// blocks in exact columns, S < 3 m W for m amount blocks (2 log2(W) + 1 bits or so: 18 at 258, 24 at 4094),
+// one propagation at that width ws, then S mod W there by the multiplier method.  The result is below
+// W <= 2^nbits: its low nbits bits are what the shifters take.  Cost: DESIGN.md (the barrel shifter).
+static Radix shift_amount(Engine& e, const Radix& amount, uint32_t n) {
+    const uint64_t W = 2ull * n;
+    const uint32_t m = amount.nblocks();
+    if (2 * m < 32 && (1ull << (2 * m)) <= W) return amount;
+    std::vector<BigConst> R(m);
+    uint64_t r = 1;
+    for (uint32_t i = 0; i < m; ++i) {
+        R[i] = big_norm(BigConst{r});
+        r = 4 * r % W;
+    }
+    ColProblem P;
+    P.nblocks = (big_bitlen(BigConst{3 * W * m}) + 1) / 2;
+    P.cols.assign(P.nblocks, {});
+    const_products(amount, R, P.nblocks, P.cols, true);
+    std::vector<ColProblem> ps{std::move(P)};
+    const uint32_t ws = ps[0].nblocks;
+    const Radix S = propagate_many(e, ps)[0];
+    // S mod W = S - W floor(S / W) as ONE multiply-add mod 4^ws: S + (4^ws - W) q
+    const Radix q = radix_scalar_div(e, S, BigConst{W});
+    return radix_mul_add(e, q, radix_trivial((1ull << (2 * ws)) - W, 0, ws), S, ws);
+}
+
 // 4-way stages from two blocks up; a one-block (2-bit) operand has a one-bit amount: the 2-way stage
-Radix radix_shr(Engine& e, const Radix& a, const Radix& amount) {
-    return a.nblocks() >= 2 ? barrel4(e, a, amount, true) : barrel(e, a, amount, true);
+static Radix shift(Engine& e, const Radix& a, const Radix& amount, bool right) {
+    const uint32_t n = a.nblocks();
+    if (n & (n - 1)) return barrel4(e, a, shift_amount(e, amount, n), right);
+    return n >= 2 ? barrel4(e, a, amount, right) : barrel(e, a, amount, right);
 }
-Radix radix_shl(Engine& e, const Radix& a, const Radix& amount) {
-    return a.nblocks() >= 2 ? barrel4(e, a, amount, false) : barrel(e, a, amount, false);
-}
+Radix radix_shr(Engine& e, const Radix& a, const Radix& amount) { return shift(e, a, amount, true); }
+Radix radix_shl(Engine& e, const Radix& a, const Radix& amount) { return shift(e, a, amount, false); }
 
 Radix radix_bitand(Engine& e, const Radix& a, const Radix& b) {
     static const auto LUT_AND = lut2([](uint32_t x, uint32_t y) { return x & y; });

@@ -380,7 +380,12 @@ int fhe_radix_cast(fhe_ctx* ctx, const fhe_radix* a, uint32_t num_bits, fhe_radi
 int fhe_radix_min(fhe_ctx* ctx, const fhe_radix* a, const fhe_radix* b, fhe_radix** out);
 int fhe_radix_max(fhe_ctx* ctx, const fhe_radix* a, const fhe_radix* b, fhe_radix** out);
 int fhe_radix_lt(fhe_ctx* ctx, const fhe_radix* a, const fhe_radix* b, fhe_radix** out);
-/* &FheUint >> &FheUint (src/perf_test.rs:36), amount mod num_bits; and << */
+/* &FheUint >> &FheUint (src/perf_test.rs:36), and <<: a shifted by (amount's value) mod (a's num_bits), for
+ * every width of a -- a power of two or not -- and an amount of any width of its own: a narrower amount
+ * counts as zero-extended, a wider one is read at its full width before the reduction (34-bit a, 66-bit
+ * amount 2^65 + 1: a shift by (2^65 + 1) mod 34).  out has a's width.  When a's width is a power of two the
+ * amount's low log2(num_bits) bits are the shift; any other width first reduces the amount mod num_bits
+ * under encryption (a narrow clear-divisor remainder: more bootstraps and levels). */
 int fhe_radix_shr(fhe_ctx* ctx, const fhe_radix* a, const fhe_radix* amount, fhe_radix** out);
 int fhe_radix_shl(fhe_ctx* ctx, const fhe_radix* a, const fhe_radix* amount, fhe_radix** out);
 int fhe_radix_bitand(fhe_ctx* ctx, const fhe_radix* a, const fhe_radix* b, fhe_radix** out);
