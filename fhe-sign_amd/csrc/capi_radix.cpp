@@ -13,6 +13,7 @@
 #include "ct_digest.h"
 #include "oprf.h"
 #include "serial.h"
+#include "switched.h"
 
 using namespace fhe;
 
@@ -1192,6 +1193,112 @@ int fhe_pack_keyswitch_words(fhe_ctx* c, const uint64_t* cts, size_t count, uint
     if (p_words < count * (size_t)c->cp.cols()) return invalid("fhe_pack_keyswitch_words: buffer too small");
     return guarded([&] {
         c->engine->pack_keyswitch_words(cts, count, P, body);
+        return FHE_OK;
+    });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------- modulus-switched stored ciphertexts
+// tfhe-rs' CompressedModulusSwitchedCiphertext of one value (switched.h): the device ends of it.  The host ends
+// (the definitions, the wire kind, fhe_switched_decrypt, the kernel hooks) are in switched.cpp.
+namespace {
+int switched_blocks(fhe_ctx* c, const std::vector<const Block*>& blocks, uint32_t form, uint32_t count,
+                    fhe_switched_list** out, bool rekey = false) {
+    if (rekey && !c->has_rekey) {
+        set_error("no re-keying key installed (fhe_set_rekey_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    return guarded([&] {
+        auto x = std::make_unique<fhe_switched_list>();
+        x->params = rekey ? c->rkp : c->p;  // a re-keyed list is the destination key's
+        x->form = form;
+        x->count = count;
+        for (const Block* b : blocks) {
+            engine_check(b->degree < 16, "compress_switched: block degree >= 16");
+            x->degrees.push_back((uint8_t)b->degree);
+        }
+        x->rows.resize(blocks.size() * switched_row_bytes(x->params.n));
+        c->engine->switched_compress(blocks, x->rows.data(), rekey);
+        *out = x.release();
+        return FHE_OK;
+    });
+}
+int switched_expand_check(fhe_ctx* c, const fhe_switched_list* x, uint32_t form) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x) return invalid("null switched list");
+    if (x->form != form)
+        return invalid(form == FHE_SEEDED_RADIX ? "switched list holds a BigUintFHE, not a radix integer"
+                                                : "switched list holds a radix integer, not a BigUintFHE");
+    uint32_t have = 0, want = 0;
+    if (const char* f = params_differ(x->params, c->p, &have, &want))
+        return invalid(std::string("switched list's ") + f + " (" + std::to_string(have) +
+                       ") differs from the context's server key (" + std::to_string(want) + ")");
+    return FHE_OK;
+}
+int radix_switched(fhe_ctx* c, const fhe_radix* x, fhe_switched_list** out, bool rekey) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x || !out) return invalid("null argument to fhe_radix_compress_switched");
+    std::vector<const Block*> blocks;
+    for (const Block& b : x->r.blocks) blocks.push_back(&b);
+    return switched_blocks(c, blocks, FHE_SEEDED_RADIX, x->bits, out, rekey);
+}
+int biguint_switched(fhe_ctx* c, const fhe_biguint* x, fhe_switched_list** out, bool rekey) {
+    int rc = need_engine(c);
+    if (rc) return rc;
+    if (!x || !out) return invalid("null argument to fhe_biguint_compress_switched");
+    std::vector<const Block*> blocks;
+    for (const Radix& d : x->v.digits) {
+        if (d.nblocks() != kLimbBlocks) return invalid("fhe_biguint_compress_switched: a limb is not a 32-bit radix");
+        for (const Block& b : d.blocks) blocks.push_back(&b);
+    }
+    if (blocks.size() > kCompressedMaxBlocks) return invalid("stored list of more than 2^24 blocks");
+    return switched_blocks(c, blocks, FHE_SEEDED_BIGUINT, (uint32_t)x->v.digits.size(), out, rekey);
+}
+}  // namespace
+
+extern "C" {
+
+int fhe_radix_compress_switched(fhe_ctx* c, const fhe_radix* x, fhe_switched_list** out) {
+    return radix_switched(c, x, out, false);
+}
+int fhe_biguint_compress_switched(fhe_ctx* c, const fhe_biguint* x, fhe_switched_list** out) {
+    return biguint_switched(c, x, out, false);
+}
+int fhe_radix_compress_switched_rekeyed(fhe_ctx* c, const fhe_radix* x, fhe_switched_list** out) {
+    return radix_switched(c, x, out, true);
+}
+int fhe_biguint_compress_switched_rekeyed(fhe_ctx* c, const fhe_biguint* x, fhe_switched_list** out) {
+    return biguint_switched(c, x, out, true);
+}
+
+int fhe_switched_expand_radix(fhe_ctx* c, const fhe_switched_list* x, fhe_radix** out) {
+    int rc = switched_expand_check(c, x, FHE_SEEDED_RADIX);
+    if (rc) return rc;
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        Radix r;
+        r.blocks = c->engine->switched_decompress(*x);
+        *out = wrap(std::move(r), x->count);
+        return FHE_OK;
+    });
+}
+
+int fhe_switched_expand_biguint(fhe_ctx* c, const fhe_switched_list* x, fhe_biguint** out) {
+    int rc = switched_expand_check(c, x, FHE_SEEDED_BIGUINT);
+    if (rc) return rc;
+    if (!out) return FHE_ERR_INVALID;
+    return guarded([&] {
+        const Blocks all = c->engine->switched_decompress(*x);
+        auto v = std::make_unique<fhe_biguint>();
+        for (size_t at = 0; at < all.size(); at += kLimbBlocks) {
+            Radix d;
+            d.blocks.assign(all.begin() + at, all.begin() + at + kLimbBlocks);
+            v->v.digits.push_back(std::move(d));
+        }
+        *out = v.release();
         return FHE_OK;
     });
 }

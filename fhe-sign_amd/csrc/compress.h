@@ -134,6 +134,9 @@ void expand_seeded_compression_key_host(const fhe_seeded_compression_key& sck, f
 void pack_keyswitch_host(const fhe_compression_key& key, const uint64_t* cts, size_t B, uint8_t* packed);
 // blocks of a form / count pair (FHE_SEEDED_RADIX: num_bits / 2, FHE_SEEDED_BIGUINT: 16 nlimbs)
 bool compressed_nblocks(uint32_t form, uint32_t count, size_t* nblocks, std::string* why);
+// sum v_k 4^k of decoded block values (each < 16), per value (radix) or per 32-bit limb (BigUintFHE: 16 blocks,
+// limb i at bits 32 i), the carries of blocks above degree 3 kept inside it -- as fhe_radix_decrypt assembles
+void assemble_block_values(const std::vector<uint32_t>& vals, uint32_t form, uint64_t* words, size_t nwords);
 // the first main-parameter field in which a and b differ, or null
 const char* params_differ(const Params& a, const Params& b, uint32_t* have, uint32_t* want);
 }  // namespace fhe

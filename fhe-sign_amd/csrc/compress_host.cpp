@@ -100,6 +100,29 @@ const char* params_differ(const Params& a, const Params& b, uint32_t* have, uint
     return nullptr;
 }
 
+void assemble_block_values(const std::vector<uint32_t>& vals, uint32_t form, uint64_t* words, size_t nwords) {
+    const size_t B = vals.size();
+    std::memset(words, 0, nwords * 8);
+    const size_t per = form == FHE_SEEDED_RADIX ? B : 16;
+    for (size_t base = 0; base < B; base += per ? per : 1) {
+        const uint32_t vbits = (uint32_t)(2 * per);
+        std::vector<uint64_t> acc(vbits / 64 + 2, 0);
+        for (size_t k = 0; k < per; ++k) {
+            unsigned __int128 add = (unsigned __int128)vals[base + k] << ((2 * k) % 64);
+            for (size_t w = 2 * k / 64; w < acc.size() && add; ++w) {
+                const unsigned __int128 s2 = (unsigned __int128)acc[w] + (uint64_t)add;
+                acc[w] = (uint64_t)s2;
+                add = (add >> 64) + (s2 >> 64);
+            }
+        }
+        for (uint32_t b = 0; b < vbits; ++b)
+            if ((acc[b / 64] >> (b % 64)) & 1) {
+                const size_t o = 2 * base + b;
+                words[o / 64] |= 1ull << (o % 64);
+            }
+    }
+}
+
 namespace {
 unsigned pool_size(size_t items) {
     unsigned nth = std::thread::hardware_concurrency();
@@ -687,26 +710,7 @@ int fhe_compressed_decrypt(const fhe_compression_private_key* priv, const fhe_co
             }
             in += cp.glwe_bytes(nb);
         }
-        // sum v_k 4^k, per value (radix) or per 32-bit limb (BigUintFHE), carries kept inside it
-        std::memset(words, 0, nwords * 8);
-        const size_t per = x->form == FHE_SEEDED_RADIX ? B : 16;
-        for (size_t base = 0; base < B; base += per ? per : 1) {
-            const uint32_t vbits = (uint32_t)(2 * per);
-            std::vector<uint64_t> acc(vbits / 64 + 2, 0);
-            for (size_t k = 0; k < per; ++k) {
-                unsigned __int128 add = (unsigned __int128)vals[base + k] << ((2 * k) % 64);
-                for (size_t w = 2 * k / 64; w < acc.size() && add; ++w) {
-                    const unsigned __int128 s2 = (unsigned __int128)acc[w] + (uint64_t)add;
-                    acc[w] = (uint64_t)s2;
-                    add = (add >> 64) + (s2 >> 64);
-                }
-            }
-            for (uint32_t b = 0; b < vbits; ++b)
-                if ((acc[b / 64] >> (b % 64)) & 1) {
-                    const size_t o = 2 * base + b;
-                    words[o / 64] |= 1ull << (o % 64);
-                }
-        }
+        assemble_block_values(vals, x->form, words, nwords);
         return FHE_OK;
     });
 }

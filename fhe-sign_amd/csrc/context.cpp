@@ -169,6 +169,10 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
         const int rc = release_public_key();
         if (rc) return rc;
     }
+    if (has_rekey) {  // nor a re-keying key
+        const int rc = release_rekey();
+        if (rc) return rc;
+    }
     if (d_ms) FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read it
     ms_cap = 0;
     FHE_HIP_CHECK(d_ms.reset());
@@ -343,18 +347,43 @@ int fhe_ctx::ensure_ks(size_t count) {
 }
 
 hipError_t fhe_ctx::keyswitch(const uint64_t* in, const fhe::PbsDesc* desc, size_t count) {
+    return keyswitch(main_ks(), in, desc, count);
+}
+
+hipError_t fhe_ctx::keyswitch(const KsKeys& ks, const uint64_t* in, const fhe::PbsDesc* desc, size_t count) {
     hipError_t e;
     if (ks_kernel == FHE_KS_MFMA) {
         if (ensure_ks(count) != FHE_OK) return hipErrorOutOfMemory;
-        e = launch_keyswitch_mfma(in, desc, (int)count, d_ksk_planes, d_ks_digits, d_ks_body, d_ms, ms_stride, (int)p.n,
-                                  stream);
+        e = launch_keyswitch_mfma(in, desc, (int)count, ks.planes, d_ks_digits, d_ks_body, ks.ms, ks.ms_stride, ks.n, stream);
     } else if (desc) {
-        e = launch_keyswitch_desc(desc, (int)count, d_ksk, d_ms, ms_stride, (int)p.n, stream);
+        e = launch_keyswitch_desc(desc, (int)count, ks.ksk, ks.ms, ks.ms_stride, ks.n, stream);
     } else {
-        e = launch_keyswitch(in, (int)count, d_ksk, d_ms, ms_stride, (int)p.n, stream);
+        e = launch_keyswitch(in, (int)count, ks.ksk, ks.ms, ks.ms_stride, ks.n, stream);
     }
     if (e != hipSuccess || ms_mode != FHE_MS_CENTERED) return e;
-    return launch_ms_center(d_ms, count, p.n, (size_t)ms_stride, stream);
+    return launch_ms_center(ks.ms, count, (uint32_t)ks.n, (size_t)ks.ms_stride, stream);
+}
+
+int fhe_ctx::ensure_rk_ms(size_t count) {
+    if (count <= rk_ms_cap) return FHE_OK;
+    if (d_rk_ms) FHE_HIP_CHECK(hipStreamSynchronize(stream));
+    rk_ms_cap = 0;
+    const size_t cap = std::max<size_t>(count, 256);
+    rk_ms_stride = (int)((rkp.n + 1 + 7) / 8 * 8);
+    FHE_HIP_CHECK(d_rk_ms.grow(cap * rk_ms_stride));
+    rk_ms_cap = cap;
+    return FHE_OK;
+}
+
+int fhe_ctx::release_rekey() {
+    if (stream) FHE_HIP_CHECK(hipStreamSynchronize(stream));
+    rk_ms_cap = 0;
+    rk_ms_stride = 0;
+    (void)d_rk_ksk.reset();
+    (void)d_rk_planes.reset();
+    (void)d_rk_ms.reset();
+    has_rekey = false;
+    return FHE_OK;
 }
 
 hipError_t fhe_ctx::blind_rotate(const fhe::PbsDesc* desc, const uint32_t* lut_idx, uint64_t* out, size_t count) {
@@ -653,6 +682,10 @@ int release_key(fhe_ctx* c) {
         const int rc = c->release_public_key();
         if (rc) return rc;
     }
+    if (c->has_rekey) {  // and a re-keying key
+        const int rc = c->release_rekey();
+        if (rc) return rc;
+    }
     if (c->has_key) FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->has_key = false;
     FHE_HIP_CHECK(c->d_ksk.reset());
@@ -879,6 +912,58 @@ int fhe_set_server_key_seeded(fhe_ctx* c, const fhe_seeded_server_key* ssk) {
     };
     rc = body();
     return rc ? drop_key(c, rc) : FHE_OK;
+}
+
+// The re-keying key's install: the bodies are the only upload (82 KB); seeded_key.hip's KSK expansion regenerates
+// the masks under the key's own stream id, ks_mfma.hip derives the byte planes.  Same device words as an upload
+// of expand_rekey_key_host's KSK.
+int fhe_set_rekey_key(fhe_ctx* c, const fhe_rekey_key* key) {
+    if (!c || !key) {
+        set_error("null argument to fhe_set_rekey_key");
+        return FHE_ERR_INVALID;
+    }
+    if (!c->has_key) {
+        set_error("no server key installed (fhe_set_server_key)");
+        return FHE_ERR_NO_KEY;
+    }
+    const Params& p = key->params;
+    Params checked;
+    const char* why = nullptr;
+    if (!Params::from_c(p.to_c(), &checked, &why) || !seeded_key_rows_ok(p, &why) ||
+        key->bodies.size() != (size_t)kPolySize * p.ks_level) {
+        set_error(why ? why : "re-keying key: body count differs from what its parameters need");
+        return FHE_ERR_UNSUPPORTED;
+    }
+    uint32_t have = 0, want = 0;
+    if (const char* f = rekey_params_differ(p, c->p, &have, &want)) {
+        set_error(std::string("re-keying key's ") + f + " (" + std::to_string(have) + ") differs from the installed server key's (" +
+                  std::to_string(want) + ")");
+        return FHE_ERR_INVALID;
+    }
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    int rc = c->release_rekey();
+    if (rc) return rc;
+    const KeyWords k = bytes_key(key->seed);
+    const int rows = (int)(kPolySize * p.ks_level);
+    DeviceBuf<uint64_t> d_kb;  // freed on return, behind the wait below
+    auto body = [&]() -> int {
+        FHE_HIP_CHECK(d_kb.grow(key->bodies.size()));
+        FHE_HIP_CHECK(c->d_rk_ksk.grow((size_t)rows * (p.n + 1)));
+        FHE_HIP_CHECK(c->d_rk_planes.grow(fhe::ks_planes_bytes((int)p.n)));
+        FHE_HIP_CHECK(hipMemcpyAsync(d_kb, key->bodies.data(), key->bodies.size() * 8, hipMemcpyHostToDevice, c->stream));
+        FHE_HIP_CHECK(launch_expand_ksk(chacha_stream_key(k.data(), kStreamRekeyKsk), c->d_rk_ksk, d_kb, rows, (int)p.n, c->stream));
+        FHE_HIP_CHECK(launch_ksk_to_planes(c->d_rk_ksk, (int)p.n, c->d_rk_planes, c->stream));
+        FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+        return FHE_OK;
+    };
+    rc = body();
+    if (rc) {
+        (void)c->release_rekey();
+        return rc;
+    }
+    c->rkp = p;
+    c->has_rekey = true;
+    return FHE_OK;
 }
 
 int fhe_ctx_export_fourier_bsk(fhe_ctx* c, double* out, size_t len) {

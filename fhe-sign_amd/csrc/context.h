@@ -171,6 +171,19 @@ struct fhe_ctx {
     // keyswitch of `count` inputs (contiguous big LWE in `in`, or descriptors) into d_ms; in centered mode
     // the rows' bodies are then corrected in place (k_ms_center), behind the keyswitch on the stream
     hipError_t keyswitch(const uint64_t* in, const fhe::PbsDesc* desc, size_t count);
+    // The key set one keyswitch runs under, in the spirit of BrKeys below: the KSK in its two forms, the
+    // destination dimension and the workspace the rows go to.  main_ks() is what every level uses; rekey_ks() the
+    // re-keying key (fhe_set_rekey_key: another small key, its own workspace -- d_ms' stride is sized for p.n).
+    struct KsKeys {
+        const uint64_t* ksk;
+        const int8_t* planes;
+        int n;
+        uint64_t* ms;
+        int ms_stride;
+    };
+    KsKeys main_ks() const { return {d_ksk, d_ksk_planes, (int)p.n, d_ms, ms_stride}; }
+    KsKeys rekey_ks() const { return {d_rk_ksk, d_rk_planes, (int)rkp.n, d_rk_ms, rk_ms_stride}; }
+    hipError_t keyswitch(const KsKeys& ks, const uint64_t* in, const fhe::PbsDesc* desc, size_t count);
     int ensure_stage(size_t count);
     int sync_luts();
     int register_lut(const uint32_t* table, uint32_t* id);
@@ -228,4 +241,17 @@ struct fhe_ctx {
     fhe::DeviceBuf<uint64_t> d_rr_z;
     int ensure_rr(size_t chunks);
     int release_public_key();  // waits for the stream, frees all of the above
+
+    // Re-keying key (fhe_set_rekey_key; dropped by every server-key install): the expanded KSK to the destination's
+    // small key (FHE_KS_VALU reads it) and its byte planes, the destination's parameters, and a row workspace of
+    // `rk_ms_cap` rows whose stride is sized for the destination's dimension.
+    bool has_rekey = false;
+    fhe::Params rkp;
+    fhe::DeviceBuf<uint64_t> d_rk_ksk;
+    fhe::DeviceBuf<int8_t> d_rk_planes;
+    fhe::DeviceBuf<uint64_t> d_rk_ms;
+    size_t rk_ms_cap = 0;
+    int rk_ms_stride = 0;
+    int ensure_rk_ms(size_t count);
+    int release_rekey();  // waits for the stream, frees all of the above
 };

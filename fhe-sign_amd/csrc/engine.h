@@ -23,6 +23,8 @@
 #include "kernels.h"
 #include "public_key.h"
 
+struct fhe_switched_list;  // switched.h
+
 namespace fhe {
 
 constexpr uint32_t kMsgBits = 2;
@@ -252,6 +254,19 @@ public:
     // block.  Independent of fhe_ctx_set_modulus_switch: the rows are not centered, their phase is the
     // randomness.  Device engines only.
     Blocks oprf(const uint8_t seed[32], size_t count, uint32_t bits, uint32_t tail_bits = 0);
+    // Modulus-switched stored ciphertexts (switched.h).  switched_compress: the blocks -> their stored rows, n x
+    // switched_row_bytes(p.n) bytes, byte for byte fhe_switched_compress_host of the blocks' exported rows in
+    // the context's modulus-switch mode.  Inputs made real as rerandomize's (pending producers launched: a plain
+    // flush, rank-local under a communicator; a lazy block combined; a trivial block enters as (0, delta value));
+    // a block whose noise label admits no lookup (> kMaxNoise) is refused.  In chunks of the bootstrap workspace
+    // as it stands (oprf's rule): the context's keyswitch through one-term descriptors, k_ms_pack, one download.
+    // switched_decompress: n fresh slots (noise 1, degrees from the list), stream-ordered like decompress -- no
+    // flush, no collective: upload, k_ms_unpack into the workspace, the blind rotation under the main key set with
+    // the identity table; no keyswitch and no k_ms_center, whatever the mode.  Device engines only.
+    // rekey: the keyswitch runs under the installed re-keying key (fhe_set_rekey_key) into its own workspace, and
+    // the rows are the destination key's: switched_row_bytes(rkp.n) bytes each.
+    void switched_compress(const std::vector<const Block*>& blocks, uint8_t* rows, bool rekey = false);
+    Blocks switched_decompress(const fhe_switched_list& x);
     void download(const Block& b, uint64_t* ct);
     // the slot blocks' ciphertexts -> host, contiguous (one gather + one copy + one wait instead of a
     // round trip per block: the decryption of a 256-bit result is 128-144 blocks)
@@ -328,7 +343,10 @@ private:
     size_t desc_cap_ = 0;  // of h_desc_; 0 while either is not grown
     int desc_turn_ = 0;
     DeviceBuf<PbsDesc> d_desc_;
-    DeviceBuf<PbsDesc> d_oprf_desc_;  // oprf's descriptors, one chunk (the level descriptors above may be in flight)
+    // the eager ops' descriptors (oprf, the stored form), one chunk (the level descriptors above may be in flight)
+    DeviceBuf<PbsDesc> d_oprf_desc_;
+    void ensure_eager_desc(size_t chunk);
+    DeviceBuf<uint32_t> d_sw_packed_;  // the stored form's packed rows, one chunk (switched.h)
     void ensure_desc(size_t n);
     void graph_stats(const std::vector<std::vector<int32_t>>& deps);
     void flush_tail(size_t k0);

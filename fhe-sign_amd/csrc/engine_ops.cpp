@@ -1,6 +1,6 @@
 // engine_ops.cpp -- the engine's eager device operations (engine.h): uploads and downloads, the seeded,
 // compact and compressed forms expanded into fresh slots, re-randomization, digests, oblivious pseudo-random
-// blocks, the broadcasts' adopt / gather.  Each runs at once on the context's stream, outside the deferred
+// blocks, the modulus-switched stored form, the broadcasts' adopt / gather.  Each runs at once on the context's stream, outside the deferred
 // graph (engine.cpp), and follows one idiom:
 //   * result blocks come from fresh_blocks(), their slot pointers from slot_ptrs();
 //   * what goes through the upload staging is stated once, in order, on a Stage cursor that issues the copy,
@@ -11,6 +11,7 @@
 #include "ct_digest.h"
 #include "keygen.h"
 #include "oprf.h"
+#include "switched.h"
 
 #include <algorithm>
 #include <cstring>
@@ -291,10 +292,7 @@ Blocks Engine::oprf(const uint8_t seed[32], size_t count, uint32_t bits, uint32_
     constexpr size_t kOprfChunk = 4096;
     const size_t chunk = std::min(n, std::max(ctx_->ms_cap, kOprfChunk));
     engine_check(ctx_->ensure_ms(chunk) == FHE_OK, "bootstrap workspace");
-    if (!d_oprf_desc_.fits(chunk)) {
-        hip_check(hipStreamSynchronize(ctx_->stream), "oprf descriptors sync");
-        hip_check(d_oprf_desc_.grow(std::max<size_t>(chunk, 256)), "oprf descriptors");
-    }
+    ensure_eager_desc(chunk);
     std::vector<uint32_t> degrees(n, (1u << bits) - 1);
     if (tail_bits) degrees[count] = (1u << tail_bits) - 1;
     Blocks out = fresh_blocks(degrees);
@@ -315,6 +313,102 @@ Blocks Engine::oprf(const uint8_t seed[32], size_t count, uint32_t bits, uint32_
         hip_check(launch_oprf_body_add(d_oprf_desc_, (uint32_t)m, ctx_->stream), "oprf body constant");
     }
     hip_check(hipStreamSynchronize(ctx_->stream), "oprf sync");  // host buffers may go
+    pbs_count += n;
+    return out;
+}
+
+void Engine::ensure_eager_desc(size_t chunk) {
+    if (d_oprf_desc_.fits(chunk)) return;
+    hip_check(hipStreamSynchronize(ctx_->stream), "eager descriptors sync");
+    hip_check(d_oprf_desc_.grow(std::max<size_t>(chunk, 256)), "eager descriptors");
+}
+
+// ------------------------------------------------------------------ modulus-switched stored ciphertexts
+namespace {
+// the workspace as it stands (at least this many rows) is the chunk of the stored form's two ops, as of oprf
+constexpr size_t kSwitchedChunk = 4096;
+}  // namespace
+
+void Engine::switched_compress(const std::vector<const Block*>& blocks, uint8_t* rows, bool rekey) {
+    engine_check(host_mode_ == kDevice, "compress_switched on a host-only engine");
+    if (rekey && !ctx_->has_rekey) throw EngineError(FHE_ERR_NO_KEY, "no re-keying key installed (fhe_set_rekey_key)");
+    const size_t n = blocks.size();
+    engine_check(n <= kCompressedMaxBlocks, "stored list of more than 2^24 blocks");
+    if (n == 0) return;
+    const Params& p = ctx_->p;
+    Blocks real;
+    const std::vector<const Block*> in = realize(*this, blocks, "compress_switched", real);
+    // one-term descriptors: the keyswitch reads the slot as it is; a trivial block is the constant alone
+    std::vector<PbsDesc> desc(n);
+    std::memset(desc.data(), 0, n * sizeof(PbsDesc));
+    for (size_t i = 0; i < n; ++i) {
+        const Block& b = *in[i];
+        engine_check(b.noise <= kMaxNoise, "compress_switched: block noise above the budget of a lookup");
+        if (b.trivial()) {
+            desc[i].cst = trivial_body(b, p.delta(), "compress_switched");
+            continue;
+        }
+        desc[i].src[0] = b.ptr();
+        desc[i].coef[0] = 1;
+        desc[i].nterms = 1;
+    }
+    const size_t chunk = std::min(n, std::max(rekey ? ctx_->rk_ms_cap : ctx_->ms_cap, kSwitchedChunk));
+    engine_check((rekey ? ctx_->ensure_rk_ms(chunk) : ctx_->ensure_ms(chunk)) == FHE_OK, "row workspace");
+    ensure_eager_desc(chunk);
+    const fhe_ctx::KsKeys ks = rekey ? ctx_->rekey_ks() : ctx_->main_ks();
+    const uint32_t nd = (uint32_t)ks.n;  // the rows' dimension: the destination key's when re-keying
+    const size_t dev_bytes = switched_dev_row_bytes(nd), bytes = switched_row_bytes(nd);
+    if (!d_sw_packed_.fits(chunk * dev_bytes / 4)) {
+        hip_check(hipStreamSynchronize(ctx_->stream), "stored rows sync");
+        hip_check(d_sw_packed_.grow(std::max<size_t>(chunk, 256) * dev_bytes / 4), "stored rows");
+    }
+    std::vector<uint8_t> stage(chunk * dev_bytes);
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        hip_check(hipMemcpyAsync(d_oprf_desc_, desc.data() + at, m * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream),
+                  "compress_switched descriptors");
+        hip_check(ctx_->keyswitch(ks, nullptr, d_oprf_desc_, m), "compress_switched keyswitch");
+        hip_check(launch_ms_pack(ks.ms, d_sw_packed_, m, nd, ctx_->stream), "row packing");
+        hip_check(hipMemcpyAsync(stage.data(), d_sw_packed_, m * dev_bytes, hipMemcpyDeviceToHost, ctx_->stream),
+                  "compress_switched download");
+        wait_check(ctx_, "compress_switched");
+        // the device keeps every row on whole 12-byte groups; the wire starts a row on the next byte
+        for (size_t i = 0; i < m; ++i) std::memcpy(rows + (at + i) * bytes, stage.data() + i * dev_bytes, bytes);
+    }
+}
+
+Blocks Engine::switched_decompress(const fhe_switched_list& x) {
+    engine_check(host_mode_ == kDevice, "decompress on a host-only engine");
+    const size_t n = x.degrees.size();
+    if (n == 0) return {};
+    const Params& p = ctx_->p;
+    const size_t dev_bytes = switched_dev_row_bytes(p.n), bytes = switched_row_bytes(p.n);
+    engine_check(x.params.n == p.n && x.rows.size() == n * bytes, "stored list: rows of another LWE dimension");
+    std::vector<uint32_t> ident(p.msg_carry());
+    for (uint32_t v = 0; v < ident.size(); ++v) ident[v] = v;
+    uint32_t lut = 0;
+    engine_check(ctx_->register_lut(ident.data(), &lut) == FHE_OK && ctx_->sync_luts() == FHE_OK, "identity table");
+    const size_t chunk = std::min(n, std::max(ctx_->ms_cap, kSwitchedChunk));
+    engine_check(ctx_->ensure_ms(chunk) == FHE_OK, "bootstrap workspace");
+    ensure_eager_desc(chunk);
+    if (!d_sw_packed_.fits(chunk * dev_bytes / 4)) {
+        hip_check(hipStreamSynchronize(ctx_->stream), "stored rows sync");
+        hip_check(d_sw_packed_.grow(std::max<size_t>(chunk, 256) * dev_bytes / 4), "stored rows");
+    }
+    Blocks out = fresh_blocks(std::vector<uint32_t>(x.degrees.begin(), x.degrees.end()));
+    const std::vector<PbsDesc> desc = bare_descs(out, lut, 0);
+    std::vector<uint8_t> stage(chunk * dev_bytes, 0);
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        for (size_t i = 0; i < m; ++i) std::memcpy(stage.data() + i * dev_bytes, x.rows.data() + (at + i) * bytes, bytes);
+        hip_check(hipMemcpyAsync(d_sw_packed_, stage.data(), m * dev_bytes, hipMemcpyHostToDevice, ctx_->stream),
+                  "stored rows upload");
+        hip_check(launch_ms_unpack(d_sw_packed_, ctx_->d_ms, m, p.n, ctx_->stream), "row unpacking");
+        hip_check(hipMemcpyAsync(d_oprf_desc_, desc.data() + at, m * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream),
+                  "decompress descriptors");
+        hip_check(ctx_->blind_rotate(ctx_->main_keys(), d_oprf_desc_, nullptr, nullptr, m), "decompression blind rotate");
+        hip_check(hipStreamSynchronize(ctx_->stream), "decompress sync");  // the stage and the descriptors may be reused
+    }
     pbs_count += n;
     return out;
 }

@@ -417,6 +417,53 @@ void expand_seeded_server_key_host(const fhe_seeded_server_key& ssk, fhe_server_
     });
 }
 
+// ------------------------------------------------------------------------------ re-keying key
+const char* rekey_params_differ(const Params& a, const Params& b, uint32_t* have, uint32_t* want) {
+    const struct {
+        const char* name;
+        uint32_t have, want;
+    } fields[] = {{"message_modulus", a.message_modulus, b.message_modulus}, {"carry_modulus", a.carry_modulus, b.carry_modulus},
+                  {"ks_base_log", a.ks_base_log, b.ks_base_log},             {"ks_level", a.ks_level, b.ks_level},
+                  {"pbs_base_log", a.pbs_base_log, b.pbs_base_log},          {"glwe_noise_log2", a.glwe_noise_log2, b.glwe_noise_log2}};
+    for (const auto& f : fields)
+        if (f.have != f.want) {
+            *have = f.have;
+            *want = f.want;
+            return f.name;
+        }
+    return nullptr;
+}
+
+void generate_rekey_key(const fhe_client_key* src, fhe_client_key* dst, const uint8_t seed[32], fhe_rekey_key* out) {
+    const Params& p = dst->params;
+    const uint32_t n = p.n, L = p.ks_level, krows = kPolySize * L;
+    out->params = p;
+    std::memcpy(out->seed, seed, 32);
+    // the noise words first: the destination's encryption stream advances by exactly krows words
+    out->bodies.resize(krows);
+    dst->enc_rng.fill_u64(out->bodies.data(), krows);
+    const uint64_t *s = dst->lwe_sk.data(), *S = src->glwe_sk.data();
+    seeded_key_rows(bytes_key(seed), kStreamRekeyKsk, krows, [&](uint32_t r, ChaChaStream& masks) {
+        std::vector<uint64_t> a(n);
+        masks.fill_u64(a.data(), n);
+        uint64_t dot = 0;
+        for (uint32_t t = 0; t < n; ++t) dot += a[t] * s[t];
+        const uint32_t j = r / L, l = r % L;
+        const int64_t e = tuniform_of(out->bodies[r], p.lwe_noise_log2);
+        out->bodies[r] = dot + (S[j] << (64 - p.ks_base_log * (l + 1))) + (uint64_t)e;
+    });
+}
+
+void expand_rekey_key_host(const fhe_rekey_key& key, std::vector<uint64_t>* ksk) {
+    const uint32_t n = key.params.n, krows = kPolySize * key.params.ks_level;
+    ksk->assign((size_t)krows * (n + 1), 0);
+    seeded_key_rows(bytes_key(key.seed), kStreamRekeyKsk, krows, [&](uint32_t r, ChaChaStream& masks) {
+        uint64_t* row = ksk->data() + (size_t)r * (n + 1);
+        masks.fill_u64(row, n);
+        row[n] = key.bodies[r];
+    });
+}
+
 static void encrypt_with(ChaChaStream& rng, const fhe_client_key* ck, uint64_t pt, uint64_t* ct) {
     rng.fill_u64(ct, kBigDim);
     uint64_t dot = 0;

@@ -126,6 +126,10 @@ constexpr uint32_t kStreamRerandNoise = 110;
 // are the first n u64 words of ChaCha blocks [b R, (b + 1) R), R = ceil(n / 8) -- a row starts on a block
 // boundary, whatever the workspace's stride or the number of rows is.
 constexpr uint32_t kStreamOprf = 111;
+// Mask stream of a re-keying key (fhe_rekey_key below), keyed by its PUBLIC seed, with the seeded server key's
+// row stride: row r's n_dst mask words are u64 words [2048 r, 2048 r + n_dst) -- launch_expand_ksk serves it
+// unchanged under this stream's key.
+constexpr uint32_t kStreamRekeyKsk = 112;
 
 }  // namespace fhe
 
@@ -172,7 +176,32 @@ struct fhe_seeded_server_key {
     std::vector<uint64_t> bsk_bodies;  // [ggsw][row][N]
 };
 
+// A re-keying key: tfhe-rs' KeySwitchingKey from the big key of a source client key to the small key of a
+// destination client key.  Host only and seeded only (the full form would be 2048 ks_level
+// (n_dst + 1) words for nothing).  `params` are the DESTINATION's; the source agrees with them in everything but
+// lwe_dimension, lwe_noise_log2 and grouping.  Row r = j ks_level + l:
+//   mask word t < n_dst = u64 word 2048 r + t of ChaChaStream(bytes_key(seed), kStreamRekeyKsk)
+//   bodies[r] = <mask, dst.lwe_sk> + (src.glwe_sk[j] << (64 - ks_base_log (l + 1))) + e
+// With it the keyswitch of a block under the source key is a small LWE row under the destination's: a stored
+// value (switched.h) the destination's client key reads and the destination's server key bootstraps.
+// One seed, one object: a seed is never reused for a second key, or for a seeded ciphertext, under the same
+// client key.
+struct fhe_rekey_key {
+    fhe::Params params;
+    uint8_t seed[32] = {};
+    std::vector<uint64_t> bodies;  // [N * ks_level]
+};
+
 namespace fhe {
+// The re-keying key from src to dst under the public `seed`.  Noise: exactly N ks_level words of dst->enc_rng,
+// in row order, drawn before the threaded pass: e = tuniform_of(w, dst lwe_noise_log2).  The caller has checked
+// that the two parameter sets agree (rekey_params_differ).
+void generate_rekey_key(const fhe_client_key* src, fhe_client_key* dst, const uint8_t seed[32], fhe_rekey_key* out);
+// the full KSK of a re-keying key, [N][ks_level][n_dst + 1] in the server key's layout: masks regenerated,
+// bodies in place.  The word-for-word definition of the device install (fhe_set_rekey_key).
+void expand_rekey_key_host(const fhe_rekey_key& key, std::vector<uint64_t>* ksk);
+// the first field a re-keying key's two sides must share in which a and b differ, or null
+const char* rekey_params_differ(const Params& a, const Params& b, uint32_t* have, uint32_t* want);
 void generate_keys(const Params& p, const KeyWords& key, fhe_client_key* ck, fhe_server_key* sk);
 // The seeded server key of ck under the public `seed`.  Noise: exactly N ks_level + ggsw 2 N words of
 // ck->enc_rng, the KSK rows' first (row order), then the BSK's in (q, rho, m) order, all drawn before the

@@ -29,6 +29,12 @@
 //           2048 pks_level N' u64 packing-key bodies | k' N' 2 2048 u64 BSK body polynomials -- 128 +
 //           8 (2048 pks_level N' + 4096 k' N') bytes in all.  The masks are not stored: streams 107 (packing
 //           KSK) and 108 (decompression BSK) under the seed, one row per 256 ChaCha blocks (compress.h).
+//   kind 13 (modulus-switched stored list, switched.cpp): params | u32 form | u32 count | u32 B | B degree bytes
+//           (each < 16) | B rows of ceil(12 (n + 1) / 8) bytes, the 12-bit stream of a row's n + 1 values, the pad
+//           nibble of an odd n + 1 zero -- 80 + B (1 + ceil(12 (n + 1) / 8)) bytes in all.
+//   kind 14 (re-keying key, switched.cpp): the DESTINATION's params | 32 seed bytes | 2048 ks_level u64 body words
+//           -- 100 + 8 (2048 ks_level) bytes in all.  The masks are not stored: stream 112 under the seed, one
+//           row per 256 ChaCha blocks (keys.h fhe_rekey_key).
 // Readers check magic, version, kind, length, checksum, parameter ranges and every count before
 // touching memory, and refuse block metadata (degree, noise) outside the radix layer's budget, so a
 // corrupted or hostile buffer fails with FHE_ERR_INVALID instead of poisoning the scheduler.
@@ -45,7 +51,8 @@ namespace fhe::ser {
 
 enum Kind : uint32_t { kClientKey = 1, kServerKey = 2, kRadix = 3, kBigUint = 4, kSeeded = 5, kSeededServerKey = 6,
                        kCompressionPrivateKey = 7, kCompressionKey = 8, kCompressedList = 9,
-                       kPublicKey = 10, kCompactList = 11, kSeededCompressionKey = 12 };
+                       kPublicKey = 10, kCompactList = 11, kSeededCompressionKey = 12, kSwitchedList = 13,
+                       kRekeyKey = 14 };
 constexpr uint32_t kVersion = 2;  // 2: params carry the blind-rotation grouping (9th word); 1 still read
 constexpr size_t kHeaderBytes = 32;
 

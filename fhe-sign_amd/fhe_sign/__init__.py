@@ -25,6 +25,10 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
                                       generate_oblivious_pseudo_random[_bounded]: a seed becomes an encrypted uniformly
                                       random value on the GPU, one blind rotation per block, no keyswitch, no upload
                                       (oprf_rows_host, oprf_lut_host: the host definitions)
+  x.compress_switched() / SwitchedCiphertextList   tfhe's FheUint::compress(): the keyswitched, modulus-switched rows,
+                                      12 bits per value and no extra key; .decrypt(client_key) with the small key
+                                      alone, .decompress() by one blind rotation per block (switched_pack_host,
+                                      switched_unpack_host, SwitchedCiphertextList.compress_host: the host definitions)
   Schnorr.sign_fhe_with_k0 / sign_fhe src/schnorr.rs:154-290
   x.rem_pseudo_mersenne(k, c) / Schnorr.eval_s / sign_fhe_with_k0(reduce=True)   x mod (2^k - c) by folds (both
                                       secp256k1 moduli: SECP256K1_N_C, SECP256K1_P_C); the signer reduces s mod n
@@ -32,13 +36,14 @@ Mirrors the reference crate's surface (coset-io/fhe-sign):
 All ciphertext arithmetic runs on the GPU through lib/libfhe_rocm.so; this package only marshals.
 """
 from ._lib import CompressionParams, FheError, FheParams, load  # noqa: F401
-from .core import (ClientKey, CompactPublicKey, CompressedCompressionKey, CompressedServerKey, CompressionKey, CompressionKeys, CompressionPrivateKey, Context, ServerKey, comm_unique_id, default_params,  # noqa: F401
-                   default_compression_params, generate_keys, ms_center_host, ms_stride, multi_bit_params, oprf_lut_host, oprf_rows_host, tuning)
+from .core import (ClientKey, RekeyKey, CompactPublicKey, CompressedCompressionKey, CompressedServerKey, CompressionKey, CompressionKeys, CompressionPrivateKey, Context, ServerKey, comm_unique_id, default_params,  # noqa: F401
+                   default_compression_params, generate_keys, ms_center_host, ms_stride, multi_bit_params, oprf_lut_host, oprf_rows_host, tuning,
+                   switched_pack_host, switched_row_bytes, switched_unpack_host)
 from .integer import (  # noqa: F401,E402
     COMPAT, FAST, PUBLIC, BigUintFHE, FheBool, FheUint, FheUint8, FheUint32, FheUint64, FheUint128, FheUint256, set_server_key,
     LEVEL_SPLIT, level_log, rank_pbs, stats, to_u32_digits, SECP256K1_N_C, SECP256K1_P_C,
     CompressedBigUintFHE, CompressedFheUint, CompressedFheUint8, CompressedFheUint32, CompressedFheUint64,
-    CompressedFheUint128, CompressedFheUint256, CompressedCiphertextList,
+    CompressedFheUint128, CompressedFheUint256, CompressedCiphertextList, SwitchedCiphertextList,
     CompactCiphertextList, CompactCiphertextListBuilder,
     rerandomization_seed, rerandomize_host, rerandomize_rows, rerandomize_zero_host,
     ReRandomizationContext, ct_digest_host, ct_digest_rows, ct_value_digest_host, re_randomize_bound)

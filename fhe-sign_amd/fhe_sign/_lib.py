@@ -320,6 +320,35 @@ _SIGNATURES = [
     ("fhe_radix_random_below", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, u64p, C.c_size_t, C.c_uint32,
                                          C.POINTER(C.c_void_p)]),
     ("fhe_biguint_random", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("fhe_switched_pack_host", C.c_int, [u64p, C.c_size_t, C.c_uint32, C.c_size_t, u8p, C.c_size_t]),
+    ("fhe_switched_unpack_host", C.c_int, [u8p, C.c_size_t, C.c_uint32, C.c_size_t, u64p, C.c_size_t]),
+    ("fhe_switched_compress_host", C.c_int,
+     [C.c_void_p, C.c_int, u64p, C.c_size_t, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("fhe_switched_list_info", C.c_int, [C.c_void_p, u32p, u32p, C.POINTER(C.c_size_t)]),
+    ("fhe_switched_list_params", C.c_int, [C.c_void_p, C.POINTER(FheParams)]),
+    ("fhe_switched_list_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_switched_list_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_switched_list_destroy", None, [C.c_void_p]),
+    ("fhe_switched_decrypt", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_radix_compress_switched", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_biguint_compress_switched", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_switched_expand_radix", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_switched_expand_biguint", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_switched_pack_rows", C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_uint32, C.c_size_t, u8p, C.c_size_t]),
+    ("fhe_switched_unpack_rows", C.c_int, [C.c_void_p, u8p, C.c_size_t, C.c_uint32, C.c_size_t, u64p, C.c_size_t]),
+    ("fhe_ctx_time_switched", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float)]),
+    ("fhe_rekey_key_generate", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    ("fhe_rekey_key_params", C.c_int, [C.c_void_p, C.POINTER(FheParams)]),
+    ("fhe_rekey_key_serialize", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_rekey_key_deserialize", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    ("fhe_rekey_key_expand_host", C.c_int, [C.c_void_p, u64p, C.c_size_t]),
+    ("fhe_rekey_key_destroy", None, [C.c_void_p]),
+    ("fhe_switched_compress_host_rekeyed", C.c_int,
+     [C.c_void_p, C.c_int, u64p, C.c_size_t, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("fhe_set_rekey_key", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fhe_radix_compress_switched_rekeyed", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fhe_biguint_compress_switched_rekeyed", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_schnorr_sign_fhe_with_k0_rerand", C.c_int, [C.c_void_p, C.c_void_p, u8p, C.c_size_t, u8p, u8p, C.c_void_p, C.c_int,
                                                      C.c_char_p, C.c_size_t, u8p]),
     ("fhe_schnorr_public_key", C.c_int, [u8p, u8p]),

@@ -213,6 +213,60 @@ class CompactPublicKey:
         return cls(h)
 
 
+class RekeyKey:
+    """tfhe-rs' KeySwitchingKey from the big key of one client key to the small key of another (include/fhe_rocm.h
+    "re-keying through the stored form"): seeded only, 82 KB at the defaults.  Context.set_rekey_key installs it;
+    x.compress_switched(rekey=True) then gives a stored value under the destination key."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_rekey_key_destroy(self._h)
+            self._h = None
+
+    @classmethod
+    def new(cls, src_client_key: "ClientKey", dst_client_key: "ClientKey", seed=None) -> "RekeyKey":
+        """advances dst_client_key's encryption stream by exactly 2048 ks_level words; `seed` (32 bytes, PUBLIC) is
+        for tests, None draws it from the OS.  One seed, one object."""
+        if seed is not None:
+            seed = bytes(seed)
+            if len(seed) != 32:
+                raise ValueError("a mask seed is 32 bytes")
+        h = C.c_void_p()
+        check(load().fhe_rekey_key_generate(src_client_key.handle, dst_client_key.handle, seed, C.byref(h)))
+        return cls(h)
+
+    @property
+    def params(self) -> FheParams:
+        """the destination's"""
+        p = FheParams()
+        check(load().fhe_rekey_key_params(self._h, C.byref(p)))
+        return p
+
+    def serialize(self) -> bytes:
+        """100 + 8 (2048 ks_level) bytes: frame, the destination's params, seed, bodies"""
+        return serialize_with(load().fhe_rekey_key_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes) -> "RekeyKey":
+        h = C.c_void_p()
+        check(load().fhe_rekey_key_deserialize(data, len(data), C.byref(h)))
+        return cls(h)
+
+    def expand_host(self) -> np.ndarray:
+        """the full KSK [2048][ks_level][n_dst + 1] as flat uint64, in the server key's layout"""
+        p = self.params
+        ksk = np.zeros(p.polynomial_size * p.ks_level * (p.lwe_dimension + 1), np.uint64)
+        check(load().fhe_rekey_key_expand_host(self._h, ptr(ksk), ksk.size))
+        return ksk
+
+
 def default_compression_params() -> CompressionParams:
     p = CompressionParams()
     check(load().fhe_compression_params_default(C.byref(p)))
@@ -447,6 +501,47 @@ def oprf_lut_host(bits: int, params: FheParams | None = None) -> np.ndarray:
     return out
 
 
+SWITCHED_GAP_BYTE = 0xE7  # what switched_pack_host / Context.switched_pack_rows leave between packed rows
+
+
+def switched_row_bytes(n: int) -> int:
+    """bytes of one modulus-switched stored row: n + 1 values of 12 bits from a byte boundary"""
+    return (12 * (n + 1) + 7) // 8
+
+
+def _switched_pack(call, rows, n, byte_stride):
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rows.ndim != 2:
+        raise ValueError("rows must be (count, stride) words")
+    byte_stride = switched_row_bytes(n) if byte_stride is None else int(byte_stride)
+    out = np.full((rows.shape[0], max(byte_stride, 1)), SWITCHED_GAP_BYTE, np.uint8)
+    check(call(ptr(rows), rows.shape[0], int(n), rows.shape[1], ptr(out, C.c_uint8), byte_stride))
+    return out
+
+
+def _switched_unpack(call, packed, n, stride):
+    packed = np.ascontiguousarray(packed, dtype=np.uint8)
+    if packed.ndim != 2:
+        raise ValueError("packed must be (count, byte_stride) bytes")
+    stride = n + 1 if stride is None else int(stride)
+    out = np.zeros((packed.shape[0], max(stride, 1)), np.uint64)
+    check(call(ptr(packed, C.c_uint8), packed.shape[0], int(n), packed.shape[1], ptr(out), stride))
+    return out
+
+
+def switched_pack_host(rows, n: int, byte_stride=None) -> np.ndarray:
+    """the host definition of a stored row (fhe_switched_pack_host): (count, stride >= n + 1) words -> (count,
+    byte_stride) bytes, each row the 12-bit roundings of its words 0 .. n, little-endian bit-contiguous, the pad nibble
+    zero; the bytes above switched_row_bytes(n) keep SWITCHED_GAP_BYTE.  No GPU."""
+    return _switched_pack(load().fhe_switched_pack_host, rows, n, byte_stride)
+
+
+def switched_unpack_host(packed, n: int, stride=None) -> np.ndarray:
+    """the inverse (fhe_switched_unpack_host): (count, byte_stride) bytes -> (count, stride) words, value << 52 at
+    words 0 .. n, MS_PAD_WORD above.  No GPU."""
+    return _switched_unpack(load().fhe_switched_unpack_host, packed, n, stride)
+
+
 class Context:
     """One GPU + installed server key (tfhe::set_server_key, src/schnorr.rs:443)."""
 
@@ -656,6 +751,30 @@ class Context:
         ms = C.c_float()
         check(load().fhe_ctx_time_oprf_rows(self._h, int(count), int(n), int(reps), C.byref(ms)))
         return float(ms.value)
+
+    def set_rekey_key(self, key: "RekeyKey") -> None:
+        """after set_server_key, dropped by the next one (fhe_set_rekey_key): x.compress_switched(rekey=True) then
+        stores values under the key's destination"""
+        check(load().fhe_set_rekey_key(self._h, key.handle))
+
+    def switched_pack_rows(self, rows, n: int, byte_stride=None) -> np.ndarray:
+        """test hook (fhe_switched_pack_rows): k_ms_pack over a scratch copy of the rows in the bootstrap workspace's
+        layout, returned as switched_pack_host returns its bytes.  Needs no server key."""
+        h = self._h
+        return _switched_pack(lambda *a: load().fhe_switched_pack_rows(h, *a), rows, n, byte_stride)
+
+    def switched_unpack_rows(self, packed, n: int, stride=None) -> np.ndarray:
+        """test hook (fhe_switched_unpack_rows): k_ms_unpack over a scratch buffer, returned as switched_unpack_host
+        lays its rows out.  Needs no server key."""
+        h = self._h
+        return _switched_unpack(lambda *a: load().fhe_switched_unpack_rows(h, *a), packed, n, stride)
+
+    def time_switched(self, count: int, n: int, reps: int = 30):
+        """measurement hook (fhe_ctx_time_switched): mean ms of one k_ms_pack and of one k_ms_unpack launch over
+        count workspace rows"""
+        a, b = C.c_float(), C.c_float()
+        check(load().fhe_ctx_time_switched(self._h, int(count), int(n), int(reps), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
 
     def set_wide_threshold(self, threshold: int) -> None:
         check(load().fhe_ctx_set_wide_threshold(self._h, int(threshold)))

@@ -13,7 +13,8 @@ import threading
 
 import numpy as np
 
-from ._lib import CompressionParams, FheError, check, load, ptr, serialize_with
+from ._lib import CompressionParams, FheError, FheParams, check, load, ptr, serialize_with
+from .core import RekeyKey, modulus_switch_mode
 
 COMPAT = 0  # exact replay of src/biguint.rs:214-254 incl. the wrapping add at :247-249
 FAST = 1    # true product/sum, single wide carry propagation
@@ -847,6 +848,106 @@ def _compress_biguint(self) -> CompressedCiphertextList:
 
 FheUint.compress = _compress_radix
 BigUintFHE.compress = _compress_biguint
+
+
+class SwitchedCiphertextList:
+    """tfhe-rs' CompressedModulusSwitchedCiphertext holding one computed value: per block the keyswitched,
+    modulus-switched row, n + 1 values of 12 bits (include/fhe_rocm.h "modulus-switched stored ciphertexts").  No
+    key beyond the server key.  A host object: serialize / deserialize / decrypt(client_key) need no context;
+    decompress() brings it back onto this thread's GPU context with one blind rotation per block."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().fhe_switched_list_destroy(self._h)
+            self._h = None
+
+    def _info(self):
+        form, count, nb = C.c_uint32(), C.c_uint32(), C.c_size_t()
+        check(load().fhe_switched_list_info(self._h, C.byref(form), C.byref(count), C.byref(nb)))
+        return int(form.value), int(count.value), int(nb.value)
+
+    @property
+    def nblocks(self) -> int:
+        return self._info()[2]
+
+    @property
+    def params(self) -> FheParams:
+        p = FheParams()
+        check(load().fhe_switched_list_params(self._h, C.byref(p)))
+        return p
+
+    @property
+    def bits(self) -> int:
+        form, count, _ = self._info()
+        return count if form == SEEDED_RADIX else 32 * count
+
+    @classmethod
+    def compress_host(cls, server_key, cts, degrees, form: int, count: int, ms_mode: str = "standard"):
+        """the stored form on the host (fhe_switched_compress_host): the definition of the GPU path in the given
+        modulus-switch mode ("standard" / "centered")"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2049)
+        deg = np.ascontiguousarray(np.broadcast_to(np.asarray(degrees, np.uint8), (cts.shape[0],)))
+        h = C.c_void_p()
+        # a RekeyKey in the server key's place: its expanded KSK, the list under its destination
+        fn = load().fhe_switched_compress_host_rekeyed if isinstance(server_key, RekeyKey) else load().fhe_switched_compress_host
+        check(fn(server_key.handle, modulus_switch_mode(ms_mode), ptr(cts), cts.shape[0], ptr(deg, C.c_uint8), form, count,
+                 C.byref(h)))
+        return cls(h)
+
+    def serialize(self) -> bytes:
+        """80 + nblocks (1 + ceil(12 (n + 1) / 8)) bytes"""
+        return serialize_with(load().fhe_switched_list_serialize, self._h)
+
+    @classmethod
+    def deserialize(cls, data: bytes):
+        h = C.c_void_p()
+        check(load().fhe_switched_list_deserialize(data, len(data), C.byref(h)))
+        return cls(h)
+
+    def decrypt(self, client_key) -> int:
+        """the value, from the 12-bit rows and the small key alone (BigUintFHE form: limb i at bits 32 i)"""
+        n = max(1, (self.bits + 63) // 64)
+        w = np.zeros(n, np.uint64)
+        check(load().fhe_switched_decrypt(client_key.handle, self._h, ptr(w), n))
+        return sum(int(w[i]) << (64 * i) for i in range(n))
+
+    def decompress(self, ctx=None):
+        """FheUint or BigUintFHE on ctx (default: this thread's context), fresh noise"""
+        ctx = ctx or _ctx()
+        form, count, _ = self._info()
+        h = C.c_void_p()
+        if form == SEEDED_BIGUINT:
+            check(load().fhe_switched_expand_biguint(ctx.handle, self._h, C.byref(h)))
+            return BigUintFHE(h)
+        check(load().fhe_switched_expand_radix(ctx.handle, self._h, C.byref(h)))
+        return FheUint._wrap(h, count)
+
+
+def _compress_switched_radix(self, rekey: bool = False) -> SwitchedCiphertextList:
+    """FheUint::compress() on this thread's context: the modulus-switched stored form; rekey=True: under the
+    destination of the context's re-keying key (Context.set_rekey_key)"""
+    h = C.c_void_p()
+    fn = load().fhe_radix_compress_switched_rekeyed if rekey else load().fhe_radix_compress_switched
+    check(fn(_ctx().handle, self._h, C.byref(h)))
+    return SwitchedCiphertextList(h)
+
+
+def _compress_switched_biguint(self, rekey: bool = False) -> SwitchedCiphertextList:
+    h = C.c_void_p()
+    fn = load().fhe_biguint_compress_switched_rekeyed if rekey else load().fhe_biguint_compress_switched
+    check(fn(_ctx().handle, self._h, C.byref(h)))
+    return SwitchedCiphertextList(h)
+
+
+FheUint.compress_switched = _compress_switched_radix
+BigUintFHE.compress_switched = _compress_switched_biguint
 
 
 class CompactCiphertextListBuilder:

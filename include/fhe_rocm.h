@@ -1083,6 +1083,114 @@ int fhe_radix_random_below(fhe_ctx* ctx, const uint8_t seed[32] /* NULL: OS entr
 /* BigUintFHE of bits / 32 digits (bits a multiple of 32), block i of the whole on row i */
 int fhe_biguint_random(fhe_ctx* ctx, const uint8_t seed[32] /* NULL: OS entropy */, uint32_t bits, fhe_biguint** out);
 
+/* ------------------------------------------------------------------- modulus-switched stored ciphertexts */
+/* tfhe-rs' FheUint::compress() -> CompressedModulusSwitchedCiphertext: a computed value parked or sent as the rows
+ * its next bootstrap would read, n + 1 values of 12 bits per block -- 1,253 bytes per block at the defaults against
+ * 16,392 of the full form (13x), with NO key beyond the server key.  Bringing it back costs one blind rotation
+ * under the ordinary server key; the holder of the client key reads it with the small key alone, without a GPU.
+ * With n the LWE dimension, for a block c of 2049 words:
+ * ROW      r = keyswitch(c) (n + 1 words: body - sum_{j, l} d[j, l] KSK[j][l], balanced digits of the mask words
+ *          rounded to their top ks_base_log ks_level bits); in FHE_MS_CENTERED the row's body then gives up the
+ *          public half of the rounding residues, as fhe_ms_center_host does -- what every level of the mode does.
+ * STORED   v[t] = (((r[t] >> 51) + 1) >> 1) & 4095 for t <= n, the blind rotation's own rounding; a row on the wire
+ *          is the n + 1 values packed little-endian bit-contiguously (value t at bits [12 t, 12 t + 12)) from a
+ *          byte boundary: ceil(12 (n + 1) / 8) bytes, the pad nibble of an odd n + 1 zero.
+ * BACK     row words v[t] << 52 (no residue: the blind rotation's rounding returns v[t], and no centering runs on
+ *          them), one blind rotation under the installed key set through the identity table over message_modulus
+ *          carry_modulus values: fresh slots, noise 1, degree from the degree byte -- word for word what
+ *          fhe_pbs_batch of c with that table gives in the same modulus-switch mode.
+ * CLIENT   phase = (v[n] - sum_i v[i] s[i]) mod 4096, value = round(phase / 128) mod 16, assembled as
+ *          fhe_radix_decrypt assembles blocks.  The decode margin and the rounding noise are those of a
+ *          bootstrap's modulus switch (see fhe_ctx_set_modulus_switch).
+ * Wire (kind 13): main params, u32 form (FHE_SEEDED_RADIX / FHE_SEEDED_BIGUINT semantics), u32 count (num_bits or
+ * nlimbs), u32 B (blocks), B degree bytes (each < 16), B rows:  80 + B (1 + ceil(12 (n + 1) / 8))  bytes.  The
+ * reader refuses truncation, non-zero pad bits, a degree >= 16, a block count that does not match form / count
+ * and unsupported parameters. */
+typedef struct fhe_switched_list fhe_switched_list;
+/* The definitions on the host; no context, no GPU.  rows: count x stride words, stride >= n + 1, 1 <= n <= 2048,
+ * words above n are not read (pack) / hold 0xA5A55A5AC3C33C3C (unpack: a bootstrap workspace row's padding).
+ * packed: count rows at a distance of byte_stride >= ceil(12 (n + 1) / 8) bytes; the bytes between rows are
+ * neither read nor written.  At most 2^24 rows. */
+int fhe_switched_pack_host(const uint64_t* rows, size_t count, uint32_t n, size_t stride, uint8_t* packed,
+                           size_t byte_stride);
+int fhe_switched_unpack_host(const uint8_t* packed, size_t count, uint32_t n, size_t byte_stride, uint64_t* rows,
+                             size_t stride);
+/* The whole stored form on the host -- the word-for-word definition of fhe_radix_compress_switched, and what a
+ * server without a GPU uses: ms_mode = FHE_MS_STANDARD / FHE_MS_CENTERED, cts = nblocks x 2049 words, degrees =
+ * nblocks bytes (< 16), form / count as above (count / 2, or 16 count, must equal nblocks). */
+int fhe_switched_compress_host(const fhe_server_key* sk, int ms_mode, const uint64_t* cts, size_t nblocks,
+                               const uint8_t* degrees, uint32_t form, uint32_t count, fhe_switched_list** out);
+int fhe_switched_list_info(const fhe_switched_list* x, uint32_t* form, uint32_t* count, size_t* nblocks);
+int fhe_switched_list_params(const fhe_switched_list* x, fhe_params* main);
+int fhe_switched_list_serialize(const fhe_switched_list* x, uint8_t* buf, size_t cap, size_t* len);
+int fhe_switched_list_deserialize(const uint8_t* buf, size_t len, fhe_switched_list** out);
+void fhe_switched_list_destroy(fhe_switched_list* x);
+/* Client side, no GPU and no context; nwords >= ceil(bits / 64), bits = num_bits or 32 nlimbs.  FHE_ERR_INVALID,
+ * with the differing field named, if the list's parameters are not the client key's. */
+int fhe_switched_decrypt(const fhe_client_key* ck, const fhe_switched_list* x, uint64_t* words, size_t nwords);
+/* FheUint::compress(): the value's blocks made real as for a download (pending producers launched -- a plain
+ * flush, rank-local under a communicator; lazy blocks combined; a trivial block enters as (0, delta value)), then
+ * per chunk of the bootstrap workspace the context's keyswitch (and centering, in that mode), the row-packing
+ * kernel and one download.  Byte-identical to fhe_switched_compress_host on the exported blocks in the context's
+ * mode.  FHE_ERR_INVALID for a block whose noise label admits no lookup, or of degree >= 16. */
+int fhe_radix_compress_switched(fhe_ctx* ctx, const fhe_radix* x, fhe_switched_list** out);
+int fhe_biguint_compress_switched(fhe_ctx* ctx, const fhe_biguint* x, fhe_switched_list** out);
+/* decompress(): fresh block slots, stream-ordered like fhe_compressed_expand_radix (no flush, no collective: under
+ * a communicator every rank expands the same bytes): upload, the row-unpacking kernel into the bootstrap
+ * workspace, the blind rotate under the server key.  FHE_ERR_INVALID, with the differing field named, if the
+ * list's parameters are not the installed server key's. */
+int fhe_switched_expand_radix(fhe_ctx* ctx, const fhe_switched_list* x, fhe_radix** out);
+int fhe_switched_expand_biguint(fhe_ctx* ctx, const fhe_switched_list* x, fhe_biguint** out);
+/* Test hooks: the two kernels alone over scratch buffers in the device layouts (workspace rows of n + 1 words
+ * rounded up to 8; packed rows of whole 12-byte groups), arguments and results as the host functions'.  They need
+ * no server key, so any n runs without a key generation.  Same validation; FHE_ERR_INVALID too if a kernel wrote
+ * behind its last device row.  Synchronous. */
+int fhe_switched_pack_rows(fhe_ctx* ctx, const uint64_t* rows, size_t count, uint32_t n, size_t stride, uint8_t* packed,
+                           size_t byte_stride);
+int fhe_switched_unpack_rows(fhe_ctx* ctx, const uint8_t* packed, size_t count, uint32_t n, size_t byte_stride,
+                             uint64_t* rows, size_t stride);
+/* Measurement hook: each kernel alone, `reps` launches over `count` rows between HIP events on the context's
+ * stream; the means per launch. */
+int fhe_ctx_time_switched(fhe_ctx* ctx, size_t count, uint32_t n, uint32_t reps, float* pack_ms, float* unpack_ms);
+
+/* ------------------------------------------------- re-keying through the stored form */
+/* A stored row is the midpoint of a key change: keyswitched with a KSK from the big key of client key A to the
+ * SMALL key of client key B, a value under A becomes a stored value under B -- B's client key reads it, a context
+ * holding B's server key bootstraps it -- and the secret never appears in clear.  tfhe-rs' KeySwitchingKey; the
+ * only way to rotate the FHE key over an Enc(d) whose owner no longer keeps d.  The owner of both client keys makes
+ * the re-keying key; it is seeded only: the DESTINATION's parameters, a PUBLIC 32-byte seed and 2048 ks_level body
+ * words, 82,020 bytes serialized at the defaults (kind 14: params | seed | bodies).
+ *   masks   row r = j ks_level + l: mask word t < n_dst = u64 word 2048 r + t of the ChaCha20 stream keyed by the
+ *           seed bytes, nonce {112, "ROCM", 0} -- the seeded server key's row stride under a stream id of its own
+ *   noise   exactly 2048 ks_level words of the DESTINATION key's encryption stream, in row order:
+ *           e = TUniform(lwe_noise_log2 of the destination) of the word
+ *   body    bodies[r] = <mask_r, s_dst> + (S_src[j] << (64 - ks_base_log (l + 1))) + e
+ * The two client keys must agree in message_modulus, carry_modulus, ks_base_log, ks_level, pbs_base_log and
+ * glwe_noise_log2 (FHE_ERR_INVALID names the field); lwe_dimension, lwe_noise_log2 and grouping are the
+ * destination's and may differ.  ONE SEED, ONE OBJECT, as for every seeded object.  A re-keyed row carries the
+ * destination's keyswitch noise, and FHE_MS_CENTERED applies to it with the destination's dimension. */
+typedef struct fhe_rekey_key fhe_rekey_key;
+int fhe_rekey_key_generate(const fhe_client_key* src, fhe_client_key* dst, const uint8_t* mask_seed /* NULL: OS entropy */,
+                           fhe_rekey_key** out);
+int fhe_rekey_key_params(const fhe_rekey_key* key, fhe_params* out); /* the destination's */
+int fhe_rekey_key_serialize(const fhe_rekey_key* key, uint8_t* buf, size_t cap, size_t* len);
+int fhe_rekey_key_deserialize(const uint8_t* buf, size_t len, fhe_rekey_key** out);
+/* the full KSK, [2048][ks_level][n_dst + 1] words in the server key's layout: the definition of the install */
+int fhe_rekey_key_expand_host(const fhe_rekey_key* key, uint64_t* ksk, size_t len);
+void fhe_rekey_key_destroy(fhe_rekey_key* key);
+/* fhe_switched_compress_host with the expanded re-keying KSK in place of the server key's: the list carries the
+ * destination's parameters.  The definition of fhe_*_compress_switched_rekeyed. */
+int fhe_switched_compress_host_rekeyed(const fhe_rekey_key* key, int ms_mode, const uint64_t* cts, size_t nblocks,
+                                       const uint8_t* degrees, uint32_t form, uint32_t count, fhe_switched_list** out);
+/* After fhe_set_server_key; dropped by the next server-key install (then FHE_ERR_NO_KEY from the calls below).
+ * FHE_ERR_INVALID, with the field named, unless the six shared fields equal the installed server key's.  Uploads
+ * the bodies, regenerates the masks on the GPU, derives the byte planes; the key gets a row workspace of its own.
+ * Nothing else of the context changes: every other call launches exactly as before. */
+int fhe_set_rekey_key(fhe_ctx* ctx, const fhe_rekey_key* key);
+/* fhe_*_compress_switched under the re-keying key: a stored value under the destination key. */
+int fhe_radix_compress_switched_rekeyed(fhe_ctx* ctx, const fhe_radix* x, fhe_switched_list** out);
+int fhe_biguint_compress_switched_rekeyed(fhe_ctx* ctx, const fhe_biguint* x, fhe_switched_list** out);
+
 /* ------------------------------------------------------------------- Schnorr / BIP-340 */
 /* The caller of the hot path (src/schnorr.rs).  32-byte scalars are big-endian.  The plaintext
  * EC / hash steps run on the host; the FHE block s = k + e*d runs on the GPU engine. */
