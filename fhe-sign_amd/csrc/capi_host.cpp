@@ -2,6 +2,7 @@
 // algorithms run on a host engine (engine.h: kHostFold on public values, kDry for the schedule, kSim with a
 // plaintext shadow), no GPU and no key.  The CPU tests and tools/engine_host_check.c drive them.
 #include <algorithm>
+#include <memory>
 #include <string>
 
 #include "capi_internal.h"
@@ -161,6 +162,26 @@ int fhe_schedule_levels_ranks(const int32_t* off, const int32_t* deps, size_t n,
         for (size_t l = 0; l < lv.size(); ++l)
             for (int32_t i : lv[l]) level_of[i] = (int32_t)l + 1;
         *nlevels = (int32_t)lv.size();
+        return FHE_OK;
+    });
+}
+
+// A simulated context: no device, no stream, the default parameters, has_key set, an Engine::kSim engine.  The
+// C ABI's radix layer runs on it through its real code (capi_radix.cpp: widths, casts, clones, word forms, amounts
+// of another width, the column-form decryption and its partial flush): fhe_radix_encrypt / fhe_biguint_encrypt make
+// shadowed blocks of the plaintext (the client key is ignored and may be NULL), the decryptions make the flush a
+// device decryption makes and read the shadow.  What needs device memory or a real key refuses with
+// FHE_ERR_INVALID and leaves the context usable.  fhe_ctx_destroy frees it.
+// Known limit: the shadow evaluates a bootstrap when it is RECORDED, so a test on this context sees every recorded
+// graph and every value, not the launch order -- a schedule that launched a node before its producer would pass.
+int fhe_host_sim_ctx_create(fhe_ctx** ctx) {
+    if (!ctx) return FHE_ERR_INVALID;
+    return guarded([&] {
+        auto c = std::make_unique<fhe_ctx>();
+        c->simulated = true;
+        c->has_key = true;
+        c->engine = new Engine(c.get(), Engine::kSim);
+        *ctx = c.release();
         return FHE_OK;
     });
 }

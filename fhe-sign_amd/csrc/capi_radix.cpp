@@ -19,7 +19,9 @@ using namespace fhe;
 
 namespace {
 
-int need_engine(fhe_ctx* c) {
+// sim_ok: the entry point runs on a simulated context too (fhe_host_sim_ctx_create: the radix and BigUintFHE
+// arithmetic, their encryptions and decryptions); every other one refuses it
+int need_engine(fhe_ctx* c, bool sim_ok = false) {
     if (!c) {
         set_error("null context");
         return FHE_ERR_INVALID;
@@ -28,6 +30,7 @@ int need_engine(fhe_ctx* c) {
         set_error("no server key installed (fhe_set_server_key)");
         return FHE_ERR_NO_KEY;
     }
+    if (c->simulated) return sim_ok ? FHE_OK : refuse_simulated(c, "this entry point");
     if (hipSetDevice(c->device) != hipSuccess) {
         set_error("hipSetDevice failed");
         return FHE_ERR_HIP;
@@ -50,9 +53,50 @@ fhe_radix* wrap(Radix r, uint32_t bits) {
 bool valid_bits(uint32_t bits) { return bits >= 2 && bits <= FHE_RADIX_MAX_BITS && bits % 2 == 0; }
 
 // run a binary op on two radix of equal width
+constexpr bool kSimOk = true;
+
+// the decoded values of slot blocks (carry bits included): one download, decrypted on the host.  only_needed:
+// launch just the pending bootstraps the blocks depend on (Engine::flush_for).  A simulated context makes the same
+// flush and reads the plaintext shadow: nothing is launched, the graph is scheduled; ck is not looked at.
+std::vector<int64_t> read_blocks(fhe_ctx* c, const fhe_client_key* ck, const std::vector<const Block*>& enc,
+                                 bool only_needed) {
+    std::vector<int64_t> vals(enc.size());
+    if (c->simulated) {
+        if (enc.empty()) return vals;
+        if (only_needed)
+            c->engine->flush_for(enc);
+        else
+            c->engine->flush();
+        for (size_t i = 0; i < enc.size(); ++i) {
+            const int64_t h2 = c->engine->sim_half2(*enc[i]);
+            engine_check(h2 % 2 == 0 && h2 >= 0 && h2 < 2 * (int64_t)c->p.msg_carry(), "sim: a decrypted block off its message range");
+            vals[i] = h2 / 2;
+        }
+        return vals;
+    }
+    std::vector<uint64_t> cts(enc.size() * kBigCt);
+    c->engine->download_many(enc, cts.data(), only_needed);
+    for (size_t i = 0; i < enc.size(); ++i)
+        vals[i] = (int64_t)decode_block(ck->params, decrypt_phase_big(ck, cts.data() + i * kBigCt));
+    return vals;
+}
+
+// nblocks client-encrypted blocks of the given 2-bit digits; a simulated context makes sim_blocks of them
+Blocks encrypt_digits(fhe_ctx* c, fhe_client_key* ck, const std::vector<uint32_t>& digits) {
+    Blocks out;
+    if (c->simulated) {
+        for (uint32_t v : digits) out.push_back(c->engine->sim_block(v, 3));
+        return out;
+    }
+    std::vector<uint64_t> ct(digits.size() * kBigCt), pts(digits.size());
+    for (size_t k = 0; k < digits.size(); ++k) pts[k] = (uint64_t)digits[k] * ck->params.delta();
+    encrypt_big_many(ck, pts.data(), pts.size(), ct.data());
+    return c->engine->upload_many(ct.data(), digits.size(), 3);
+}
+
 template <class F>
 int binop(fhe_ctx* c, const fhe_radix* a, const fhe_radix* b, fhe_radix** out, F&& f) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !out) return FHE_ERR_INVALID;
     if (a->bits != b->bits) {
@@ -67,7 +111,7 @@ int binop(fhe_ctx* c, const fhe_radix* a, const fhe_radix* b, fhe_radix** out, F
 
 template <class F>
 int unop(fhe_ctx* c, const fhe_radix* a, fhe_radix** out, F&& f) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !out) return FHE_ERR_INVALID;
     return guarded([&] {
@@ -88,19 +132,24 @@ void engine_eager_next_batch(fhe_ctx* c, bool on) {
 // operands one after the other (the signer's e_fhe and k_fhe)
 int biguint_encrypt_batch(fhe_ctx* c, fhe_client_key* ck, const std::vector<const std::vector<uint32_t>*>& limbs,
                           fhe_biguint** outs, bool deferred) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
-    if (!ck || !outs) return FHE_ERR_INVALID;
+    if ((!ck && !c->simulated) || !outs) return FHE_ERR_INVALID;
     return guarded([&] {
         size_t total = 0;
         for (auto* l : limbs) total += l->size();
-        std::vector<uint64_t> pts(total * kLimbBlocks);
-        size_t q = 0;
+        std::vector<uint32_t> digits;
+        digits.reserve(total * kLimbBlocks);
         for (auto* l : limbs)
             for (uint32_t x : *l)
-                for (uint32_t k = 0; k < kLimbBlocks; ++k) pts[q++] = (uint64_t)((x >> (2 * k)) & 3u) * ck->params.delta();
+                for (uint32_t k = 0; k < kLimbBlocks; ++k) digits.push_back((x >> (2 * k)) & 3u);
+        std::vector<uint64_t> pts;
+        if (!c->simulated)
+            for (uint32_t v : digits) pts.push_back((uint64_t)v * ck->params.delta());
         Blocks all;
-        if (deferred) {
+        if (c->simulated) {  // shadowed blocks of the digits, at once: there is no encryption to overlap
+            all = encrypt_digits(c, ck, digits);
+        } else if (deferred) {
             // the encryption runs on a helper thread while the caller records the graph that reads the
             // blocks; the engine uploads them right before its next launch (Engine::upload_deferred)
             auto job = std::make_shared<std::future<std::vector<uint64_t>>>(std::async(std::launch::async, [ck, pts] {
@@ -134,18 +183,17 @@ int biguint_encrypt_batch(fhe_ctx* c, fhe_client_key* ck, const std::vector<cons
 extern "C" {
 
 int fhe_radix_encrypt(fhe_ctx* c, fhe_client_key* ck, const uint64_t* words, uint32_t bits, fhe_radix** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
-    if (!ck || !words || !out || !valid_bits(bits)) {
+    if ((!ck && !c->simulated) || !words || !out || !valid_bits(bits)) {
         set_error("invalid arguments to fhe_radix_encrypt");
         return FHE_ERR_INVALID;
     }
     return guarded([&] {
         Radix r;
-        std::vector<uint64_t> ct((size_t)(bits / 2) * kBigCt), pts(bits / 2);
-        for (uint32_t k = 0; k < bits / 2; ++k) pts[k] = (uint64_t)word_bits(words, 2 * k, bits) * ck->params.delta();
-        encrypt_big_many(ck, pts.data(), pts.size(), ct.data());
-        r.blocks = c->engine->upload_many(ct.data(), bits / 2, 3);
+        std::vector<uint32_t> digits(bits / 2);
+        for (uint32_t k = 0; k < bits / 2; ++k) digits[k] = word_bits(words, 2 * k, bits);
+        r.blocks = encrypt_digits(c, ck, digits);
         *out = wrap(std::move(r), bits);
         return FHE_OK;
     });
@@ -180,11 +228,9 @@ static void decrypt_columns(fhe_ctx* c, const fhe_client_key* ck, const std::vec
             else
                 want(b);
         }
-    std::vector<uint64_t> cts(enc.size() * kBigCt);
-    c->engine->download_many(enc, cts.data(), only_needed);
+    const std::vector<int64_t> got = read_blocks(c, ck, enc, only_needed);
     std::unordered_map<const uint64_t*, int64_t> vals;
-    for (size_t i = 0; i < enc.size(); ++i)
-        vals[keys[i]] = (int64_t)decode_block(ck->params, decrypt_phase_big(ck, cts.data() + i * kBigCt));
+    for (size_t i = 0; i < enc.size(); ++i) vals[keys[i]] = got[i];
     column_value(cols, nblocks, [&](const Block& b) { return vals.at(b.ptr()); }, words, nwords);
 }
 
@@ -199,20 +245,16 @@ static std::vector<uint32_t> decrypt_blocks(fhe_ctx* c, const fhe_client_key* ck
         else
             enc.push_back(&r.blocks[k]);
     }
-    std::vector<uint64_t> cts(enc.size() * kBigCt);
-    c->engine->download_many(enc, cts.data());
+    const std::vector<int64_t> got = read_blocks(c, ck, enc, false);
     for (size_t i = 0, k = 0; k < r.nblocks(); ++k)
-        if (!r.blocks[k].trivial()) {
-            vals[k] = (uint32_t)decode_block(ck->params, decrypt_phase_big(ck, cts.data() + i * kBigCt));
-            ++i;
-        }
+        if (!r.blocks[k].trivial()) vals[k] = (uint32_t)got[i++];
     return vals;
 }
 
 int fhe_radix_decrypt(fhe_ctx* c, const fhe_client_key* ck, const fhe_radix* x, uint64_t* words, size_t nwords) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
-    if (!ck || !x || !words || nwords * 64 < x->bits) {
+    if ((!ck && !c->simulated) || !x || !words || nwords * 64 < x->bits) {
         set_error("invalid arguments to fhe_radix_decrypt");
         return FHE_ERR_INVALID;
     }
@@ -316,7 +358,7 @@ int fhe_radix_lt(fhe_ctx* c, const fhe_radix* a, const fhe_radix* b, fhe_radix**
     return rc;
 }
 int fhe_radix_divrem(fhe_ctx* c, const fhe_radix* a, const fhe_radix* b, fhe_radix** q, fhe_radix** r) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || (!q && !r)) return FHE_ERR_INVALID;
     if (a->bits != b->bits) {
@@ -337,7 +379,7 @@ int fhe_radix_rem(fhe_ctx* c, const fhe_radix* a, const fhe_radix* b, fhe_radix*
     return fhe_radix_divrem(c, a, b, nullptr, out);
 }
 int fhe_radix_shr(fhe_ctx* c, const fhe_radix* a, const fhe_radix* amount, fhe_radix** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !amount || !out) return FHE_ERR_INVALID;
     return guarded([&] {
@@ -346,7 +388,7 @@ int fhe_radix_shr(fhe_ctx* c, const fhe_radix* a, const fhe_radix* amount, fhe_r
     });
 }
 int fhe_radix_shl(fhe_ctx* c, const fhe_radix* a, const fhe_radix* amount, fhe_radix** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !amount || !out) return FHE_ERR_INVALID;
     return guarded([&] {
@@ -456,6 +498,19 @@ int fhe_ctx_stats(fhe_ctx* c, uint64_t* pbs, uint64_t* levels) {
     return FHE_OK;
 }
 
+// The noise budget as the engine enforced it since the last reset (Engine::NoiseAudit): the largest label, the
+// largest merged noise, and the number of recorded bootstraps whose merged noise exceeds their label.  Device and
+// simulated contexts alike; a context without an engine reports zeros.
+int fhe_ctx_noise_audit(fhe_ctx* c, uint64_t* max_label, uint64_t* max_merged, uint64_t* n_above_label, int reset) {
+    if (!c) return FHE_ERR_INVALID;
+    const Engine::NoiseAudit a = c->engine ? c->engine->audit : Engine::NoiseAudit{};
+    if (max_label) *max_label = a.max_label;
+    if (max_merged) *max_merged = a.max_merged;
+    if (n_above_label) *n_above_label = a.n_above_label;
+    if (reset && c->engine) c->engine->audit = Engine::NoiseAudit{};
+    return FHE_OK;
+}
+
 // ----------------------------------------------------------------- operand distribution (comm.cpp)
 int fhe_ctx_broadcast_radix(fhe_ctx* c, fhe_radix** x, int root) {
     const bool sends = c && (!c->attached() || c->rank == root);
@@ -518,9 +573,9 @@ int fhe_biguint_from_digits(const fhe_radix* const* digits, size_t n, fhe_biguin
 
 int fhe_biguint_decrypt(fhe_ctx* c, const fhe_client_key* ck, const fhe_biguint* x, uint32_t* limbs, size_t cap,
                         size_t* n) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
-    if (!ck || !x || !n) return FHE_ERR_INVALID;
+    if ((!ck && !c->simulated) || !x || !n) return FHE_ERR_INVALID;
     *n = x->v.digits.size();
     if (cap < *n || (*n && !limbs)) {
         set_error("limb buffer too small");
@@ -578,7 +633,7 @@ int fhe_biguint_clone(const fhe_biguint* x, fhe_biguint** out) {
 void fhe_biguint_destroy(fhe_biguint* x) { delete x; }
 
 int fhe_biguint_add(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, int mode, fhe_biguint** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !out) return FHE_ERR_INVALID;
     return guarded([&] {
@@ -590,7 +645,7 @@ int fhe_biguint_add(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, int 
 }
 
 int fhe_biguint_mul(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, int mode, fhe_biguint** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !out) return FHE_ERR_INVALID;
     return guarded([&] {
@@ -605,7 +660,7 @@ int fhe_biguint_mul(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, int 
 // mul-add without its final carry propagation, which the decryption resolves on the host
 int fhe_biguint_mul_add_columns(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, const fhe_biguint* k, int mode,
                                 fhe_columns** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !k || !out || (mode != kCompat && mode != kFast)) return FHE_ERR_INVALID;
     return guarded([&] {
@@ -619,7 +674,7 @@ int fhe_biguint_mul_add_columns(fhe_ctx* c, const fhe_biguint* a, const fhe_bigu
 // m * a + k (m, k public words) in column form, value mod 2^(a's bits): the public-operand signer
 int fhe_radix_scalar_mul_add_columns(fhe_ctx* c, const fhe_radix* a, const uint64_t* m, size_t nm, const uint64_t* k,
                                      size_t nk, fhe_columns** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !out || (!m && nm) || (!k && nk)) return FHE_ERR_INVALID;
     const BigConst vm = words_of(m, nm), vk = words_of(k, nk);
@@ -640,9 +695,9 @@ int fhe_columns_bits(const fhe_columns* x, uint32_t* bits) {
 }
 
 int fhe_columns_decrypt(fhe_ctx* c, const fhe_client_key* ck, const fhe_columns* x, uint64_t* words, size_t nwords) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
-    if (!ck || !x || !words || nwords * 64 < 2 * (size_t)x->nblocks) {
+    if ((!ck && !c->simulated) || !x || !words || nwords * 64 < 2 * (size_t)x->nblocks) {
         set_error("invalid arguments to fhe_columns_decrypt");
         return FHE_ERR_INVALID;
     }
@@ -657,7 +712,7 @@ void fhe_columns_destroy(fhe_columns* x) { delete x; }
 // x mod (2^k_bits - c), c public words: radix_rem_pseudo_mersenne; the result has k_bits bits
 int fhe_radix_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a, uint32_t k_bits, const uint64_t* c_words, size_t nc,
                                   fhe_radix** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !out || !c_words || !nc) {
         set_error("invalid arguments to fhe_radix_rem_pseudo_mersenne");
@@ -674,7 +729,7 @@ int fhe_radix_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a, uint32_t k_bit
 // fold reads the columns unpropagated
 int fhe_columns_rem_pseudo_mersenne(fhe_ctx* c, const fhe_columns* x, uint32_t k_bits, const uint64_t* c_words, size_t nc,
                                     fhe_radix** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!x || !out || !c_words || !nc) {
         set_error("invalid arguments to fhe_columns_rem_pseudo_mersenne");
@@ -692,7 +747,7 @@ int fhe_columns_rem_pseudo_mersenne(fhe_ctx* c, const fhe_columns* x, uint32_t k
 int fhe_radix_scalar_mul_add_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a, const uint64_t* m, size_t nm,
                                                  const uint64_t* k, size_t nk, uint32_t k_bits, const uint64_t* c_words,
                                                  size_t nc, fhe_radix** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !out || !c_words || !nc || (!m && nm) || (!k && nk)) {
         set_error("invalid arguments to fhe_radix_scalar_mul_add_rem_pseudo_mersenne");
@@ -707,7 +762,7 @@ int fhe_radix_scalar_mul_add_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a,
 
 int fhe_biguint_mul_add(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, const fhe_biguint* k, int mode,
                         fhe_biguint** out) {
-    int rc = need_engine(c);
+    int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !k || !out) return FHE_ERR_INVALID;
     return guarded([&] {

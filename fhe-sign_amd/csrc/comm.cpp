@@ -374,6 +374,7 @@ int bcast_decode(fhe_ctx* c, const BcastHdr& h, const std::vector<uint32_t>& met
 }  // namespace
 
 int bcast_radix_groups(fhe_ctx* c, int root, std::vector<Radix>* groups) {
+    if (const int sim = refuse_simulated(c, "a broadcast")) return sim;
     if (!c || !groups || root < 0 || root >= c->fanout_world()) {
         set_error("broadcast needs a valid root rank");
         return FHE_ERR_INVALID;
@@ -492,6 +493,7 @@ int fhe_comm_unique_id(uint8_t id[FHE_COMM_ID_BYTES]) {
 
 int fhe_ctx_attach_comm_timeout(fhe_ctx* c, const uint8_t id[FHE_COMM_ID_BYTES], int nranks, int rank,
                                 uint32_t timeout_ms) {
+    if (const int sim = refuse_simulated(c, "fhe_ctx_attach_comm")) return sim;
     if (!c || !id || nranks < 1 || rank < 0 || rank >= nranks || timeout_ms == 0) return FHE_ERR_INVALID;
     FHE_HIP_CHECK(hipSetDevice(c->device));
     c->release_comm();
@@ -522,6 +524,7 @@ int fhe_ctx_attach_comm(fhe_ctx* c, const uint8_t id[FHE_COMM_ID_BYTES], int nra
 }
 
 int fhe_ctx_attach_test_transport(fhe_ctx* c, const fhe_test_transport* tx, int nranks, int rank) {
+    if (const int sim = refuse_simulated(c, "fhe_ctx_attach_test_transport")) return sim;
     if (!c || !tx || !tx->bcast || !tx->allgather || !tx->allreduce_min_u8 || nranks < 1 || rank < 0 ||
         rank >= nranks)
         return FHE_ERR_INVALID;
@@ -562,6 +565,7 @@ int fhe_ctx_detach_comm(fhe_ctx* c) {
 // the receivers' buffer allocations are agreed with a one-word all-reduce (min) before any data
 // moves; the final wait is bounded (comm_wait: deadline, then ncclCommAbort).
 int fhe_ctx_broadcast_server_key(fhe_ctx* c, int root) {
+    if (const int sim = refuse_simulated(c, "fhe_ctx_broadcast_server_key")) return sim;
     if (!c || !c->attached() || root < 0 || root >= c->nranks) {
         set_error("broadcast_server_key needs an attached communicator and a valid root");
         return FHE_ERR_INVALID;

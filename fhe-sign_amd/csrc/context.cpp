@@ -131,6 +131,12 @@ void make_lut_poly(const Params& p, const uint32_t* f, std::vector<uint64_t>* lu
     for (uint32_t j = 0; j < kPolySize; ++j) (*lut)[j] = tmp[(j + half) % kPolySize];
 }
 
+int refuse_simulated(const fhe_ctx* c, const char* what) {
+    if (!c || !c->simulated) return FHE_OK;
+    set_error(std::string(what) + ": not on a simulated context (fhe_host_sim_ctx_create has no device and no key)");
+    return FHE_ERR_INVALID;
+}
+
 }  // namespace fhe
 
 using namespace fhe;
@@ -138,6 +144,10 @@ using namespace fhe;
 // (fhe_ctx_destroy) what is queued runs to its end, then the engine, the communicator, the events and the
 // stream go; the DeviceBuf members free themselves after this body
 fhe_ctx::~fhe_ctx() {
+    if (simulated) {  // nothing of the device's to wait for or free
+        delete engine;
+        return;
+    }
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     delete engine;
@@ -472,6 +482,7 @@ int fhe_generate_keys_device(fhe_ctx* c, const fhe_params* params, uint64_t seed
 
 int fhe_generate_keys_device_keyed(fhe_ctx* c, const fhe_params* params, const uint8_t key[32],
                                    fhe_client_key** ck, fhe_server_key** sk) {
+    if (const int sim = refuse_simulated(c, "fhe_generate_keys_device_keyed")) return sim;
     if (!key) {
         set_error("null key");
         return FHE_ERR_INVALID;
@@ -727,6 +738,7 @@ int install_tail(fhe_ctx* c, const Params& p, bool had_key) {
 }  // namespace
 
 int fhe_set_compression_key(fhe_ctx* c, const fhe_compression_key* key) {
+    if (const int sim = refuse_simulated(c, "fhe_set_compression_key")) return sim;
     if (!c || !key) {
         set_error("null argument to fhe_set_compression_key");
         return FHE_ERR_INVALID;
@@ -776,6 +788,7 @@ int fhe_set_compression_key(fhe_ctx* c, const fhe_compression_key* key) {
 // generates the BSK mask polynomials inside the Fourier conversion.  Same device state as
 // fhe_set_compression_key of the host-expanded key.
 int fhe_set_compression_key_seeded(fhe_ctx* c, const fhe_seeded_compression_key* sck) {
+    if (const int sim = refuse_simulated(c, "fhe_set_compression_key_seeded")) return sim;
     if (!c || !sck) {
         set_error("null argument to fhe_set_compression_key_seeded");
         return FHE_ERR_INVALID;
@@ -853,6 +866,7 @@ int fhe_ctx_export_compression_state(fhe_ctx* c, int8_t* planes, size_t planes_b
 }
 
 int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
+    if (const int sim = refuse_simulated(c, "fhe_set_server_key")) return sim;
     if (!c || !sk) return FHE_ERR_INVALID;
     FHE_HIP_CHECK(hipSetDevice(c->device));
     const Params& p = sk->params;
@@ -878,6 +892,7 @@ int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
 // never allocated); seeded_key.hip regenerates the KSK masks in place and the BSK mask polynomials inside
 // the Fourier conversion.  Same device state as fhe_set_server_key of the host-expanded key.
 int fhe_set_server_key_seeded(fhe_ctx* c, const fhe_seeded_server_key* ssk) {
+    if (const int sim = refuse_simulated(c, "fhe_set_server_key_seeded")) return sim;
     if (!c || !ssk) return FHE_ERR_INVALID;
     const Params& p = ssk->params;
     Params checked;
@@ -918,6 +933,7 @@ int fhe_set_server_key_seeded(fhe_ctx* c, const fhe_seeded_server_key* ssk) {
 // the masks under the key's own stream id, ks_mfma.hip derives the byte planes.  Same device words as an upload
 // of expand_rekey_key_host's KSK.
 int fhe_set_rekey_key(fhe_ctx* c, const fhe_rekey_key* key) {
+    if (const int sim = refuse_simulated(c, "fhe_set_rekey_key")) return sim;
     if (!c || !key) {
         set_error("null argument to fhe_set_rekey_key");
         return FHE_ERR_INVALID;
@@ -967,6 +983,7 @@ int fhe_set_rekey_key(fhe_ctx* c, const fhe_rekey_key* key) {
 }
 
 int fhe_ctx_export_fourier_bsk(fhe_ctx* c, double* out, size_t len) {
+    if (const int sim = refuse_simulated(c, "fhe_ctx_export_fourier_bsk")) return sim;
     if (!c || !c->has_key) return FHE_ERR_NO_KEY;
     const size_t need = (size_t)c->p.ggsw_count() * 4 * 1024 * 2;
     if (len < need) {
@@ -990,6 +1007,7 @@ int fhe_ctx_params(const fhe_ctx* c, fhe_params* out) {
 }
 
 int fhe_ctx_sync(fhe_ctx* c) {
+    if (const int sim = refuse_simulated(c, "fhe_ctx_sync")) return sim;
     if (!c) return FHE_ERR_INVALID;
     if (c->engine) {
         try {
@@ -1021,6 +1039,7 @@ int fhe_lut_register(fhe_ctx* c, const uint32_t* table, uint32_t table_len, uint
 }
 
 int fhe_pbs_batch(fhe_ctx* c, const uint64_t* in, size_t count, const uint32_t* lut_ids, uint64_t* out) {
+    if (const int sim = refuse_simulated(c, "fhe_pbs_batch")) return sim;
     if (!c || (count && (!in || !lut_ids || !out))) return FHE_ERR_INVALID;
     if (count == 0) return FHE_OK;
     FHE_HIP_CHECK(hipSetDevice(c->device));
@@ -1041,6 +1060,7 @@ int fhe_pbs_batch(fhe_ctx* c, const uint64_t* in, size_t count, const uint32_t* 
 }
 
 int fhe_pbs_batch_device(fhe_ctx* c, const uint64_t* d_in, size_t count, const uint32_t* d_lut, uint64_t* d_out) {
+    if (const int sim = refuse_simulated(c, "fhe_pbs_batch_device")) return sim;
     if (!c) return FHE_ERR_INVALID;
     FHE_HIP_CHECK(hipSetDevice(c->device));
     return c->pbs_device(d_in, count, d_lut, d_out);
@@ -1056,6 +1076,7 @@ hipError_t copy_small(fhe_ctx* c, uint64_t* small, size_t count) {
 }  // namespace
 
 int fhe_keyswitch_batch(fhe_ctx* c, const uint64_t* in, size_t count, uint64_t* small) {
+    if (const int sim = refuse_simulated(c, "fhe_keyswitch_batch")) return sim;
     if (!c || (count && (!in || !small))) return FHE_ERR_INVALID;
     if (!c->has_key) {
         set_error("no server key installed (fhe_set_server_key)");
@@ -1081,6 +1102,7 @@ int fhe_keyswitch_batch(fhe_ctx* c, const uint64_t* in, size_t count, uint64_t* 
 int fhe_pbs_lincomb_batch(fhe_ctx* c, const uint64_t* blocks, size_t nblocks, const uint32_t* term_off,
                           const uint32_t* term_src, const int64_t* term_coef, const uint64_t* cst,
                           const uint32_t* lut_ids, size_t count, uint64_t* small, uint64_t* out) {
+    if (const int sim = refuse_simulated(c, "fhe_pbs_lincomb_batch")) return sim;
     if (!c) return FHE_ERR_INVALID;
     if (!c->has_key) {
         set_error("no server key installed (fhe_set_server_key)");

@@ -14,11 +14,15 @@
 #include "keys.h"
 #include "kernels.h"
 
+struct fhe_ctx;
+
 namespace fhe {
 
 class Engine;
 void set_error(const std::string& msg);
 const char* last_error();
+// FHE_OK on a device context; on a simulated one FHE_ERR_INVALID with a message that names it and `what`
+int refuse_simulated(const fhe_ctx* c, const char* what);
 #define FHE_HIP_CHECK(expr)                                                                   \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
@@ -54,6 +58,9 @@ struct fhe_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool has_key = false;
+    // fhe_host_sim_ctx_create: no device, no stream, no key material; the engine is Engine::kSim.  The radix
+    // layer's entry points run on it, everything that needs device memory or a real key refuses (refuse_simulated)
+    bool simulated = false;
     fhe::Params p;
     fhe::DeviceBuf<uint64_t> d_ksk;
     fhe::DeviceBuf<double2> d_bsk;  // Fourier BSK, blind-rotate layout

@@ -230,6 +230,7 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
     std::vector<size_t> gpu;
     std::vector<std::vector<Term>> live(items.size());
     std::vector<int64_t> csts(items.size());
+    std::vector<uint32_t> labels(items.size(), 0);  // sum coef^2 noise per term (the merged check is at recording)
     for (size_t i = 0; i < items.size(); ++i) {
         PbsItem& it = items[i];
         if (it.raw) {  // caller-guaranteed range (engine.h): no folding, no degree check
@@ -249,12 +250,12 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
                     hi2 += t.coef > 0 ? t.coef * bh : t.coef * bl;
                 }
             }
-            engine_check(noise <= kMaxNoise, "raw PBS input noise above the budget");
+            labels[i] = noise;
             // the caller guarantees the actual input lies in [-16, 16) (kSim checks every sampled one); the
             // degrees alone must keep it inside one period of the negacyclic domain, [-32, 32) units (the
             // widest raw item of the test suite reaches [-22.5, 21.5)), or a misuse could alias unseen
             engine_check(cst2 + lo2 >= -64 && cst2 + hi2 < 64, "raw PBS item: input interval beyond one negacyclic period");
-            if (live[i].empty()) {  // a known input: evaluate on the host
+            if (live[i].empty()) {  // a known input: evaluate on the host (no noise: the label is 0)
                 engine_check(cst2 % 2 == 0 && cst2 >= -32 && cst2 < 32, "raw PBS item: known input off the grid");
                 const int64_t v = cst2 / 2;
                 const int32_t h = v >= 0 ? it.half_table[v] : -it.half_table[v + 16];
@@ -286,7 +287,7 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
         bool ok;
         const uint64_t reach = reachable(live[i], cst, &ok);
         engine_check(ok && (reach >> mc) == 0, "PBS input out of the message space (degree overflow)");
-        engine_check(noise <= kMaxNoise, "PBS input noise above the budget");
+        labels[i] = noise;
         uint32_t lo = 0xffffffffu, hi = 0;
         bool identity = live[i].size() == 1 && live[i][0].coef == 1 && cst == 0 && live[i][0].b.noise <= 1 &&
                         !live[i][0].b.lazy();
@@ -297,6 +298,8 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
             hi = std::max(hi, f);
             if (f != v) identity = false;
         }
+        // an item that folds or aliases on the host launches nothing: its label is checked as it always was
+        if (lo == hi || identity) engine_check(noise <= kMaxNoise, "PBS input noise above the budget");
         if (lo == hi) {
             out[i] = Block::make_trivial(lo);
         } else if (identity) {
@@ -316,16 +319,59 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
     // register LUTs, allocate destinations, record pending nodes
     const uint64_t delta = p.delta();
     std::vector<TermExt> terms;
+    std::vector<uint32_t> term_noise;  // of terms' slots
     const size_t n_before = pending_.size();
     bool all_independent = true;  // no new node reads a pending one
     for (size_t i : gpu) {
-        uint32_t lut = 0;
         const bool raw = items[i].raw;
+        Pending n;
+        PbsDesc& d = n.d;
+        std::memset(&d, 0, sizeof d);
+        n.hold.push_back(nullptr);  // [0]: the output slot, allocated once the item has passed its checks
+        // flatten lazy terms into their slot blocks (merging repeats); dcst in half steps for raw items
+        int64_t dcst = csts[i];
+        const int64_t unit = raw ? 2 : 1;
+        terms.clear();
+        term_noise.clear();
+        const size_t cap = (size_t)kMaxWideTerms;  // > kMaxTerms: staged as a wide combination
+        auto put = [&](const Block& b, int32_t coef) {
+            for (TermExt& u : terms)
+                if (u.src == b.ptr()) {
+                    u.coef += coef;
+                    return;
+                }
+            engine_check(terms.size() < cap, "too many terms in one PBS input");
+            terms.push_back({b.ptr(), coef});
+            term_noise.push_back(b.noise);
+            n.hold.push_back(b.slot);
+            if (b.slot->node >= 0) n.deps.push_back((int32_t)b.slot->node);
+        };
+        for (const Term& t : live[i]) {
+            if (!t.b.lazy()) {
+                put(t.b, t.coef);
+                continue;
+            }
+            dcst += unit * (int64_t)t.coef * t.b.lin_cst;
+            for (const Term& u : *t.b.lin) put(u.b, t.coef * u.coef);
+        }
+        // The budget is enforced on what is launched: a slot named twice (x * x's diagonal products, x & x, a
+        // value and its clone) enters with its coefficients summed, so its error does too -- variance
+        // (sum coef)^2 noise per slot, where the label's sum of coef^2 noise per term assumes independent terms.
+        // Cancellation (x - x) makes the merged figure the smaller one.  Fresh client encryptions uploaded twice
+        // are distinct slots of equal, tiny noise: not seen here, and not a concern.
+        uint64_t merged = 0;
+        for (size_t u = 0; u < terms.size(); ++u) merged += (uint64_t)((int64_t)terms[u].coef * terms[u].coef) * term_noise[u];
+        audit.max_label = std::max<uint64_t>(audit.max_label, labels[i]);
+        audit.max_merged = std::max(audit.max_merged, merged);
+        if (merged > labels[i]) ++audit.n_above_label;
+        engine_check(merged <= kMaxNoise, raw ? "raw PBS input noise above the budget" : "PBS input noise above the budget");
+        uint32_t lut = 0;
         if (raw)
             engine_check(ctx_->register_lut_half(items[i].half_table.data(), &lut) == FHE_OK, "LUT registration");
         else
             engine_check(ctx_->register_lut(items[i].table.data(), &lut) == FHE_OK, "LUT registration");
         out[i].slot = pool_->alloc();
+        n.hold[0] = out[i].slot;
         if (host_mode_ == kSim) {  // the plaintext shadow of this bootstrap
             int64_t v2 = raw ? csts[i] : 2 * csts[i];
             for (const Term& t : live[i]) v2 += (int64_t)t.coef * sim_half2(t.b);
@@ -339,34 +385,6 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
                 o2 = 2 * (int64_t)(items[i].table[v2 / 2] % mc);
             }
             sim_[out[i].ptr()] = o2;
-        }
-        Pending n;
-        PbsDesc& d = n.d;
-        std::memset(&d, 0, sizeof d);
-        n.hold.push_back(out[i].slot);
-        // flatten lazy terms into their slot blocks (merging repeats); dcst in half steps for raw items
-        int64_t dcst = csts[i];
-        const int64_t unit = raw ? 2 : 1;
-        terms.clear();
-        const size_t cap = (size_t)kMaxWideTerms;  // > kMaxTerms: staged as a wide combination
-        auto put = [&](const Block& b, int32_t coef) {
-            for (TermExt& u : terms)
-                if (u.src == b.ptr()) {
-                    u.coef += coef;
-                    return;
-                }
-            engine_check(terms.size() < cap, "too many terms in one PBS input");
-            terms.push_back({b.ptr(), coef});
-            n.hold.push_back(b.slot);
-            if (b.slot->node >= 0) n.deps.push_back((int32_t)b.slot->node);
-        };
-        for (const Term& t : live[i]) {
-            if (!t.b.lazy()) {
-                put(t.b, t.coef);
-                continue;
-            }
-            dcst += unit * (int64_t)t.coef * t.b.lin_cst;
-            for (const Term& u : *t.b.lin) put(u.b, t.coef * u.coef);
         }
         const uint32_t nt = (uint32_t)terms.size();
         if (nt <= (uint32_t)kMaxTerms) {
@@ -915,20 +933,36 @@ void Engine::graph_stats(const std::vector<std::vector<int32_t>>& deps) {
     in_deg_.clear();
 }
 
+// The noise label of a combination that persists (a lazy block, lincomb's output): per slot, the squared SUM of
+// its coefficients times its noise -- what Engine::run computes for a descriptor, so a label never understates a
+// block that names one slot twice.  The terms are slot blocks.
+static uint32_t merged_label(const std::vector<Term>& terms) {
+    uint64_t noise = 0;
+    for (size_t i = 0; i < terms.size(); ++i) {
+        bool first = true;
+        int64_t coef = 0;
+        for (size_t j = 0; j < terms.size(); ++j)
+            if (terms[j].b.ptr() == terms[i].b.ptr()) {
+                if (j < i) first = false;
+                coef += terms[j].coef;
+            }
+        if (first) noise += (uint64_t)(coef * coef) * terms[i].b.noise;
+    }
+    return (uint32_t)std::min<uint64_t>(noise, 0xffffffffu);
+}
+
 Block Engine::lincomb(const std::vector<Term>& terms, uint32_t cst) {
     for (const Term& t : terms) engine_check(!t.b.lazy(), "lincomb of a lazy block");
     flush();
     int64_t c = cst;
-    uint32_t noise = 0;
     std::vector<Term> live;
     for (const Term& t : terms) {
         if (t.b.trivial())
             c += (int64_t)t.coef * t.b.value;
-        else if (t.coef) {
+        else if (t.coef)
             live.push_back(t);
-            noise += (uint32_t)(t.coef * t.coef) * t.b.noise;
-        }
     }
+    const uint32_t noise = merged_label(live);
     bool ok;
     const uint64_t reach = reachable(live, c, &ok);
     engine_check(ok && (reach >> ctx_->p.msg_carry()) == 0, "linear combination out of range");
@@ -968,8 +1002,8 @@ Block block_lazy(const std::vector<Term>& terms, int32_t cst, uint32_t degree) {
             continue;
         }
         lin->push_back(t);
-        b.noise += (uint32_t)(t.coef * t.coef) * t.b.noise;
     }
+    b.noise = merged_label(*lin);
     if (lin->empty()) {
         engine_check(cst >= 0 && (uint32_t)cst <= degree, "lazy constant out of its range");
         return Block::make_trivial((uint32_t)cst);

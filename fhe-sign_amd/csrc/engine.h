@@ -111,7 +111,8 @@ struct Term {
     int32_t coef;
 };
 
-// Lazy block of the given semantic range [0, degree] (caller's guarantee; noise = sum coef^2 noise).
+// Lazy block of the given semantic range [0, degree] (caller's guarantee; noise = sum coef^2 noise, a slot
+// named twice counted with its coefficients summed).
 Block block_lazy(const std::vector<Term>& terms, int32_t cst, uint32_t degree);
 
 struct PbsItem {
@@ -295,6 +296,14 @@ public:
     std::vector<uint32_t> level_log;
     static constexpr uint32_t kLevelSplit = 1u << 31;
     uint64_t rank_pbs = 0;  // bootstraps this rank ran itself (fanned-out levels: its slice)
+    // The noise budget as enforced, over the recorded bootstraps since the last reset (fhe_ctx_noise_audit).
+    // label: sum coef^2 noise over an item's terms, which treats them as independent; merged: per slot of the
+    // descriptor the squared sum of its coefficients times its noise -- the variance of what is launched, and the
+    // figure run() holds against kMaxNoise.  They differ where an item names one slot twice.
+    struct NoiseAudit {
+        uint64_t max_label = 0, max_merged = 0;
+        uint64_t n_above_label = 0;  // items whose merged noise exceeds their label
+    } audit;
     // kDry / kSim: FNV-1a over every scheduled level's nodes in order (LUT, terms' coefficients, constant,
     // producers by recording index) -- no addresses.  Equal across processes iff the program records
     // the same graph in the same order, which the fan-out's split relies on (every rank scatters the

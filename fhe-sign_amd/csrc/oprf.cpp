@@ -137,6 +137,7 @@ int fhe_ctx_time_oprf_rows(fhe_ctx* c, size_t count, uint32_t n, uint32_t reps, 
 }
 
 int fhe_oprf_blocks(fhe_ctx* c, const uint8_t seed[32], size_t count, uint32_t bits, uint64_t* out) {
+    if (const int sim = refuse_simulated(c, "fhe_oprf_blocks")) return sim;
     if (!c) return invalid("null context");
     if (!c->has_key || !c->engine) {
         set_error("no server key installed (fhe_set_server_key)");

@@ -118,6 +118,7 @@ int fhe_rerandomize_zero_host(const fhe_public_key* pk, const uint8_t* seed, siz
 }
 
 int fhe_set_public_key(fhe_ctx* c, const fhe_public_key* pk) {
+    if (const int sim = refuse_simulated(c, "fhe_set_public_key")) return sim;
     if (!c || !pk) return invalid("null argument to fhe_set_public_key");
     if (!c->has_key || !c->engine) {
         set_error("no server key installed: fhe_set_public_key comes after fhe_set_server_key");

@@ -552,6 +552,7 @@ extern "C" {
 // one signature, unreduced (the reference's block) or reduced
 static int sign_one(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
                     const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, bool reduced, uint8_t sig[64]) {
+    if (const int sim = fhe::refuse_simulated(ctx, "the signer")) return sim;
     if (!sig) return FHE_ERR_INVALID;
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
@@ -617,6 +618,7 @@ int fhe_schnorr_eval_s_public(fhe_ctx* ctx, const uint8_t e[32], const uint8_t k
 static int sign_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
                        const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, const uint8_t* domain,
                        size_t domain_len, bool reduced, uint8_t sig[64]) {
+    if (const int sim = fhe::refuse_simulated(ctx, "the signer")) return sim;
     if (!ctx || !ck || (len && !msg) || !k0 || !privkey || !privkey_fhe || (domain_len && !domain) || !sig) {
         set_error("null argument to fhe_schnorr_sign_fhe_with_k0_rerand");
         return FHE_ERR_INVALID;
@@ -666,6 +668,7 @@ int fhe_schnorr_sign_fhe_with_k0_rerand_reduced(fhe_ctx* ctx, fhe_client_key* ck
 static int sign_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint8_t* const* msgs, const size_t* lens,
                       const uint8_t* k0s, const uint8_t* privkeys, const fhe_biguint* const* privkeys_fhe, int mode,
                       bool reduced, uint8_t* sigs) {
+    if (const int sim = fhe::refuse_simulated(ctx, "the signer")) return sim;
     if (count && (!msgs || !lens || !k0s || !privkeys || !privkeys_fhe || !sigs)) return FHE_ERR_INVALID;
     std::vector<SignJob> jobs(count);
     for (SignJob& j : jobs) j.reduced = reduced;

@@ -831,6 +831,35 @@ class Context:
         return int(cy.value), int(tk.value), int(wg.value)
 
 
+class SimContext(Context):
+    """Test hook (fhe_host_sim_ctx_create): a context without a device, whose engine shadows every block's
+    plaintext on the host.  set_server_key(SimContext()) makes FheUint / BigUintFHE run through the C ABI's
+    real code on the CPU; SimKey() stands where a client key is asked for.  What needs device memory or a real
+    key raises FheError.  The shadow evaluates a bootstrap when it is recorded: such a run sees every recorded
+    graph and every value, not the launch order."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        check(load().fhe_host_sim_ctx_create(C.byref(h)))
+        self._h = h
+        self.params = default_params()
+        self._comp_params = None
+
+
+class SimKey:
+    """The key of a SimContext's encryptions and decryptions: a NULL handle, which only that context accepts."""
+    handle = None
+    params = None
+
+
+def noise_audit(ctx: Context, reset: bool = False):
+    """(largest label, largest merged noise, bootstraps whose merged noise exceeds their label) since the last
+    reset (fhe_ctx_noise_audit): the budget of 25 units is held against the merged figure."""
+    a, b, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(load().fhe_ctx_noise_audit(ctx.handle, C.byref(a), C.byref(b), C.byref(n), 1 if reset else 0))
+    return int(a.value), int(b.value), int(n.value)
+
+
 TUNE_KEYS = {"kara_min": 1, "kara_compat_min": 2, "kara_force": 3, "div_r16_lead": 4, "scalar_div_residue": 5,
              "flush_depth": 6}
 

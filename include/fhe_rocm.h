@@ -391,6 +391,13 @@ int fhe_radix_shl(fhe_ctx* ctx, const fhe_radix* a, const fhe_radix* amount, fhe
 int fhe_radix_bitand(fhe_ctx* ctx, const fhe_radix* a, const fhe_radix* b, fhe_radix** out);
 /* engine statistics since context creation: bootstraps executed and dependency levels */
 int fhe_ctx_stats(fhe_ctx* ctx, uint64_t* pbs_count, uint64_t* levels);
+/* The noise budget as enforced, over the bootstraps recorded since the last reset.  A bootstrap's input is a
+ * linear combination of blocks; its label is sum coef^2 noise over the terms, its merged noise the same per SLOT
+ * with a repeated slot's coefficients summed first (x * x, x & x, a value and its clone: 4x + x is 25 units, not
+ * 17).  The engine holds the merged figure against its budget of 25.  max_label / max_merged: the largest of each;
+ * n_above_label: bootstraps whose merged noise exceeds their label.  Outputs optional; reset != 0 clears the
+ * counters.  Device and simulated contexts. */
+int fhe_ctx_noise_audit(fhe_ctx* ctx, uint64_t* max_label, uint64_t* max_merged, uint64_t* n_above_label, int reset);
 /* bootstraps per launched dependency level, in launch order, since the last reset (host-side
  * record, at most 2^20 levels): *n = the number recorded, min(cap, *n) written to sizes; reset != 0
  * clears the record.  bench.py replays these level sizes through the CPU restatement. */
@@ -484,6 +491,19 @@ int fhe_host_sim_biguint_mul_add_columns(const uint32_t* a, size_t la, const uin
  * prefix columns: vals holds nprefix records of 31 block values (each <= 3): column 0's block, then
  * the two blocks of each column 1..15; K = sum_m (column m's sum) 4^m.  g: nprefix outputs. */
 int fhe_host_sim_chain_g(const uint8_t* vals, size_t nprefix, uint32_t* g, uint64_t* pbs, uint64_t* levels);
+/* A simulated context (test hook): no device, no stream, the default parameters, a simulating engine.  The radix
+ * and BigUintFHE entry points run on it through their real code: fhe_radix_encrypt / fhe_biguint_encrypt make
+ * shadowed blocks of the plaintext (the client key is ignored and may be NULL), fhe_radix_trivial, _clone, _cast,
+ * every binary, unary and scalar op (the _words forms included), the BigUintFHE add / mul / mul_add and column
+ * forms, the pseudo-Mersenne reductions, and the decryptions, which make the flush a device decryption makes
+ * (nothing is launched, the graph is scheduled) and read the shadow.  fhe_ctx_stats, fhe_ctx_level_log and
+ * fhe_ctx_noise_audit report on it.  Everything that needs device memory or a real key -- export and serialize,
+ * digest and re-randomize, compress and every expand, random, broadcast, the raw pbs / keyswitch / pbs_lincomb,
+ * every fhe_set_*_key, the signer -- returns FHE_ERR_INVALID with a message that names the simulated context, and
+ * leaves it usable.  fhe_ctx_destroy frees it.
+ * Known limit: the shadow evaluates a bootstrap when it is recorded, so a run on this context sees every recorded
+ * graph and every value, not the launch order. */
+int fhe_host_sim_ctx_create(fhe_ctx** ctx);
 /* Pseudo-Mersenne reduction x mod (2^k_bits - c) (fhe_radix_rem_pseudo_mersenne below) without a GPU or a key.
  * Simulated run on a `bits`-wide operand x (words LSB first): out gets the k_bits-wide result (nout >=
  * ceil(k_bits / 64) words); pbs, levels, folds optional.  Refusals (odd k, c = 0, c >= 2^(k-2), bits above

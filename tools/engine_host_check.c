@@ -252,6 +252,123 @@ static void schedule(void) {
     status("schedule_levels dependency on a later node", fhe_schedule_levels(off, bad, 5, 0, level_of, &nlevels), 0);
 }
 
+// The simulated context (fhe_host_sim_ctx_create): the C ABI's own entry points on the CPU.  A short chain whose
+// results feed the next op, the aliasing matrix at one width (op(x, x), op(x, clone), op(x, cast round trip)), a
+// BigUintFHE product added to itself before and after its decryption, the audit of the noise budget, and what
+// such a context refuses.  Last in main: the generator's earlier draws stay what they were.
+static uint64_t sim_value(fhe_ctx* c, fhe_radix* x) {
+    uint64_t w[2] = {0, 0};
+    status("sim_ctx decrypt", fhe_radix_decrypt(c, NULL, x, w, 2), 1);
+    return w[0];
+}
+typedef int (*binop_fn)(fhe_ctx*, const fhe_radix*, const fhe_radix*, fhe_radix**);
+static void sim_context(void) {
+    static const struct {
+        const char* name;
+        binop_fn fn;
+    } ops[] = {{"add", fhe_radix_add}, {"sub", fhe_radix_sub}, {"mul", fhe_radix_mul},       {"and", fhe_radix_bitand},
+               {"min", fhe_radix_min}, {"max", fhe_radix_max}, {"lt", fhe_radix_lt},         {"shr", fhe_radix_shr},
+               {"shl", fhe_radix_shl}, {"div", fhe_radix_div}, {"rem", fhe_radix_rem}};
+    const int nops = (int)(sizeof ops / sizeof ops[0]);
+    fhe_ctx* c = NULL;
+    if (!status("sim_ctx create", fhe_host_sim_ctx_create(&c), 1)) return;
+    // a chain at 34 bits: each result is the next step's first operand, the second one is the value itself every other step
+    {
+        uint64_t xw[1] = {rnd() & ((1ull << 34) - 1)}, yw[1] = {rnd() & ((1ull << 34) - 1)};
+        fhe_radix *x = NULL, *y = NULL;
+        status("sim_ctx encrypt", fhe_radix_encrypt(c, NULL, xw, 34, &x), 1);
+        status("sim_ctx encrypt", fhe_radix_encrypt(c, NULL, yw, 34, &y), 1);
+        printf("sim_ctx chain bits=34 x=%010" PRIx64 " y=%010" PRIx64 ":", xw[0], yw[0]);
+        for (int step = 0; step < 12 && x; ++step) {
+            const int op = step % nops == 6 ? 0 : step % nops;  // lt's one bit is not fed on
+            fhe_radix* r = NULL;
+            const int self = step % 2 && op != 1 && op != 7 && op < 9;  // not where x op x is a constant
+            if (!status(ops[op].name, ops[op].fn(c, x, self ? x : y, &r), 1)) break;
+            fhe_radix_destroy(x);  // released while its consumer is pending
+            x = r;
+            if (step % 3 == 2) printf(" %s=%010" PRIx64, ops[op].name, sim_value(c, x));
+        }
+        printf(" end=%010" PRIx64 "\n", x ? sim_value(c, x) : 0);
+        fhe_radix_destroy(x);
+        fhe_radix_destroy(y);
+    }
+    // the aliasing matrix at 8 bits
+    const uint64_t vals[5] = {0, 1, 0xff, 0x80, 0xa5};
+    for (int v = 0; v < 5; ++v) {
+        fhe_radix *x = NULL, *kinds[3] = {NULL, NULL, NULL}, *wide = NULL;
+        status("sim_ctx encrypt", fhe_radix_encrypt(c, NULL, &vals[v], 8, &x), 1);
+        kinds[0] = x;
+        status("sim_ctx clone", fhe_radix_clone(x, &kinds[1]), 1);
+        status("sim_ctx cast", fhe_radix_cast(c, x, 14, &wide), 1);
+        status("sim_ctx cast", fhe_radix_cast(c, wide, 8, &kinds[2]), 1);
+        for (int k = 0; k < 3; ++k) {
+            fhe_radix* out[16] = {NULL};
+            for (int op = 0; op < nops; ++op) status(ops[op].name, ops[op].fn(c, x, kinds[k], &out[op]), 1);
+            status("divrem", fhe_radix_divrem(c, x, kinds[k], &out[nops], &out[nops + 1]), 1);
+            printf("sim_ctx alias x=%02" PRIx64 " kind=%d:", vals[v], k);
+            for (int op = 0; op < nops + 2; ++op) {
+                printf(" %02" PRIx64, out[op] ? sim_value(c, out[op]) : (uint64_t)0xee);
+                fhe_radix_destroy(out[op]);
+            }
+            printf("\n");
+        }
+        fhe_radix_destroy(wide);
+        for (int k = 0; k < 3; ++k) fhe_radix_destroy(kinds[k]);
+    }
+    // P = a * b, P + P: decrypted before and after the reuse, compat and fast
+    for (int mode = 0; mode <= 1; ++mode) {
+        uint32_t a[3], b[3], out[16];
+        limbs(a, 3), limbs(b, 3);
+        a[2] |= 1u << 31, b[2] |= 1u << 31;
+        fhe_biguint *A = NULL, *B = NULL, *P = NULL, *S = NULL, *S2 = NULL;
+        size_t n = 0;
+        status("sim_ctx biguint encrypt", fhe_biguint_encrypt(c, NULL, a, 3, &A), 1);
+        status("sim_ctx biguint encrypt", fhe_biguint_encrypt(c, NULL, b, 3, &B), 1);
+        status("sim_ctx biguint mul", fhe_biguint_mul(c, A, B, mode, &P), 1);
+        status("sim_ctx P + P", fhe_biguint_add(c, P, P, mode, &S), 1);
+        printf("sim_ctx P+P mode=%d sum=", mode);
+        if (status("sim_ctx biguint decrypt", fhe_biguint_decrypt(c, NULL, S, out, 16, &n), 1)) limbs_out(out, n);
+        printf(" P=");
+        if (status("sim_ctx biguint decrypt", fhe_biguint_decrypt(c, NULL, P, out, 16, &n), 1)) limbs_out(out, n);
+        status("sim_ctx S + S", fhe_biguint_add(c, S, S, mode, &S2), 1);
+        fhe_biguint_destroy(S);  // its propagation is pending behind the decryption above
+        printf(" 4P=");
+        if (status("sim_ctx biguint decrypt", fhe_biguint_decrypt(c, NULL, S2, out, 16, &n), 1)) limbs_out(out, n);
+        printf("\n");
+        fhe_biguint_destroy(A), fhe_biguint_destroy(B), fhe_biguint_destroy(P), fhe_biguint_destroy(S2);
+    }
+    uint64_t label = 0, merged = 0, above = 0, pbs = 0, levels = 0;
+    status("sim_ctx noise audit", fhe_ctx_noise_audit(c, &label, &merged, &above, 1), 1);
+    status("sim_ctx stats", fhe_ctx_stats(c, &pbs, &levels), 1);
+    printf("sim_ctx audit max_label=%" PRIu64 " max_merged=%" PRIu64 " above_label=%" PRIu64 " pbs=%" PRIu64 " levels=%" PRIu64 "\n",
+           label, merged, above, pbs, levels);
+    // refusals: compared line for line, and the context works after them
+    {
+        const uint64_t w[1] = {0x5a};
+        uint64_t cts[4], words[1] = {0};
+        uint8_t buf[64], seed[32] = {1};
+        size_t len = 0;
+        fhe_radix *x = NULL, *a10 = NULL, *r = NULL;
+        status("sim_ctx encrypt", fhe_radix_encrypt(c, NULL, w, 8, &x), 1);
+        status("sim_ctx encrypt", fhe_radix_encrypt(c, NULL, w, 10, &a10), 1);
+        status("sim_ctx refuses export", fhe_radix_export(c, x, cts, 4), 0);
+        status("sim_ctx refuses serialize", fhe_radix_serialize(c, x, buf, sizeof buf, &len), 0);
+        status("sim_ctx refuses digest", fhe_radix_digest(c, x, buf), 0);
+        status("sim_ctx refuses rerandomize", fhe_radix_rerandomize(c, x, seed, &r), 0);
+        status("sim_ctx refuses random", fhe_radix_random(c, seed, 8, 8, &r), 0);
+        status("sim_ctx refuses broadcast", fhe_ctx_broadcast_radix(c, &x, 0), 0);
+        status("sim_ctx refuses set_server_key", fhe_set_server_key(c, NULL), 0);
+        status("sim_ctx refuses pbs", fhe_pbs_batch(c, cts, 0, NULL, cts), 0);
+        status("sim_ctx width mismatch", fhe_radix_add(c, x, a10, &r), 0);
+        status("sim_ctx division by zero", fhe_radix_scalar_div(c, x, 0, &r), 0);
+        if (status("sim_ctx after the refusals", fhe_radix_scalar_mul(c, x, 3, &r), 1) &&
+            status("sim_ctx after the refusals", fhe_radix_decrypt(c, NULL, r, words, 1), 1))
+            printf("sim_ctx after the refusals 3 * 5a = %02" PRIx64 "\n", words[0]);
+        fhe_radix_destroy(x), fhe_radix_destroy(a10), fhe_radix_destroy(r);
+    }
+    fhe_ctx_destroy(c);
+}
+
 int main(void) {
     radix_stats();
     sim_radix();
@@ -261,6 +378,7 @@ int main(void) {
     rem_pseudo_mersenne();
     mul_add_rem();
     schedule();
+    sim_context();
     printf(g_failed ? "engine host modes: a required case failed\n" : "engine host modes: every required case ran\n");
     return g_failed;
 }
