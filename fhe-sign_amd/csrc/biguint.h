@@ -63,5 +63,8 @@ void engine_eager_next_batch(fhe_ctx* c, bool on);
 // before the engine's next launch (Engine::upload_deferred); the client key must not be used meanwhile.
 int biguint_encrypt_batch(fhe_ctx* c, fhe_client_key* ck, const std::vector<const std::vector<uint32_t>*>& limbs,
                           fhe_biguint** outs, bool deferred = false);
+// the C boundary's ownership check of a BigUintFHE handle (capi_internal.h owned(), capi_radix.cpp), for the
+// entry points outside the radix layer's files: FHE_OK, or FHE_ERR_INVALID naming `operand`
+int biguint_owned(const fhe_ctx* c, const fhe_biguint* x, const char* operand);
 
 }  // namespace fhe

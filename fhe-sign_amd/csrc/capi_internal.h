@@ -2,6 +2,7 @@
 // capi_host.cpp: the host-only hooks).  Private to csrc/.
 #pragma once
 #include <exception>
+#include <string>
 #include <vector>
 
 #include "biguint.h"
@@ -35,6 +36,36 @@ int guarded(F&& f) {
         return FHE_ERR_INVALID;
     }
 }
+
+// Ownership at the C boundary (Engine::check_owner): every entry point that takes a context and a handle asks
+// this of each handle first, under its operand's name, so that a value made under another context is refused
+// before the entry point allocates, records or reads anything.  The engine repeats the check where blocks enter
+// it; this one names the operand.  FHE_OK, or FHE_ERR_INVALID with the error text set.
+inline int owned(const fhe_ctx* c, const Blocks& blocks, const char* operand) {
+    if (!c || !c->engine) return FHE_OK;  // no engine to own anything: the entry point's own checks refuse
+    for (const Block& b : blocks)
+        if (!c->engine->owns(b)) {
+            set_error(std::string("operand ") + operand + " was made under another context");
+            return FHE_ERR_INVALID;
+        }
+    return FHE_OK;
+}
+inline int owned(const fhe_ctx* c, const std::vector<Blocks>& cols, const char* operand) {
+    for (const Blocks& col : cols)
+        if (const int rc = owned(c, col, operand)) return rc;
+    return FHE_OK;
+}
+inline int owned(const fhe_ctx* c, const fhe_radix* x, const char* operand) { return owned(c, x->r.blocks, operand); }
+inline int owned(const fhe_ctx* c, const fhe_biguint* x, const char* operand) {
+    for (const Radix& d : x->v.digits)
+        if (const int rc = owned(c, d.blocks, operand)) return rc;
+    if (x->v.product_cols)
+        if (const int rc = owned(c, *x->v.product_cols, operand)) return rc;
+    if (x->v.sum_cols)
+        if (const int rc = owned(c, *x->v.sum_cols, operand)) return rc;
+    return FHE_OK;
+}
+inline int owned(const fhe_ctx* c, const fhe_columns* x, const char* operand) { return owned(c, x->cols, operand); }
 
 inline BigConst words_of(const uint64_t* s, size_t nwords) { return BigConst(s, s + nwords); }
 

@@ -63,6 +63,7 @@ std::vector<int64_t> read_blocks(fhe_ctx* c, const fhe_client_key* ck, const std
     std::vector<int64_t> vals(enc.size());
     if (c->simulated) {
         if (enc.empty()) return vals;
+        c->engine->check_owner(enc);  // before the flush, as download_many's
         if (only_needed)
             c->engine->flush_for(enc);
         else
@@ -103,6 +104,7 @@ int binop(fhe_ctx* c, const fhe_radix* a, const fhe_radix* b, fhe_radix** out, F
         set_error("operands must have the same bit width");
         return FHE_ERR_INVALID;
     }
+    if ((rc = owned(c, a, "a")) || (rc = owned(c, b, "b"))) return rc;
     return guarded([&] {
         *out = wrap(f(*c->engine, a->r, b->r), a->bits);
         return FHE_OK;
@@ -114,6 +116,7 @@ int unop(fhe_ctx* c, const fhe_radix* a, fhe_radix** out, F&& f) {
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !out) return FHE_ERR_INVALID;
+    if ((rc = owned(c, a, "a"))) return rc;
     return guarded([&] {
         *out = wrap(f(*c->engine, a->r), a->bits);
         return FHE_OK;
@@ -126,6 +129,8 @@ namespace fhe {
 void engine_eager_next_batch(fhe_ctx* c, bool on) {
     if (c && c->engine) c->engine->eager_next_batch(on);
 }
+
+int biguint_owned(const fhe_ctx* c, const fhe_biguint* x, const char* operand) { return x ? owned(c, x, operand) : FHE_OK; }
 
 // several BigUintFHE encryptions as one batch -- one pass of encrypt_big_many (its host threads over the
 // whole batch) and one upload: ciphertexts and encryption-stream state identical to encrypting the
@@ -258,6 +263,7 @@ int fhe_radix_decrypt(fhe_ctx* c, const fhe_client_key* ck, const fhe_radix* x, 
         set_error("invalid arguments to fhe_radix_decrypt");
         return FHE_ERR_INVALID;
     }
+    if ((rc = owned(c, x, "x"))) return rc;
     return guarded([&] {
         std::memset(words, 0, nwords * 8);
         // value = sum v_k 4^k mod 2^bits (v_k incl. carry bits)
@@ -310,6 +316,7 @@ int fhe_radix_export(fhe_ctx* c, const fhe_radix* x, uint64_t* cts, size_t nword
     int rc = need_engine(c);
     if (rc) return rc;
     if (!x || !cts || nwords < (size_t)x->r.nblocks() * kBigCt) return FHE_ERR_INVALID;
+    if ((rc = owned(c, x, "x"))) return rc;
     return guarded([&] {
         std::vector<const Block*> enc;
         for (uint32_t k = 0; k < x->r.nblocks(); ++k) {
@@ -365,6 +372,7 @@ int fhe_radix_divrem(fhe_ctx* c, const fhe_radix* a, const fhe_radix* b, fhe_rad
         set_error("operands must have the same bit width");
         return FHE_ERR_INVALID;
     }
+    if ((rc = owned(c, a, "a")) || (rc = owned(c, b, "b"))) return rc;
     return guarded([&] {
         auto qr = radix_divrem(*c->engine, a->r, b->r);
         if (q) *q = wrap(std::move(qr.first), a->bits);
@@ -382,6 +390,7 @@ int fhe_radix_shr(fhe_ctx* c, const fhe_radix* a, const fhe_radix* amount, fhe_r
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !amount || !out) return FHE_ERR_INVALID;
+    if ((rc = owned(c, a, "a")) || (rc = owned(c, amount, "amount"))) return rc;
     return guarded([&] {
         *out = wrap(radix_shr(*c->engine, a->r, amount->r), a->bits);
         return FHE_OK;
@@ -391,6 +400,7 @@ int fhe_radix_shl(fhe_ctx* c, const fhe_radix* a, const fhe_radix* amount, fhe_r
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !amount || !out) return FHE_ERR_INVALID;
+    if ((rc = owned(c, a, "a")) || (rc = owned(c, amount, "amount"))) return rc;
     return guarded([&] {
         *out = wrap(radix_shl(*c->engine, a->r, amount->r), a->bits);
         return FHE_OK;
@@ -474,8 +484,9 @@ int fhe_radix_scalar_rem_words(fhe_ctx* c, const fhe_radix* a, const uint64_t* d
 }
 int fhe_radix_cast(fhe_ctx* c, const fhe_radix* a, uint32_t bits, fhe_radix** out) {
     if (!a || !out || !valid_bits(bits)) return FHE_ERR_INVALID;
+    // no slot is read; with a context, the result is a value of that context, so the operand must be too
+    if (const int rc = owned(c, a, "a")) return rc;
     *out = wrap(radix_resize(a->r, bits / 2), bits);
-    (void)c;
     return FHE_OK;
 }
 int fhe_ctx_level_log(fhe_ctx* c, uint32_t* sizes, size_t cap, size_t* n, int reset) {
@@ -515,6 +526,8 @@ int fhe_ctx_noise_audit(fhe_ctx* c, uint64_t* max_label, uint64_t* max_merged, u
 int fhe_ctx_broadcast_radix(fhe_ctx* c, fhe_radix** x, int root) {
     const bool sends = c && (!c->attached() || c->rank == root);
     if (!c || !x || (sends && !*x)) return FHE_ERR_INVALID;
+    if (sends)
+        if (const int rc = owned(c, *x, "x")) return rc;
     std::vector<Radix> g;
     if (sends) g.push_back((*x)->r);
     const int rc = bcast_radix_groups(c, root, &g);
@@ -531,6 +544,8 @@ int fhe_ctx_broadcast_radix(fhe_ctx* c, fhe_radix** x, int root) {
 int fhe_ctx_broadcast_biguint(fhe_ctx* c, fhe_biguint** x, int root) {
     const bool sends = c && (!c->attached() || c->rank == root);
     if (!c || !x || (sends && !*x)) return FHE_ERR_INVALID;
+    if (sends)
+        if (const int rc = owned(c, *x, "x")) return rc;
     std::vector<Radix> g;
     if (sends) {
         g = (*x)->v.digits;
@@ -576,6 +591,7 @@ int fhe_biguint_decrypt(fhe_ctx* c, const fhe_client_key* ck, const fhe_biguint*
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if ((!ck && !c->simulated) || !x || !n) return FHE_ERR_INVALID;
+    if ((rc = owned(c, x, "x"))) return rc;
     *n = x->v.digits.size();
     if (cap < *n || (*n && !limbs)) {
         set_error("limb buffer too small");
@@ -636,6 +652,7 @@ int fhe_biguint_add(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, int 
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !out) return FHE_ERR_INVALID;
+    if ((rc = owned(c, a, "a")) || (rc = owned(c, b, "b"))) return rc;
     return guarded([&] {
         auto r = std::make_unique<fhe_biguint>();
         r->v = biguint_add(*c->engine, a->v, b->v, mode);
@@ -648,6 +665,7 @@ int fhe_biguint_mul(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, int 
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !out) return FHE_ERR_INVALID;
+    if ((rc = owned(c, a, "a")) || (rc = owned(c, b, "b"))) return rc;
     return guarded([&] {
         auto r = std::make_unique<fhe_biguint>();
         r->v = biguint_mul(*c->engine, a->v, b->v, mode);
@@ -663,6 +681,7 @@ int fhe_biguint_mul_add_columns(fhe_ctx* c, const fhe_biguint* a, const fhe_bigu
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !k || !out || (mode != kCompat && mode != kFast)) return FHE_ERR_INVALID;
+    if ((rc = owned(c, a, "a")) || (rc = owned(c, b, "b")) || (rc = owned(c, k, "k"))) return rc;
     return guarded([&] {
         auto r = std::make_unique<fhe_columns>();
         r->cols = biguint_mul_add_columns(*c->engine, a->v, b->v, k->v, mode, &r->nblocks);
@@ -677,6 +696,7 @@ int fhe_radix_scalar_mul_add_columns(fhe_ctx* c, const fhe_radix* a, const uint6
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !out || (!m && nm) || (!k && nk)) return FHE_ERR_INVALID;
+    if ((rc = owned(c, a, "a"))) return rc;
     const BigConst vm = words_of(m, nm), vk = words_of(k, nk);
     return guarded([&] {
         auto r = std::make_unique<fhe_columns>();
@@ -701,6 +721,7 @@ int fhe_columns_decrypt(fhe_ctx* c, const fhe_client_key* ck, const fhe_columns*
         set_error("invalid arguments to fhe_columns_decrypt");
         return FHE_ERR_INVALID;
     }
+    if ((rc = owned(c, x, "x"))) return rc;
     return guarded([&] {
         decrypt_columns(c, ck, x->cols, x->nblocks, words, nwords, false);
         return FHE_OK;
@@ -718,6 +739,7 @@ int fhe_radix_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a, uint32_t k_bit
         set_error("invalid arguments to fhe_radix_rem_pseudo_mersenne");
         return FHE_ERR_INVALID;
     }
+    if ((rc = owned(c, a, "a"))) return rc;
     const BigConst cc = words_of(c_words, nc);
     return guarded([&] {
         *out = wrap(radix_rem_pseudo_mersenne(*c->engine, a->r, k_bits, cc), k_bits);
@@ -735,6 +757,7 @@ int fhe_columns_rem_pseudo_mersenne(fhe_ctx* c, const fhe_columns* x, uint32_t k
         set_error("invalid arguments to fhe_columns_rem_pseudo_mersenne");
         return FHE_ERR_INVALID;
     }
+    if ((rc = owned(c, x, "x"))) return rc;
     const BigConst cc = words_of(c_words, nc);
     return guarded([&] {
         *out = wrap(radix_rem_pseudo_mersenne_columns(*c->engine, x->cols, x->nblocks, k_bits, cc), k_bits);
@@ -753,6 +776,7 @@ int fhe_radix_scalar_mul_add_rem_pseudo_mersenne(fhe_ctx* c, const fhe_radix* a,
         set_error("invalid arguments to fhe_radix_scalar_mul_add_rem_pseudo_mersenne");
         return FHE_ERR_INVALID;
     }
+    if ((rc = owned(c, a, "a"))) return rc;
     const BigConst cc = words_of(c_words, nc), vm = words_of(m, nm), vk = words_of(k, nk);
     return guarded([&] {
         *out = wrap(radix_scalar_mul_add_rem_pseudo_mersenne(*c->engine, a->r, vm, vk, k_bits, cc), k_bits);
@@ -765,6 +789,7 @@ int fhe_biguint_mul_add(fhe_ctx* c, const fhe_biguint* a, const fhe_biguint* b, 
     int rc = need_engine(c, kSimOk);
     if (rc) return rc;
     if (!a || !b || !k || !out) return FHE_ERR_INVALID;
+    if ((rc = owned(c, a, "a")) || (rc = owned(c, b, "b")) || (rc = owned(c, k, "k"))) return rc;
     return guarded([&] {
         auto r = std::make_unique<fhe_biguint>();
         r->v = biguint_mul_add(*c->engine, a->v, b->v, k->v, mode);
@@ -843,6 +868,7 @@ int fhe_radix_serialize(fhe_ctx* c, const fhe_radix* x, uint8_t* buf, size_t cap
     int rc = need_engine(c);
     if (rc) return rc;
     if (!x || !len) return FHE_ERR_INVALID;
+    if ((rc = owned(c, x, "x"))) return rc;
     return guarded([&] {
         ser::Writer w;
         w.params(c->p);
@@ -882,6 +908,7 @@ int fhe_biguint_serialize(fhe_ctx* c, const fhe_biguint* x, uint8_t* buf, size_t
     int rc = need_engine(c);
     if (rc) return rc;
     if (!x || !len) return FHE_ERR_INVALID;
+    if ((rc = owned(c, x, "x"))) return rc;
     return guarded([&] {
         ser::Writer w;
         w.params(c->p);
@@ -1177,6 +1204,7 @@ int fhe_radix_compress(fhe_ctx* c, const fhe_radix* x, fhe_compressed_list** out
     int rc = need_engine(c);
     if (rc) return rc;
     if (!x || !out) return invalid("null argument to fhe_radix_compress");
+    if ((rc = owned(c, x, "x"))) return rc;
     std::vector<const Block*> blocks;
     for (const Block& b : x->r.blocks) blocks.push_back(&b);
     return compress_blocks(c, blocks, FHE_SEEDED_RADIX, x->bits, out);
@@ -1186,6 +1214,7 @@ int fhe_biguint_compress(fhe_ctx* c, const fhe_biguint* x, fhe_compressed_list**
     int rc = need_engine(c);
     if (rc) return rc;
     if (!x || !out) return invalid("null argument to fhe_biguint_compress");
+    if ((rc = owned(c, x, "x"))) return rc;
     std::vector<const Block*> blocks;
     for (const Radix& d : x->v.digits) {
         if (d.nblocks() != kLimbBlocks) return invalid("fhe_biguint_compress: a limb is not a 32-bit radix");
@@ -1296,6 +1325,7 @@ int radix_switched(fhe_ctx* c, const fhe_radix* x, fhe_switched_list** out, bool
     int rc = need_engine(c);
     if (rc) return rc;
     if (!x || !out) return invalid("null argument to fhe_radix_compress_switched");
+    if ((rc = owned(c, x, "x"))) return rc;
     std::vector<const Block*> blocks;
     for (const Block& b : x->r.blocks) blocks.push_back(&b);
     return switched_blocks(c, blocks, FHE_SEEDED_RADIX, x->bits, out, rekey);
@@ -1304,6 +1334,7 @@ int biguint_switched(fhe_ctx* c, const fhe_biguint* x, fhe_switched_list** out, 
     int rc = need_engine(c);
     if (rc) return rc;
     if (!x || !out) return invalid("null argument to fhe_biguint_compress_switched");
+    if ((rc = owned(c, x, "x"))) return rc;
     std::vector<const Block*> blocks;
     for (const Radix& d : x->v.digits) {
         if (d.nblocks() != kLimbBlocks) return invalid("fhe_biguint_compress_switched: a limb is not a 32-bit radix");
@@ -1472,6 +1503,7 @@ int fhe_radix_rerandomize(fhe_ctx* c, const fhe_radix* x, const uint8_t* seed, f
     if (!x || !out) return invalid("null argument to fhe_radix_rerandomize");
     uint8_t seed32[32];
     int rc = rerandomize_check(c, seed, seed32);
+    if (!rc && (rc = owned(c, x, "x"))) wipe32(seed32);
     if (rc) return rc;
     rc = guarded([&] {
         std::vector<const Block*> blocks;
@@ -1489,6 +1521,7 @@ int fhe_biguint_rerandomize(fhe_ctx* c, const fhe_biguint* x, const uint8_t* see
     if (!x || !out) return invalid("null argument to fhe_biguint_rerandomize");
     uint8_t seed32[32];
     int rc = rerandomize_check(c, seed, seed32);
+    if (!rc && (rc = owned(c, x, "x"))) wipe32(seed32);
     if (rc) return rc;
     rc = guarded([&] {
         std::vector<const Block*> blocks;
@@ -1548,6 +1581,7 @@ void value_digest(fhe_ctx* c, uint8_t kind, uint32_t bits, const std::vector<con
 }
 int radix_digest(fhe_ctx* c, const fhe_radix* x, uint8_t out[32]) {
     int rc = need_engine(c);
+    if (!rc) rc = owned(c, x, "x");
     if (rc) return rc;
     return guarded([&] {
         std::vector<const Block*> blocks;
@@ -1558,6 +1592,7 @@ int radix_digest(fhe_ctx* c, const fhe_radix* x, uint8_t out[32]) {
 }
 int biguint_digest(fhe_ctx* c, const fhe_biguint* x, uint8_t out[32]) {
     int rc = need_engine(c);
+    if (!rc) rc = owned(c, x, "x");
     if (rc) return rc;
     return guarded([&] {
         std::vector<const Block*> blocks;

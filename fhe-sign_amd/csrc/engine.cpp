@@ -69,7 +69,8 @@ std::shared_ptr<Slot> BlockPool::alloc() {
         auto s = std::make_shared<Slot>();
         s->p = reinterpret_cast<uint64_t*>(dry_next_);
         dry_next_ += kBigCt * 8;
-        return s;  // no pool: nothing to release
+        s->pool = shared_from_this();  // the owner (Engine::owns); release() keeps nothing of a placeholder
+        return s;
     }
     if (free_.empty()) {
         const size_t per = 1024;  // 16 MiB chunks
@@ -99,9 +100,30 @@ Engine::Engine(fhe_ctx* ctx, int host_mode) : ctx_(ctx), host_mode_(host_mode) {
     gstats_ = debug().graph;
 }
 
+bool Engine::owns(const Block& b) const {
+    if (b.lazy()) {
+        for (const Term& t : *b.lin)
+            if (t.b.slot && t.b.slot->pool.get() != pool_.get()) return false;
+        return true;
+    }
+    return !b.slot || b.slot->pool.get() == pool_.get();
+}
+
+void Engine::check_owner(const Block& b, const char* operand) const {
+    if (owns(b)) return;
+    throw EngineError(FHE_ERR_INVALID, operand ? std::string("operand ") + operand + " was made under another context"
+                                               : std::string("a ciphertext block was made under another context"));
+}
+
+void Engine::check_owner(const std::vector<const Block*>& blocks, const char* operand) const {
+    for (const Block* b : blocks) check_owner(*b, operand);
+}
+
 int32_t Engine::depth_of(const Block& b) const {
+    check_owner(b);
     int32_t d = 0;
     auto one = [&](const Block& x) {
+        // an owned slot's node indexes this engine's list (flush keeps it so); the bound states it
         if (x.slot && x.slot->node >= 0 && (size_t)x.slot->node < pending_.size())
             d = std::max(d, pending_[x.slot->node].depth);
     };
@@ -121,6 +143,7 @@ Block Engine::sim_block(uint32_t value, uint32_t degree) {
 
 int64_t Engine::sim_half2(const Block& b) const {
     if (b.trivial()) return trivial_half2(b);
+    check_owner(b);  // another engine's placeholder address would find this engine's shadow under it
     if (b.lazy()) {
         int64_t v = 2 * (int64_t)b.lin_cst;
         for (const Term& t : *b.lin) v += (int64_t)t.coef * sim_half2(t.b);
@@ -215,6 +238,8 @@ uint64_t reachable(const std::vector<Term>& terms, int64_t cst, bool* ok) {
     }
     return set;
 }
+// a reachable plaintext at or above the message space of mc values (mc <= 64; at 64 the mask is the whole space)
+bool beyond(uint64_t reach, uint32_t mc) { return mc < 64 && (reach >> mc) != 0; }
 }  // namespace
 
 Blocks Engine::run(std::vector<PbsItem>& items) {
@@ -223,6 +248,9 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
         std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
         ~Clock() { e->run_ns_ += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count(); }
     } clock{this};
+    // ownership first: a refusal leaves no item processed, no slot allocated and no statistic moved
+    for (const PbsItem& it : items)
+        for (const Term& t : it.terms) check_owner(t.b);
     ++run_calls_;
     const Params& p = ctx_->p;
     const uint32_t mc = p.msg_carry();
@@ -286,7 +314,7 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
         }
         bool ok;
         const uint64_t reach = reachable(live[i], cst, &ok);
-        engine_check(ok && (reach >> mc) == 0, "PBS input out of the message space (degree overflow)");
+        engine_check(ok && !beyond(reach, mc), "PBS input out of the message space (degree overflow)");
         labels[i] = noise;
         uint32_t lo = 0xffffffffu, hi = 0;
         bool identity = live[i].size() == 1 && live[i][0].coef == 1 && cst == 0 && live[i][0].b.noise <= 1 &&
@@ -344,7 +372,11 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
             terms.push_back({b.ptr(), coef});
             term_noise.push_back(b.noise);
             n.hold.push_back(b.slot);
-            if (b.slot->node >= 0) n.deps.push_back((int32_t)b.slot->node);
+            if (b.slot->node >= 0) {
+                // the slot is this engine's (checked above), so its node is an index into this engine's list
+                engine_check((size_t)b.slot->node < pending_.size(), "a pending producer outside the recorded graph");
+                n.deps.push_back((int32_t)b.slot->node);
+            }
         };
         for (const Term& t : live[i]) {
             if (!t.b.lazy()) {
@@ -483,6 +515,7 @@ void Engine::flush_tail(size_t k0) {
 // swept by a collective, and a rank-local read (a broadcast's root, one rank's decryption) that found
 // pending work would then run one collective on its own rank.
 void Engine::flush_for(const std::vector<const Block*>& blocks) {
+    check_owner(blocks);
     if (pending_.empty() || gstats_ || ctx_->fanout_world() > 1 || (ctx_->attached() && ctx_->nranks > 1))
         return flush();
     sweep_dead();
@@ -952,7 +985,10 @@ static uint32_t merged_label(const std::vector<Term>& terms) {
 }
 
 Block Engine::lincomb(const std::vector<Term>& terms, uint32_t cst) {
-    for (const Term& t : terms) engine_check(!t.b.lazy(), "lincomb of a lazy block");
+    for (const Term& t : terms) {
+        engine_check(!t.b.lazy(), "lincomb of a lazy block");
+        check_owner(t.b);
+    }
     flush();
     int64_t c = cst;
     std::vector<Term> live;
@@ -965,7 +1001,7 @@ Block Engine::lincomb(const std::vector<Term>& terms, uint32_t cst) {
     const uint32_t noise = merged_label(live);
     bool ok;
     const uint64_t reach = reachable(live, c, &ok);
-    engine_check(ok && (reach >> ctx_->p.msg_carry()) == 0, "linear combination out of range");
+    engine_check(ok && !beyond(reach, ctx_->p.msg_carry()), "linear combination out of range");
     uint32_t hi = 63 - __builtin_clzll(reach);
     if (live.empty()) return Block::make_trivial((uint32_t)c);
     Block b;

@@ -57,7 +57,7 @@ class BlockPool;
 
 struct Slot {
     uint64_t* p = nullptr;
-    std::shared_ptr<BlockPool> pool;
+    std::shared_ptr<BlockPool> pool;  // the maker's pool: kept alive by the slot, and the slot's owner (Engine::owns)
     int64_t node = -1;  // index of the pending bootstrap that writes this slot (Engine::flush), or -1
     ~Slot();
 };
@@ -94,7 +94,9 @@ public:
     explicit BlockPool(int device, bool dry = false) : device_(device), dry_(dry) {}
     ~BlockPool();
     std::shared_ptr<Slot> alloc();
-    void release(uint64_t* p) { free_.push_back(p); }
+    void release(uint64_t* p) {
+        if (!dry_) free_.push_back(p);  // placeholder addresses are never handed out twice
+    }
     size_t live() const { return total_ - free_.size(); }
 
 private:
@@ -161,6 +163,14 @@ public:
     int64_t sim_half2(const Block& b) const;
     // diagnostics: the dependency depth (levels) of a pending block's producer, 0 if none is pending
     int32_t depth_of(const Block& b) const;
+    // Ownership: a slot block (a lazy block: each of its terms) belongs to the engine whose pool made its slot,
+    // and only there do its address, its pending node index and (kSim) its plaintext shadow mean anything.
+    // Every block that enters an engine passes check_owner first -- one pointer comparison per slot -- and a
+    // foreign one is refused with FHE_ERR_INVALID before anything is recorded, staged, launched or read
+    // (`operand`: the entry point's name for it, when the C layer knows it).  Trivial blocks have no owner.
+    bool owns(const Block& b) const;
+    void check_owner(const Block& b, const char* operand = nullptr) const;
+    void check_owner(const std::vector<const Block*>& blocks, const char* operand = nullptr) const;
     ~Engine();
     fhe_ctx* ctx() const { return ctx_; }
     // Records one dependency level of items; returns one output block per item (possibly trivial).

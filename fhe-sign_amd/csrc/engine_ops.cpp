@@ -52,11 +52,12 @@ std::vector<uint64_t*> slot_ptrs(const Blocks& blocks) {
     return p;
 }
 
-// the slots of blocks that must be real ciphertexts (`what`: the refusal)
-std::vector<const uint64_t*> source_ptrs(const std::vector<const Block*>& blocks, const char* what) {
+// the slots of blocks that must be real ciphertexts of this engine (`what`: the refusal)
+std::vector<const uint64_t*> source_ptrs(const Engine& e, const std::vector<const Block*>& blocks, const char* what) {
     std::vector<const uint64_t*> p(blocks.size());
     for (size_t i = 0; i < blocks.size(); ++i) {
         engine_check(blocks[i]->slot != nullptr && !blocks[i]->lazy(), what);
+        e.check_owner(*blocks[i]);
         p[i] = blocks[i]->slot->p;
     }
     return p;
@@ -65,6 +66,7 @@ std::vector<const uint64_t*> source_ptrs(const std::vector<const Block*>& blocks
 // The blocks an operation reads, ready on the stream: a lazy block is combined into a slot of its own (lincomb
 // flushes; its semantic degree carried over) in `real`, then the pending producers of all of them are launched.
 std::vector<const Block*> realize(Engine& e, const std::vector<const Block*>& blocks, const std::string& op, Blocks& real) {
+    e.check_owner(blocks);  // all of them, before the first lazy one is combined (a flush and a launch)
     real.assign(blocks.size(), Block());
     std::vector<const Block*> in(blocks);
     for (size_t i = 0; i < blocks.size(); ++i) {
@@ -186,6 +188,7 @@ void Engine::compress(const std::vector<const Block*>& blocks, uint8_t* packed) 
     const size_t n = blocks.size();
     engine_check(n <= kCompressedMaxBlocks, "compressed list of more than 2^24 blocks");
     if (n == 0) return;
+    check_owner(blocks);
     const CompParams& cp = ctx_->cp;
     // trivial blocks become ciphertexts (0, b) in slots of their own: the kernels see no special case
     std::vector<uint64_t> cts;
@@ -535,6 +538,7 @@ void Engine::digest(const std::vector<const Block*>& blocks, uint8_t* out, std::
 // ------------------------------------------------------------------ downloads, the broadcasts' ends
 void Engine::download(const Block& b, uint64_t* ct) {
     engine_check(!b.trivial() && !b.lazy(), "download of a trivial or lazy block");
+    check_owner(b);
     flush();
     hip_check(hipMemcpyAsync(ct, b.slot->p, kBigCt * 8, hipMemcpyDeviceToHost, ctx_->stream), "download");
     wait_check(ctx_, "download");
@@ -543,6 +547,7 @@ void Engine::download(const Block& b, uint64_t* ct) {
 void Engine::download_many(const std::vector<const Block*>& blocks, uint64_t* cts, bool only_needed) {
     const size_t n = blocks.size();
     if (n == 0) return;
+    check_owner(blocks);  // before the flush: a refusal leaves what is pending pending
     if (only_needed)
         flush_for(blocks);
     else if (n == 1)
@@ -551,7 +556,7 @@ void Engine::download_many(const std::vector<const Block*>& blocks, uint64_t* ct
         flush();
     const size_t words = n * kBigCt + n;  // gathered ciphertexts, then the slot pointers
     Stage st(ctx_->stream, staging(words), words);
-    const std::vector<const uint64_t*> src = source_ptrs(blocks, "download of a trivial or lazy block");
+    const std::vector<const uint64_t*> src = source_ptrs(*this, blocks, "download of a trivial or lazy block");
     uint64_t* d_cts = st.reserve<uint64_t>(n * kBigCt);
     const uint64_t** d_src = st.put(src.data(), n, "download");
     hip_check(launch_gather_blocks(d_src, d_cts, (int)n, ctx_->stream), "download gather");
@@ -576,11 +581,12 @@ Blocks Engine::adopt_device(const uint64_t* d_cts, size_t n) {
 }
 
 void Engine::gather_device(const std::vector<const Block*>& blocks, uint64_t* d_out) {
+    check_owner(blocks);
     flush();
     const size_t n = blocks.size();
     if (n == 0) return;
     Stage st(ctx_->stream, staging(n), n);  // the slot pointers
-    const std::vector<const uint64_t*> src = source_ptrs(blocks, "gather of a trivial or lazy block");
+    const std::vector<const uint64_t*> src = source_ptrs(*this, blocks, "gather of a trivial or lazy block");
     const uint64_t** d_src = st.put(src.data(), n, "gather");
     hip_check(launch_gather_blocks(d_src, d_out, (int)n, ctx_->stream), "gather");
     hip_check(hipStreamSynchronize(ctx_->stream), "gather sync");

@@ -31,9 +31,20 @@ bool Params::from_c(const fhe_params& c, Params* out, const char** why) {
         *why = "blind-rotate kernel is compiled for pbs_base_log 23";
         return false;
     }
-    uint32_t mc = c.message_modulus * c.carry_modulus;
-    if (c.message_modulus < 2 || mc > 64 || (mc & (mc - 1)) || (kPolySize % mc)) {
-        *why = "message*carry modulus must be a power of two <= 64";
+    // each modulus on its own first: a product formed from unchecked factors can wrap to a legal value
+    // (0x40000001 * 4 = 4 in 32 bits), and a zero carry_modulus would reach the division below
+    auto pow2_to_64 = [](uint32_t m) { return m >= 1 && m <= 64 && (m & (m - 1)) == 0; };
+    if (!pow2_to_64(c.message_modulus) || c.message_modulus < 2) {
+        *why = "message_modulus must be a power of two, 2 .. 64";
+        return false;
+    }
+    if (!pow2_to_64(c.carry_modulus)) {
+        *why = "carry_modulus must be a power of two, 1 .. 64";
+        return false;
+    }
+    const uint64_t mc = (uint64_t)c.message_modulus * c.carry_modulus;
+    if (mc > 64 || (kPolySize % mc)) {
+        *why = "message_modulus * carry_modulus must be a power of two <= 64";
         return false;
     }
     if (c.lwe_noise_log2 > 62 || c.glwe_noise_log2 > 62) {

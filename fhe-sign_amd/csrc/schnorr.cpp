@@ -554,6 +554,8 @@ static int sign_one(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t
                     const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, bool reduced, uint8_t sig[64]) {
     if (const int sim = fhe::refuse_simulated(ctx, "the signer")) return sim;
     if (!sig) return FHE_ERR_INVALID;
+    // before e and k are encrypted and uploaded: a refusal allocates nothing
+    if (const int own = fhe::biguint_owned(ctx, privkey_fhe, "privkey_fhe")) return own;
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     SignJob j;
@@ -595,6 +597,9 @@ int fhe_schnorr_eval_s(fhe_ctx* ctx, const fhe_biguint* e_fhe, const fhe_biguint
         set_error("invalid arguments to fhe_schnorr_eval_s (mode: FHE_BIGUINT_COMPAT or FHE_BIGUINT_FAST)");
         return FHE_ERR_INVALID;
     }
+    if (const int own = fhe::biguint_owned(ctx, e_fhe, "e_fhe")) return own;
+    if (const int own = fhe::biguint_owned(ctx, k_fhe, "k_fhe")) return own;
+    if (const int own = fhe::biguint_owned(ctx, privkey_fhe, "privkey_fhe")) return own;
     fhe_columns* cols = nullptr;
     int rc = fhe_biguint_mul_add_columns(ctx, e_fhe, privkey_fhe, k_fhe, mode, &cols);
     if (!rc) rc = fhe_columns_rem_pseudo_mersenne(ctx, cols, 256, kNC, 3, s);
@@ -609,6 +614,7 @@ int fhe_schnorr_eval_s_public(fhe_ctx* ctx, const uint8_t e[32], const uint8_t k
         set_error("null argument to fhe_schnorr_eval_s_public");
         return FHE_ERR_INVALID;
     }
+    if (const int own = fhe::biguint_owned(ctx, privkey_fhe, "privkey_fhe")) return own;
     return eval_s_public(ctx, U256::from_be(e), U256::from_be(k), privkey_fhe, s);
 }
 
@@ -623,6 +629,7 @@ static int sign_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, siz
         set_error("null argument to fhe_schnorr_sign_fhe_with_k0_rerand");
         return FHE_ERR_INVALID;
     }
+    if (const int own = fhe::biguint_owned(ctx, privkey_fhe, "privkey_fhe")) return own;
     if (!ctx->has_pk) {
         set_error("no public key installed (fhe_set_public_key)");
         return FHE_ERR_NO_KEY;
@@ -670,6 +677,8 @@ static int sign_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint
                       bool reduced, uint8_t* sigs) {
     if (const int sim = fhe::refuse_simulated(ctx, "the signer")) return sim;
     if (count && (!msgs || !lens || !k0s || !privkeys || !privkeys_fhe || !sigs)) return FHE_ERR_INVALID;
+    for (size_t i = 0; i < count; ++i)  // every key first: a refusal uploads nothing
+        if (const int own = fhe::biguint_owned(ctx, privkeys_fhe[i], "privkeys_fhe")) return own;
     std::vector<SignJob> jobs(count);
     for (SignJob& j : jobs) j.reduced = reduced;
     for (size_t i = 0; i < count; ++i) {  // uploads first: the engine graph is not started yet

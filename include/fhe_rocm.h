@@ -309,7 +309,19 @@ int fhe_ctx_fanout_info(const fhe_ctx* ctx, int* rank, int* nranks, uint64_t* fa
 /* ------------------------------------------------------------------- radix integers */
 /* FheUint<num_bits> (num_bits even, <= FHE_RADIX_MAX_BITS): num_bits/2 radix blocks, device-resident.
  * Replaces tfhe's FheUint8/32/64 as used at src/biguint.rs:26,135-143,221-248 and
- * src/perf_test.rs:19-54.  Arithmetic wraps modulo 2^num_bits (tfhe semantics). */
+ * src/perf_test.rs:19-54.  Arithmetic wraps modulo 2^num_bits (tfhe semantics).
+ *
+ * Ownership.  An fhe_radix, fhe_biguint or fhe_columns handle is a value of the context that made it (encrypt,
+ * expand, deserialize, random, a broadcast's copy, or an op on its values).  Every entry point that takes a context
+ * and a handle refuses a handle made under another context -- simulated or device, live or destroyed -- with
+ * FHE_ERR_INVALID and a message that says "another context" (with the operand's name where the entry point has
+ * one), before anything is recorded, staged, launched or read: both contexts stay as they were.  Values made by
+ * fhe_radix_trivial (and the trivial blocks of any value) have no owner and are accepted everywhere.  The entry
+ * points without a context (fhe_radix_clone, fhe_radix_cast with ctx = NULL, *_num_bits, fhe_biguint_len / _digit /
+ * _to_radix / _from_digits, *_destroy) look at no owner; what they return shares its source's blocks, and its owner.
+ * A handle may outlive its context (it keeps its blocks' storage alive) and is destroyed like any other.
+ * A value stays its context's across fhe_set_server_key on the SAME context: whether it still means anything
+ * under the new key is the caller's business, as under tfhe-rs' set_server_key. */
 #define FHE_RADIX_MAX_BITS 4096
 /* FheUint::try_encrypt (src/biguint.rs:26, src/perf_test.rs:19-21); words little-endian */
 int fhe_radix_encrypt(fhe_ctx* ctx, fhe_client_key* ck, const uint64_t* words, uint32_t num_bits,

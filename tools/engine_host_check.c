@@ -14,7 +14,8 @@
 //         tools/engine_host_check.c -Lfhe-sign_amd/lib_asan -lfhe_rocm -Wl,-rpath,$PWD/fhe-sign_amd/lib_asan
 //         -Wl,-rpath,$(dirname $(clang -print-file-name=libclang_rt.asan-x86_64.so)) -o engine_host_check
 // (clang = the ROCm toolchain's, as for tools/oprf_host_check.c).  A refused case prints its status and message,
-// which are compared like any other line; the exit status is 1 only if a case that must succeed did not.
+// which are compared like any other line; the exit status is 1 only if a case that must succeed did not, or an
+// ownership case (the "owner" lines, last) that must be refused was accepted.
 #include <inttypes.h>
 #include <stdio.h>
 #include <string.h>
@@ -369,6 +370,108 @@ static void sim_context(void) {
     fhe_ctx_destroy(c);
 }
 
+// Ownership (include/fhe_rocm.h, the radix section): a handle is a value of the context that made it.  Two or three
+// simulated contexts live at once; every line here is a refusal that must happen (a library without the check
+// prints the value it computed instead, or ends at the last case).  Then the moduli whose 32-bit product wraps to a
+// legal message space.  After sim_context and without the generator: every earlier line stays what it was.  The
+// pending-foreign case is the last of the program: a library without the check follows a node index of A into B's
+// empty list there.
+static void must_refuse(const char* name, int rc, uint64_t value) {
+    if (rc == FHE_OK) {
+        printf("owner %s: ACCEPTED value=%" PRIx64 "\n", name, value);
+        g_failed = 1;
+    } else {
+        printf("owner %s: rc=%d (%s)\n", name, rc, fhe_last_error());
+    }
+    fflush(stdout);
+}
+static fhe_radix* sim_enc(fhe_ctx* c, uint64_t v, uint32_t bits) {
+    uint64_t w[4] = {v, 0, 0, 0};
+    fhe_radix* x = NULL;
+    status("owner encrypt", fhe_radix_encrypt(c, NULL, w, bits, &x), 1);
+    return x;
+}
+static void ownership(void) {
+    fhe_ctx *A = NULL, *B = NULL, *C3 = NULL;
+    if (!status("owner create", fhe_host_sim_ctx_create(&A), 1) || !status("owner create", fhe_host_sim_ctx_create(&B), 1)) return;
+    uint64_t w[4] = {0};
+    fhe_radix *a1 = sim_enc(A, 0x1234, 16), *a2 = sim_enc(A, 0x0101, 16), *b1 = sim_enc(B, 0xBEEF, 16), *b2 = sim_enc(B, 0x0F0F, 16);
+    fhe_radix *r = NULL, *t = NULL, *p = NULL, *q = NULL;
+    // the wrong value of a library without the check: B's shadow under A's placeholder address
+    must_refuse("a1.decrypt under B", fhe_radix_decrypt(B, NULL, a1, w, 1), w[0]);
+    int rc = fhe_radix_add(B, a1, a2, &r);
+    if (rc == FHE_OK) fhe_radix_decrypt(B, NULL, r, w, 1);
+    must_refuse("a1 + a2 under B", rc, w[0]);
+    fhe_radix_destroy(r), r = NULL;
+    must_refuse("b1 + a2 under B", fhe_radix_add(B, b1, a2, &r), 0);
+    fhe_radix_destroy(r), r = NULL;
+    // trivial values have no owner
+    const uint64_t tw[1] = {0x0F0F};
+    status("owner trivial", fhe_radix_trivial(A, tw, 16, &t), 1);
+    if (status("owner b1 + trivial of A", fhe_radix_add(B, b1, t, &r), 1) && status("owner decrypt", fhe_radix_decrypt(B, NULL, r, w, 1), 1))
+        printf("owner b1 + trivial of A = %04" PRIx64 "\n", w[0]);
+    fhe_radix_destroy(r), r = NULL;
+    // both contexts as they were: the right values under the makers
+    if (status("owner a1 + a2 under A", fhe_radix_add(A, a1, a2, &r), 1)) printf("owner a1 + a2 under A = %04" PRIx64 "\n", sim_value(A, r));
+    fhe_radix_destroy(r), r = NULL;
+    if (status("owner b1 + b2 under B", fhe_radix_add(B, b1, b2, &r), 1)) printf("owner b1 + b2 under B = %04" PRIx64 "\n", sim_value(B, r));
+    fhe_radix_destroy(r), r = NULL;
+    // lifetimes: a context goes while its handles live; they are refused under a live context, destroyed without
+    // an error, and a context made afterwards computes
+    {
+        fhe_ctx* D = NULL;
+        status("owner create", fhe_host_sim_ctx_create(&D), 1);
+        fhe_radix *d1 = sim_enc(D, 0x4321, 16), *dp = NULL;
+        status("owner d1 * d1 pending", fhe_radix_mul(D, d1, d1, &dp), 1);
+        fhe_ctx_destroy(D);
+        must_refuse("handle of a destroyed context, decrypt under B", fhe_radix_decrypt(B, NULL, d1, w, 1), w[0]);
+        must_refuse("pending handle of a destroyed context, b1 + it under B", fhe_radix_add(B, b1, dp, &r), 0);
+        fhe_radix_destroy(r), r = NULL;
+        fhe_radix_destroy(d1), fhe_radix_destroy(dp);
+        status("owner create", fhe_host_sim_ctx_create(&C3), 1);
+        fhe_radix* c1 = sim_enc(C3, 0x4321, 16);
+        if (status("owner c1 * c1 under C", fhe_radix_mul(C3, c1, c1, &r), 1)) printf("owner c1 * c1 under C = %04" PRIx64 "\n", sim_value(C3, r));
+        must_refuse("c1.decrypt under B", fhe_radix_decrypt(B, NULL, c1, w, 1), w[0]);
+        fhe_radix_destroy(r), r = NULL;
+        fhe_radix_destroy(c1);
+        fhe_ctx_destroy(C3);
+    }
+    // moduli: each refused on its own, the product formed in 64 bits (a zero carry modulus last: a division by it)
+    static const uint32_t moduli[8][2] = {{0x40000001u, 4}, {4, 0x40000001u}, {0x80000000u, 2}, {1, 16}, {3, 4}, {128, 1}, {0, 4}, {2, 0}};
+    for (int i = 0; i < 8; ++i) {
+        fhe_params prm;
+        fhe_client_key* ck = NULL;
+        fhe_server_key* sk = NULL;
+        status("owner params", fhe_params_default(&prm), 1);
+        prm.message_modulus = moduli[i][0], prm.carry_modulus = moduli[i][1];
+        char name[64];
+        snprintf(name, sizeof name, "generate_keys moduli %#x x %#x", moduli[i][0], moduli[i][1]);
+        must_refuse(name, fhe_generate_keys(&prm, 7, &ck, &sk), 0);
+        fhe_client_key_destroy(ck), fhe_server_key_destroy(sk);
+    }
+    // B holds forty 256-bit values and nothing pending; A leaves p = (a1 * a2) * a2 + a1 pending; p + b1 under B
+    fhe_radix* held[40];
+    for (int i = 0; i < 40; ++i) held[i] = sim_enc(B, (uint64_t)i, 256);
+    status("owner flush B", fhe_radix_decrypt(B, NULL, held[39], w, 4), 1);
+    status("owner a1 * a2", fhe_radix_mul(A, a1, a2, &q), 1);
+    status("owner (a1 * a2) * a2", fhe_radix_mul(A, q, a2, &r), 1);
+    status("owner (a1 * a2) * a2 + a1", fhe_radix_add(A, r, a1, &p), 1);
+    fhe_radix_destroy(q), fhe_radix_destroy(r), r = NULL;
+    printf("owner pending foreign value: p + b1 under B follows\n");
+    fflush(stdout);
+    rc = fhe_radix_add(B, p, b1, &r);
+    if (rc == FHE_OK) fhe_radix_decrypt(B, NULL, r, w, 1);
+    must_refuse("p + b1 under B, p pending in A", rc, w[0]);
+    fhe_radix_destroy(r), r = NULL;
+    printf("owner p under A = %04" PRIx64 "\n", sim_value(A, p));
+    if (status("owner b1 + b2 under B", fhe_radix_add(B, b1, b2, &r), 1)) printf("owner b1 + b2 under B afterwards = %04" PRIx64 "\n", sim_value(B, r));
+    fhe_radix_destroy(r);
+    for (int i = 0; i < 40; ++i) fhe_radix_destroy(held[i]);
+    fhe_radix_destroy(a1), fhe_radix_destroy(a2), fhe_radix_destroy(b1), fhe_radix_destroy(b2), fhe_radix_destroy(t), fhe_radix_destroy(p);
+    fhe_ctx_destroy(A);
+    fhe_ctx_destroy(B);
+}
+
 int main(void) {
     radix_stats();
     sim_radix();
@@ -379,6 +482,7 @@ int main(void) {
     mul_add_rem();
     schedule();
     sim_context();
+    ownership();
     printf(g_failed ? "engine host modes: a required case failed\n" : "engine host modes: every required case ran\n");
     return g_failed;
 }
