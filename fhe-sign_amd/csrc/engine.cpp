@@ -60,10 +60,6 @@ BlockPool::~BlockPool() {
     (void)hipSetDevice(device_);            // the chunks free themselves
 }
 
-// pool growth (FHE_TRACE_LEVELS prints it with the host time of run())
-static double g_pool_grow_ns = 0.0;
-static size_t g_pool_grows = 0;
-
 std::shared_ptr<Slot> BlockPool::alloc() {
     if (dry_) {
         auto s = std::make_shared<Slot>();
@@ -77,8 +73,8 @@ std::shared_ptr<Slot> BlockPool::alloc() {
         DeviceBuf<uint64_t> chunk;
         const auto t0 = std::chrono::steady_clock::now();
         hip_check(chunk.grow(per * kBigCt), "block pool allocation");
-        g_pool_grow_ns += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count();
-        ++g_pool_grows;
+        grow_ns_ += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count();
+        ++grows_;
         uint64_t* const c = chunk;
         chunks_.push_back(std::move(chunk));
         for (size_t i = 0; i < per; ++i) free_.push_back(c + (per - 1 - i) * kBigCt);
@@ -754,12 +750,13 @@ void Engine::flush() {
     if (pending_.empty()) return;
     const auto f0 = std::chrono::steady_clock::now();
     if (trace_) {
+        size_t grows = 0;
+        double grow_ns = 0.0;
+        pool_->take_growth(&grows, &grow_ns);
         fprintf(stderr, "[host] %zu run() calls, %.3f ms inside run() since the last flush (pool grown %zu x, %.3f ms)\n",
-                run_calls_, run_ns_ * 1e-6, g_pool_grows, g_pool_grow_ns * 1e-6);
+                run_calls_, run_ns_ * 1e-6, grows, grow_ns * 1e-6);
         run_ns_ = 0.0;
         run_calls_ = 0;
-        g_pool_grows = 0;
-        g_pool_grow_ns = 0.0;
     }
     sweep_next_ = false;
     sweep_dead();

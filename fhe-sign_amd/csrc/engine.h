@@ -98,6 +98,12 @@ public:
         if (!dry_) free_.push_back(p);  // placeholder addresses are never handed out twice
     }
     size_t live() const { return total_ - free_.size(); }
+    // growth since the last call (the level trace prints it with the host time of run()); per pool:
+    // contexts on other threads grow their own
+    void take_growth(size_t* grows, double* ns) {
+        *grows = grows_, *ns = grow_ns_;
+        grows_ = 0, grow_ns_ = 0.0;
+    }
 
 private:
     int device_;
@@ -106,6 +112,8 @@ private:
     std::vector<DeviceBuf<uint64_t>> chunks_;
     std::vector<uint64_t*> free_;
     size_t total_ = 0;
+    size_t grows_ = 0;
+    double grow_ns_ = 0.0;
 };
 
 struct Term {

@@ -57,19 +57,19 @@ PbsItem item2(const Block& hi, const Block& lo, std::vector<uint32_t> table) {
     return it;
 }
 const std::vector<uint32_t>& LUT_MOD4() {
-    static auto t = lut1([](uint32_t x) { return x & 3; });
+    static const auto t = lut1([](uint32_t x) { return x & 3; });
     return t;
 }
 const std::vector<uint32_t>& LUT_DIV4() {
-    static auto t = lut1([](uint32_t x) { return x >> 2; });
+    static const auto t = lut1([](uint32_t x) { return x >> 2; });
     return t;
 }
 const std::vector<uint32_t>& LUT_STATE() {  // 2 generate, 1 propagate, 0 kill
-    static auto t = lut1([](uint32_t v) { return v >= 4 ? 2u : (v == 3 ? 1u : 0u); });
+    static const auto t = lut1([](uint32_t v) { return v >= 4 ? 2u : (v == 3 ? 1u : 0u); });
     return t;
 }
 const std::vector<uint32_t>& LUT_GEN() {
-    static auto t = lut1([](uint32_t v) { return v >= 4 ? 1u : 0u; });
+    static const auto t = lut1([](uint32_t v) { return v >= 4 ? 1u : 0u; });
     return t;
 }
 }  // namespace
@@ -1697,9 +1697,11 @@ static Radix barrel4(Engine& e, const Radix& a, const Radix& amount, bool right)
     Blocks o = e.run(items);
     const Blocks sh1(o.begin(), o.begin() + n);
     const Block topbit = odd ? o[n] : Block::make_trivial(0);
-    static std::vector<std::vector<uint32_t>> sel4;
-    if (sel4.empty())
-        for (uint32_t c = 0; c < 4; ++c) sel4.push_back(lut1([c](uint32_t v) { return (v >> 2) == c ? v & 3 : 0u; }));
+    static const auto sel4 = [] {
+        std::vector<std::vector<uint32_t>> t;
+        for (uint32_t c = 0; c < 4; ++c) t.push_back(lut1([c](uint32_t v) { return (v >> 2) == c ? v & 3 : 0u; }));
+        return t;
+    }();
     static const auto LUT_IF = lut2([](uint32_t c, uint32_t v) { return c ? v : 0u; });
     static const auto LUT_IFNOT = lut2([](uint32_t c, uint32_t v) { return c ? 0u : v; });
     auto sel = [](const Block& c, const Block& v, const std::vector<uint32_t>& t) {

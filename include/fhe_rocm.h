@@ -9,7 +9,24 @@
  * (the reference panics via unwrap at src/biguint.rs:207; here that is FHE_ERR_*).
  *
  * Threading: like tfhe-rs's thread-local `set_server_key` (src/schnorr.rs:443), a server key is
- * installed per context and a context is used by one host thread at a time.
+ * installed per context and a context is used by one host thread at a time.  There is no lock
+ * inside a context.  What that means, piece by piece:
+ *  - Contexts are independent across threads: any number of threads may each drive a context of
+ *    their own at once, device or simulated, on one GPU or several.  A context may move between
+ *    threads as long as its uses do not overlap; every entry point selects the context's device
+ *    itself, whatever the calling thread's current device is.
+ *  - A context's handles (fhe_radix, fhe_biguint, column forms, lists made from its values) count
+ *    as the context, their destroy calls included: destroying a handle from another thread while
+ *    its context is in use is a misuse.
+ *  - A client key carries a mutable encryption stream (fhe_client_key_seed_encryption) and belongs
+ *    to one thread at a time.
+ *  - Server, public, compression and re-keying key objects are read-only once made and may be
+ *    installed into several contexts from several threads.
+ *  - fhe_last_error() is per thread: a thread reads the message of its own last refusal.
+ *  - fhe_host_set_tuning is process-wide (test hook): set before any op runs on any thread.
+ * tools/threads_host_check.c drives four simulated contexts on four threads (under the host
+ * ThreadSanitizer build: tools/tsan_host.sh); tests/test_threads.py and tests/test_threads_gpu.py
+ * pin the same on the Python layer and on device contexts.
  *
  * Ciphertext layout (one radix block = one LWE ciphertext under the big key):
  *   uint64_t[2049] = mask[2048] then body.  A radix integer of B bits has B/2 blocks, LSB first.
