@@ -522,6 +522,120 @@ int fhe_ctx_noise_audit(fhe_ctx* c, uint64_t* max_label, uint64_t* max_merged, u
     return FHE_OK;
 }
 
+// ----------------------------------------------------------------- launch trace and its read-only hooks
+int fhe_ctx_trace(fhe_ctx* c, int enable) {
+    if (!c || !c->engine) {
+        set_error("fhe_ctx_trace: a context without an engine (no key installed)");
+        return FHE_ERR_INVALID;
+    }
+    c->engine->trace_enable(enable != 0);
+    return FHE_OK;
+}
+
+int fhe_ctx_trace_read(fhe_ctx* c, uint64_t* buf, size_t cap, size_t* n, int reset) {
+    if (!c || !n || (cap && !buf)) return FHE_ERR_INVALID;
+    if (!c->engine) {
+        *n = 0;
+        return FHE_OK;
+    }
+    Engine& e = *c->engine;
+    if (e.trace_overflowed()) {
+        *n = 0;
+        if (reset) e.trace_reset();
+        set_error("fhe_ctx_trace_read: the launch trace overflowed its " + std::to_string(Engine::kTraceCap) +
+                  " words and is incomplete");
+        return FHE_ERR_INVALID;
+    }
+    const std::vector<uint64_t>& t = e.trace_words();
+    *n = t.size();
+    if (cap && !t.empty()) std::memcpy(buf, t.data(), std::min(cap, t.size()) * 8);
+    if (reset) e.trace_reset();
+    return FHE_OK;
+}
+
+// addrs[k] = block k's slot address (a simulated context: its placeholder), 0 for a trivial block, whose value
+// goes to values[k] (optional; 0 for the others).  A lazy block (an unevaluated combination) has no address.
+static int block_addrs(const fhe_ctx* c, const std::vector<const Block*>& blocks, uint64_t* addrs, uint32_t* values,
+                       size_t cap, size_t* n) {
+    *n = blocks.size();
+    if (cap < blocks.size()) {
+        if (cap == 0) return FHE_OK;  // a size query
+        set_error("block address buffer too small");
+        return FHE_ERR_INVALID;
+    }
+    if (!addrs) return FHE_ERR_INVALID;
+    for (size_t k = 0; k < blocks.size(); ++k) {
+        const Block& b = *blocks[k];
+        if (b.lazy() || (b.trivial() && b.half_neg)) {
+            set_error("block_addrs: block " + std::to_string(k) + " is an unevaluated combination, not a slot");
+            return FHE_ERR_INVALID;
+        }
+        addrs[k] = (uint64_t)reinterpret_cast<uintptr_t>(b.ptr());
+        if (values) values[k] = b.trivial() ? b.value : 0;
+    }
+    (void)c;
+    return FHE_OK;
+}
+
+int fhe_radix_block_addrs(fhe_ctx* c, const fhe_radix* x, uint64_t* addrs, uint32_t* values, size_t cap, size_t* n) {
+    if (!c || !x || !n) return FHE_ERR_INVALID;
+    if (const int rc = owned(c, x, "x")) return rc;
+    std::vector<const Block*> blocks;
+    for (const Block& b : x->r.blocks) blocks.push_back(&b);
+    return block_addrs(c, blocks, addrs, values, cap, n);
+}
+
+int fhe_biguint_block_addrs(fhe_ctx* c, const fhe_biguint* x, uint64_t* addrs, uint32_t* values, size_t cap, size_t* n) {
+    if (!c || !x || !n) return FHE_ERR_INVALID;
+    if (const int rc = owned(c, x, "x")) return rc;
+    std::vector<const Block*> blocks;
+    for (const Radix& d : x->v.digits)
+        for (const Block& b : d.blocks) blocks.push_back(&b);
+    return block_addrs(c, blocks, addrs, values, cap, n);
+}
+
+int fhe_ctx_lut_table(fhe_ctx* c, uint32_t id, int* kind, int32_t entries[16]) {
+    if (!c || !kind || !entries) return FHE_ERR_INVALID;
+    const uint32_t mods = c->p.msg_carry();
+    for (const auto& kv : c->lut_ids) {
+        if (kv.second != id) continue;
+        const std::vector<uint32_t>& key = kv.first;
+        std::memset(entries, 0, 16 * sizeof(int32_t));
+        if (key.size() == mods && mods <= 16) {
+            *kind = FHE_LUT_INTEGER;
+            for (uint32_t i = 0; i < mods; ++i) entries[i] = (int32_t)key[i];
+        } else if (key.size() == (size_t)mods + 1 && key[0] == 0xFFFFFFFFu && mods <= 16) {
+            *kind = FHE_LUT_HALF_STEP;
+            for (uint32_t i = 0; i < mods; ++i) entries[i] = (int32_t)key[1 + i];
+        } else if (key.size() == 3 && key[0] == 0xFFFFFFFEu) {
+            *kind = FHE_LUT_OPRF;
+            entries[0] = (int32_t)key[2];
+        } else {
+            set_error("fhe_ctx_lut_table: a table of no known kind");
+            return FHE_ERR_INVALID;
+        }
+        return FHE_OK;
+    }
+    set_error("fhe_ctx_lut_table: no table with id " + std::to_string(id));
+    return FHE_ERR_INVALID;
+}
+
+int fhe_ctx_export_luts(fhe_ctx* c, uint32_t first, uint32_t count, uint64_t* polys) {
+    if (const int sim = refuse_simulated(c, "fhe_ctx_export_luts")) return sim;
+    if (!c || (count && !polys)) return FHE_ERR_INVALID;
+    if (count == 0) return FHE_OK;
+    // the device table as it stands: what sync_luts last sent, not the host copy
+    if (!c->d_luts || !c->d_luts.fits(((size_t)first + count) * kPolySize)) {
+        set_error("fhe_ctx_export_luts: tables beyond the device table");
+        return FHE_ERR_INVALID;
+    }
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    FHE_HIP_CHECK(hipMemcpyAsync(polys, c->d_luts + (size_t)first * kPolySize, (size_t)count * kPolySize * 8,
+                                 hipMemcpyDeviceToHost, c->stream));
+    FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return FHE_OK;
+}
+
 // ----------------------------------------------------------------- operand distribution (comm.cpp)
 int fhe_ctx_broadcast_radix(fhe_ctx* c, fhe_radix** x, int root) {
     const bool sends = c && (!c->attached() || c->rank == root);

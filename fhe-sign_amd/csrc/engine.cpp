@@ -156,7 +156,41 @@ Block Engine::dry_block(uint32_t degree) {
     b.slot = pool_->alloc();
     b.degree = degree;
     b.noise = 1;
+    if (ltrace_on_) trace_write(kWriteUpload, &b.slot->p, 1);  // a placeholder's "upload"
     return b;
+}
+
+// ============================================================================ launch trace (engine.h)
+bool Engine::trace_room(size_t words) {
+    if (ltrace_overflow_ || ltrace_.size() + words > kTraceCap) {
+        ltrace_overflow_ = true;
+        return false;
+    }
+    return true;
+}
+
+void Engine::trace_write(uint64_t kind, uint64_t* const* dst, size_t n) {
+    if (n == 0 || !trace_room(3 + n)) return;
+    ltrace_.push_back(kTraceWrite);
+    ltrace_.push_back(kind);
+    ltrace_.push_back(n);
+    for (size_t i = 0; i < n; ++i) ltrace_.push_back((uint64_t)reinterpret_cast<uintptr_t>(dst[i]));
+}
+
+// one node or lincomb record from a descriptor as it is launched; `wide`: the host copy of its TermExt table
+void Engine::trace_op(uint64_t tag, const PbsDesc& d, const uint64_t* dst, const TermExt* wide) {
+    const bool node = tag == kTraceNode;
+    engine_check(wide || d.nterms <= (uint32_t)kMaxTerms, "trace: a wide combination without its term table");
+    if (!trace_room((node ? 5 : 4) + 2 * (size_t)d.nterms)) return;
+    ltrace_.push_back(tag);
+    ltrace_.push_back((uint64_t)reinterpret_cast<uintptr_t>(dst));
+    if (node) ltrace_.push_back(d.lut);
+    ltrace_.push_back(d.cst);
+    ltrace_.push_back(d.nterms);
+    for (uint32_t u = 0; u < d.nterms; ++u) {
+        ltrace_.push_back((uint64_t)reinterpret_cast<uintptr_t>(wide ? wide[u].src : d.src[u]));
+        ltrace_.push_back((uint64_t)(wide ? wide[u].coef : (int64_t)d.coef[u]));
+    }
 }
 
 Engine::~Engine() {
@@ -785,6 +819,14 @@ void Engine::flush() {
                 for (int32_t dp : pn.deps) mix((uint64_t)(int64_t)dp);
             }
         }
+        if (ltrace_on_)  // nothing is staged here: the pending nodes, in scheduled order
+            for (size_t li = 0; li < lv.size(); ++li) {
+                if (trace_room(4)) ltrace_.insert(ltrace_.end(), {kTraceLevel, levels + li + 1, (uint64_t)lv[li].size(), 0});
+                for (int32_t k : lv[li]) {
+                    const Pending& pn = pending_[k];
+                    trace_op(kTraceNode, pn.d, pn.d.dst, pn.ext.empty() ? nullptr : pn.ext.data());
+                }
+            }
         for (auto& l : lv) {
             pbs_count += l.size();
             levels += 1;
@@ -850,6 +892,29 @@ void Engine::flush() {
     }
     hip_check(hipMemcpyAsync(dev, h, ndesc * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream), "desc copy");
     hip_check(hipEventRecord(desc_ev_[desc_turn_], ctx_->stream), "desc event");
+    if (ltrace_on_) {
+        // read back from the staged host buffer, i.e. what the copy above sends: a node's terms through its staged
+        // src[0] into the staged term tables, a split level's destinations from its staged scatter table
+        const size_t ext_cap = (ndesc - ext_at) * sizeof(PbsDesc) / sizeof(TermExt);
+        for (size_t li = 0; li < lv.size(); ++li) {
+            const auto [G, split, chunk, units] = shape[li];
+            if (trace_room(4)) ltrace_.insert(ltrace_.end(), {kTraceLevel, levels + li + 1, (uint64_t)G, (uint64_t)split});
+            uint64_t* const* scat = reinterpret_cast<uint64_t* const*>(h + at[li] + G);
+            for (size_t g = 0; g < G; ++g) {
+                const PbsDesc& d = h[at[li] + g];
+                const TermExt* wide = nullptr;
+                if (d.nterms > (uint32_t)kMaxTerms) {
+                    const uintptr_t a = reinterpret_cast<uintptr_t>(d.src[0]), a0 = reinterpret_cast<uintptr_t>(d_ext);
+                    const size_t off = (size_t)(a - a0) / sizeof(TermExt);
+                    engine_check(a >= a0 && (a - a0) % sizeof(TermExt) == 0 && d.nterms <= (uint32_t)kMaxWideTerms &&
+                                     off + d.nterms <= ext_cap,
+                                 "trace: a staged term table outside the staged copy");
+                    wide = h_ext + off;
+                }
+                trace_op(kTraceNode, d, split ? scat[g] : d.dst, wide);
+            }
+        }
+    }
     if (trace_)
         fprintf(stderr, "[flush] %zu nodes (%llu dropped so far), %zu levels, scheduled in %.3f ms\n", N,
                 (unsigned long long)dead_nodes, lv.size(),
@@ -1001,6 +1066,7 @@ Block Engine::lincomb(const std::vector<Term>& terms, uint32_t cst) {
     engine_check(ok && !beyond(reach, ctx_->p.msg_carry()), "linear combination out of range");
     uint32_t hi = 63 - __builtin_clzll(reach);
     if (live.empty()) return Block::make_trivial((uint32_t)c);
+    engine_check(live.size() <= (size_t)kMaxTerms, "linear combination of more terms than a descriptor holds");
     Block b;
     b.degree = hi;
     b.noise = noise;
@@ -1017,6 +1083,7 @@ Block Engine::lincomb(const std::vector<Term>& terms, uint32_t cst) {
     d.cst = (uint64_t)c * ctx_->p.delta();
     d.dst = b.slot->p;
     h[0] = d;
+    if (ltrace_on_) trace_op(kTraceLincomb, h[0], h[0].dst, nullptr);
     hip_check(hipMemcpyAsync(dev, h, sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream), "desc copy");
     hip_check(hipEventRecord(desc_ev_[desc_turn_], ctx_->stream), "desc event");
     hip_check(launch_lincomb(dev, 1, ctx_->stream), "lincomb");

@@ -328,6 +328,26 @@ public:
     // gathered slices by its own node order)
     uint64_t fingerprint = 1469598103934665603ull;
     static constexpr size_t kLevelLogCap = 1u << 20;
+    // Launch trace (test hook, fhe_ctx_trace / fhe_ctx_trace_read; off by default: one branch per flush and per
+    // eager op): what is enqueued on the stream, in that order, as a flat stream of u64 records
+    //   kTraceLevel   level number, bootstraps, split flag -- followed by one node record per bootstrap, in launch order
+    //   kTraceNode    dst, LUT id, cst, nterms, then nterms x (src, coefficient as int64)
+    //   kTraceLincomb dst, cst, nterms, then nterms x (src, coefficient)
+    //   kTraceWrite   kind (kWrite*), n, then n destination addresses
+    // A device engine reads a node's fields back from the staged host copy of what goes to the device (the level's
+    // descriptors, a wide combination's staged TermExt table through the staged src[0], a split level's scatter
+    // table); the dry and simulated modes, which stage nothing, record from the pending nodes in scheduled order.
+    // At most kTraceCap words are kept; a record that would pass them sets the overflow flag instead.
+    enum : uint64_t { kTraceLevel = 1, kTraceNode = 2, kTraceLincomb = 3, kTraceWrite = 4 };
+    enum : uint64_t { kWriteUpload = 0, kWriteDeferred = 1, kWriteOpaque = 2 };
+    static constexpr size_t kTraceCap = (size_t)1 << 23;  // 64 MiB
+    void trace_enable(bool on) { ltrace_on_ = on; }
+    bool trace_overflowed() const { return ltrace_overflow_; }
+    const std::vector<uint64_t>& trace_words() const { return ltrace_; }
+    void trace_reset() {
+        ltrace_.clear();
+        ltrace_overflow_ = false;
+    }
 
 private:
     fhe_ctx* ctx_;
@@ -336,9 +356,16 @@ private:
     std::shared_ptr<BlockPool> pool_;
     DeviceBuf<uint64_t> d_up_;  // upload / download staging, carved by engine_ops.cpp's cursor
     uint64_t* staging(size_t words);
-    // n blocks in fresh slots (noise 1), one degree for all or one per block
-    Blocks fresh_blocks(size_t n, uint32_t degree);
-    Blocks fresh_blocks(const std::vector<uint32_t>& degrees);
+    // n blocks in fresh slots (noise 1), one degree for all or one per block; write_kind: the launch trace's
+    // record of the op that fills them (-1: the caller records it itself, when the write is enqueued)
+    Blocks fresh_blocks(size_t n, uint32_t degree, int write_kind = (int)kWriteOpaque);
+    Blocks fresh_blocks(const std::vector<uint32_t>& degrees, int write_kind = (int)kWriteOpaque);
+    // launch trace (above)
+    bool ltrace_on_ = false, ltrace_overflow_ = false;
+    std::vector<uint64_t> ltrace_;
+    bool trace_room(size_t words);
+    void trace_write(uint64_t kind, uint64_t* const* dst, size_t n);
+    void trace_op(uint64_t tag, const PbsDesc& d, const uint64_t* dst, const TermExt* wide);
     // dst.size() contiguous host ciphertexts into the slots: two copies, one scatter, one stream sync
     void scatter_upload(const uint64_t* cts, const std::vector<uint64_t*>& dst);
     bool trace_ = false;

@@ -114,21 +114,27 @@ void pack_keyswitch(fhe_ctx* c, const std::vector<const uint64_t*>& src) {
 }
 }  // namespace
 
-Blocks Engine::fresh_blocks(const std::vector<uint32_t>& degrees) {
+Blocks Engine::fresh_blocks(const std::vector<uint32_t>& degrees, int write_kind) {
     Blocks out(degrees.size());
     for (size_t i = 0; i < out.size(); ++i) {
         out[i].slot = pool_->alloc();
         out[i].degree = degrees[i];
         out[i].noise = 1;
     }
+    if (ltrace_on_ && write_kind >= 0) {  // the op that asked for them fills them next on the stream
+        const std::vector<uint64_t*> dst = slot_ptrs(out);
+        trace_write((uint64_t)write_kind, dst.data(), dst.size());
+    }
     return out;
 }
 
-Blocks Engine::fresh_blocks(size_t n, uint32_t degree) { return fresh_blocks(std::vector<uint32_t>(n, degree)); }
+Blocks Engine::fresh_blocks(size_t n, uint32_t degree, int write_kind) {
+    return fresh_blocks(std::vector<uint32_t>(n, degree), write_kind);
+}
 
 // ------------------------------------------------------------------ uploads
 Block Engine::upload(const uint64_t* ct, uint32_t degree) {
-    Block b = fresh_blocks(1, degree)[0];
+    Block b = fresh_blocks(1, degree, (int)kWriteUpload)[0];
     hip_check(hipMemcpyAsync(b.slot->p, ct, kBigCt * 8, hipMemcpyHostToDevice, ctx_->stream), "upload");
     hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");
     return b;
@@ -145,20 +151,22 @@ void Engine::scatter_upload(const uint64_t* cts, const std::vector<uint64_t*>& d
 }
 
 Blocks Engine::upload_many(const uint64_t* cts, size_t n, uint32_t degree) {
-    Blocks out = fresh_blocks(n, degree);
+    Blocks out = fresh_blocks(n, degree, (int)kWriteUpload);
     if (n) scatter_upload(cts, slot_ptrs(out));
     return out;
 }
 
 Blocks Engine::upload_deferred(size_t n, uint32_t degree, std::function<std::vector<uint64_t>()> fill) {
     run_before_launch();  // an earlier deferred upload first (one at a time)
-    Blocks out = fresh_blocks(n, degree);
+    // a device engine records the write where it is enqueued (the deferred upload below), a host mode now
+    Blocks out = fresh_blocks(n, degree, host_mode_ == kDevice ? -1 : (int)kWriteDeferred);
     if (n == 0 || host_mode_ != kDevice) return out;
     std::vector<std::shared_ptr<Slot>> held(n);  // alive until the upload, whatever the caller drops
     for (size_t i = 0; i < n; ++i) held[i] = out[i].slot;
     before_launch_ = [this, held = std::move(held), dst = slot_ptrs(out), fill = std::move(fill)]() {
         const std::vector<uint64_t> cts = fill();
         engine_check(cts.size() == dst.size() * kBigCt, "deferred upload: ciphertext count");
+        if (ltrace_on_) trace_write(kWriteDeferred, dst.data(), dst.size());
         scatter_upload(cts.data(), dst);
     };
     return out;

@@ -42,6 +42,7 @@ from .core import (ClientKey, RekeyKey, CompactPublicKey, CompressedCompressionK
 from .integer import (  # noqa: F401,E402
     COMPAT, FAST, PUBLIC, BigUintFHE, FheBool, FheUint, FheUint8, FheUint32, FheUint64, FheUint128, FheUint256, set_server_key,
     LEVEL_SPLIT, level_log, rank_pbs, stats, to_u32_digits, SECP256K1_N_C, SECP256K1_P_C,
+    trace_enable, trace_read, block_addrs, lut_table, export_luts, LUT_INTEGER, LUT_HALF_STEP, LUT_OPRF,
     CompressedBigUintFHE, CompressedFheUint, CompressedFheUint8, CompressedFheUint32, CompressedFheUint64,
     CompressedFheUint128, CompressedFheUint256, CompressedCiphertextList, SwitchedCiphertextList,
     CompactCiphertextList, CompactCiphertextListBuilder,

@@ -170,6 +170,12 @@ _SIGNATURES = [
     ("fhe_ctx_noise_audit", C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_int]),
     ("fhe_host_sim_ctx_create", C.c_int, [C.POINTER(C.c_void_p)]),
     ("fhe_ctx_level_log", C.c_int, [C.c_void_p, u32p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]),
+    ("fhe_ctx_trace", C.c_int, [C.c_void_p, C.c_int]),
+    ("fhe_ctx_trace_read", C.c_int, [C.c_void_p, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]),
+    ("fhe_radix_block_addrs", C.c_int, [C.c_void_p, C.c_void_p, u64p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_biguint_block_addrs", C.c_int, [C.c_void_p, C.c_void_p, u64p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("fhe_ctx_lut_table", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
+    ("fhe_ctx_export_luts", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u64p]),
     ("fhe_ctx_rank_pbs", C.c_int, [C.c_void_p, u64p]),
     ("fhe_schedule_levels", C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, C.c_int,
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

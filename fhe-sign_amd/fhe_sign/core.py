@@ -835,8 +835,8 @@ class SimContext(Context):
     """Test hook (fhe_host_sim_ctx_create): a context without a device, whose engine shadows every block's
     plaintext on the host.  set_server_key(SimContext()) makes FheUint / BigUintFHE run through the C ABI's
     real code on the CPU; SimKey() stands where a client key is asked for.  What needs device memory or a real
-    key raises FheError.  The shadow evaluates a bootstrap when it is recorded: such a run sees every recorded
-    graph and every value, not the launch order."""
+    key raises FheError.  The shadow evaluates a bootstrap when it is recorded: a decryption sees every recorded
+    graph and every value; the launch order is seen through the launch trace (trace_enable / trace_read)."""
 
     def __init__(self):
         h = C.c_void_p()

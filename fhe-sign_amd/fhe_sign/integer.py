@@ -1121,3 +1121,49 @@ def stats(ctx):
     p, lv = C.c_uint64(), C.c_uint64()
     check(load().fhe_ctx_stats(ctx.handle, C.byref(p), C.byref(lv)))
     return int(p.value), int(lv.value)
+
+
+# ---- test hooks: the launch trace (fhe_ctx_trace) and the read-only hooks its replay needs
+def trace_enable(ctx, on: bool = True) -> None:
+    check(load().fhe_ctx_trace(ctx.handle, 1 if on else 0))
+
+
+def trace_read(ctx, reset: bool = True) -> np.ndarray:
+    """the launch trace's u64 words since the last reset (fhe_ctx_trace_read; an overflowed trace raises)"""
+    n = C.c_size_t()
+    try:
+        check(load().fhe_ctx_trace_read(ctx.handle, None, 0, C.byref(n), 0))
+    except FheError:
+        if reset:  # the refusal of an overflowed trace still clears it
+            load().fhe_ctx_trace_read(ctx.handle, None, 0, C.byref(n), 1)
+        raise
+    buf = np.zeros(max(1, n.value), np.uint64)
+    check(load().fhe_ctx_trace_read(ctx.handle, ptr(buf), buf.size, C.byref(n), 1 if reset else 0))
+    return buf[: n.value].copy()
+
+
+def block_addrs(ctx, x) -> tuple[list[int], list[int]]:
+    """(addresses, trivial values) of the blocks of an FheUint or a BigUintFHE: address 0 marks a trivial block"""
+    fn = load().fhe_biguint_block_addrs if isinstance(x, BigUintFHE) else load().fhe_radix_block_addrs
+    n = C.c_size_t()
+    check(fn(ctx.handle, x.handle, None, None, 0, C.byref(n)))
+    a, v = np.zeros(max(1, n.value), np.uint64), np.zeros(max(1, n.value), np.uint32)
+    check(fn(ctx.handle, x.handle, ptr(a), ptr(v, C.c_uint32), n.value, C.byref(n)))
+    return [int(t) for t in a[: n.value]], [int(t) for t in v[: n.value]]
+
+
+LUT_INTEGER, LUT_HALF_STEP, LUT_OPRF = 0, 1, 2
+
+
+def lut_table(ctx, lut_id: int) -> tuple[int, list[int]]:
+    """(kind, the 16 entries) of a registered table (fhe_ctx_lut_table)"""
+    kind, e = C.c_int(), (C.c_int32 * 16)()
+    check(load().fhe_ctx_lut_table(ctx.handle, lut_id, C.byref(kind), e))
+    return int(kind.value), [int(t) for t in e]
+
+
+def export_luts(ctx, first: int, count: int) -> np.ndarray:
+    """tables [first, first + count) of the device table as it stands, (count, 2048) u64"""
+    out = np.zeros((count, 2048), np.uint64)
+    check(load().fhe_ctx_export_luts(ctx.handle, first, count, ptr(out)))
+    return out

@@ -434,6 +434,45 @@ int fhe_ctx_level_log(fhe_ctx* ctx, uint32_t* sizes, size_t cap, size_t* n, int 
 /* Bit 31 of a level_log entry: the level was fanned out over the ranks (split + all-gather); the
  * low bits are its bootstrap count.  Only set while ranks are attached or emulated. */
 #define FHE_LEVEL_SPLIT 0x80000000u
+/* TEST HOOK -- the launch trace: what the engine enqueues on the context's stream, in that order, so that a test
+ * can replay it against a reference of its own (tests/launch_replay.py).  Off by default (one branch per flush
+ * and per eager op); fhe_ctx_trace turns it on and off, fhe_ctx_trace_read copies min(cap, *n) of the *n recorded
+ * u64 words (reset != 0 clears the record).  The trace only reads: results, fhe_ctx_stats and fhe_ctx_level_log
+ * are the same with it on or off.  At most 2^23 words are kept; a trace that would have passed them is refused
+ * by fhe_ctx_trace_read with FHE_ERR_INVALID and a message (reset still clears it).  Records:
+ *   FHE_TRACE_LEVEL    level number (as counted by fhe_ctx_stats), bootstraps, split flag; then one
+ *   FHE_TRACE_NODE     per bootstrap, in launch order: dst address, LUT id, cst (the u64 added to the body),
+ *                      nterms, then nterms x (src address, coefficient as int64)
+ *   FHE_TRACE_LINCOMB  a linear combination without bootstrap: dst, cst, nterms, nterms x (src, coefficient)
+ *   FHE_TRACE_WRITE    kind, n, n dst addresses: any other op that writes block slots -- kind 0 an upload
+ *                      (a simulated context: an encryption's placeholder blocks), 1 a deferred upload (recorded
+ *                      when it is enqueued, before the flush that follows it), 2 opaque: seeded / compact /
+ *                      compressed / stored expansion, re-randomization, random values, a broadcast's copy
+ * On a device context a node's fields are read back from the staged host buffer that is copied to the device:
+ * the level's descriptors after the wide term tables and the scatter tables were written into them, a wide
+ * combination's terms through the staged src[0] into the staged table, a fanned-out level's real destination
+ * from its staged scatter table.  A dry or simulated engine stages nothing and records its scheduled nodes. */
+#define FHE_TRACE_LEVEL 1
+#define FHE_TRACE_NODE 2
+#define FHE_TRACE_LINCOMB 3
+#define FHE_TRACE_WRITE 4
+int fhe_ctx_trace(fhe_ctx* ctx, int enable);
+int fhe_ctx_trace_read(fhe_ctx* ctx, uint64_t* buf, size_t cap, size_t* n, int reset);
+/* Read-only hooks of the same tests.  *_block_addrs: *n = the value's block count (a BigUintFHE: its limbs' blocks,
+ * 16 per limb, LSB first); with cap >= *n, addrs[k] = block k's device address (a simulated context: its
+ * placeholder address), 0 for a trivial block, whose value goes to values[k] (optional).  cap == 0 only asks
+ * for *n.  Nothing is flushed: a pending block's address is where its bootstrap will write. */
+int fhe_radix_block_addrs(fhe_ctx* ctx, const fhe_radix* x, uint64_t* addrs, uint32_t* values, size_t cap, size_t* n);
+int fhe_biguint_block_addrs(fhe_ctx* ctx, const fhe_biguint* x, uint64_t* addrs, uint32_t* values, size_t cap, size_t* n);
+/* the registered table `id`: its kind and entries -- an integer table's 16 outputs, a half-step table's 16 signed
+ * outputs in half message steps, an OPRF staircase's bit count in entries[0] */
+#define FHE_LUT_INTEGER 0
+#define FHE_LUT_HALF_STEP 1
+#define FHE_LUT_OPRF 2
+int fhe_ctx_lut_table(fhe_ctx* ctx, uint32_t id, int* kind, int32_t entries[16]);
+/* tables [first, first + count) of the DEVICE table as it stands (a download of what the last launch saw, not the
+ * host copy): count x 2048 words.  Device contexts only. */
+int fhe_ctx_export_luts(fhe_ctx* ctx, uint32_t first, uint32_t count, uint64_t* polys);
 /* Bootstraps this rank ran itself since context creation: its slice of every fanned-out level plus
  * every level it ran redundantly (with emulated ranks: rank 0's share). */
 int fhe_ctx_rank_pbs(const fhe_ctx* ctx, uint64_t* pbs);
@@ -530,8 +569,10 @@ int fhe_host_sim_chain_g(const uint8_t* vals, size_t nprefix, uint32_t* g, uint6
  * digest and re-randomize, compress and every expand, random, broadcast, the raw pbs / keyswitch / pbs_lincomb,
  * every fhe_set_*_key, the signer -- returns FHE_ERR_INVALID with a message that names the simulated context, and
  * leaves it usable.  fhe_ctx_destroy frees it.
- * Known limit: the shadow evaluates a bootstrap when it is recorded, so a run on this context sees every recorded
- * graph and every value, not the launch order. */
+ * The shadow evaluates a bootstrap when it is recorded, so a decryption on this context sees every recorded graph
+ * and every value; what is launched afterwards, and in which order, is seen through the launch trace
+ * (fhe_ctx_trace), which tests/test_launch_replay.py replays in plaintext on this context and
+ * tests/test_launch_replay_gpu.py word for word on a device. */
 int fhe_host_sim_ctx_create(fhe_ctx** ctx);
 /* Pseudo-Mersenne reduction x mod (2^k_bits - c) (fhe_radix_rem_pseudo_mersenne below) without a GPU or a key.
  * Simulated run on a `bits`-wide operand x (words LSB first): out gets the k_bits-wide result (nout >=

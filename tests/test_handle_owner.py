@@ -79,6 +79,7 @@ W1, W3 = words(0x1234), words(3)
 LIMBS = (C.c_uint32 * 8)()
 NLIMBS = C.c_size_t()
 WBUF = words(0, 4)
+ABUF = words(0, 256)
 
 
 def _bin(fn):
@@ -132,6 +133,11 @@ SIMULATED = {
         c, h[0], 32, wp(W3), 1, out())),
     "fhe_biguint_decrypt": ((("x", "B"),), lambda c, h, out: lib().fhe_biguint_decrypt(
         c, None, h[0], LIMBS, 8, C.byref(NLIMBS))),
+    # the launch trace's read-only hooks: an address means something under its own context only
+    "fhe_radix_block_addrs": ((("x", "R"),), lambda c, h, out: lib().fhe_radix_block_addrs(
+        c, h[0], wp(ABUF), None, ABUF.size, C.byref(NLIMBS))),
+    "fhe_biguint_block_addrs": ((("x", "B"),), lambda c, h, out: lib().fhe_biguint_block_addrs(
+        c, h[0], wp(ABUF), None, ABUF.size, C.byref(NLIMBS))),
 }
 for _mode, _tag in ((COMPAT, "compat"), (FAST, "fast")):
     SIMULATED[f"fhe_biguint_add/{_tag}"] = _big("fhe_biguint_add", "ab", _mode)
