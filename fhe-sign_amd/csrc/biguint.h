@@ -58,6 +58,8 @@ BigUint compat_chain_mul(Engine& e, const BigUint& a, const BigUint& b);
 Blocks compat_chain_g(Engine& e, const std::vector<const std::vector<Blocks>*>& prefixes);
 // Engine::eager_next_batch on the context's engine (capi_radix.cpp)
 void engine_eager_next_batch(fhe_ctx* c, bool on);
+// drops an armed deferred upload and waits for its helper thread (Engine::cancel_deferred); a no-op otherwise
+void engine_cancel_deferred(fhe_ctx* c);
 // fhe_biguint_encrypt of several operands as one batch (capi_radix.cpp): outs[i] as if encrypted one
 // after the other.  deferred: the encryption runs on a helper thread and the blocks are uploaded right
 // before the engine's next launch (Engine::upload_deferred); the client key must not be used meanwhile.

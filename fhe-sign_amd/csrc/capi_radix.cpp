@@ -130,6 +130,10 @@ void engine_eager_next_batch(fhe_ctx* c, bool on) {
     if (c && c->engine) c->engine->eager_next_batch(on);
 }
 
+void engine_cancel_deferred(fhe_ctx* c) {
+    if (c && c->engine) c->engine->cancel_deferred();
+}
+
 int biguint_owned(const fhe_ctx* c, const fhe_biguint* x, const char* operand) { return x ? owned(c, x, operand) : FHE_OK; }
 
 // several BigUintFHE encryptions as one batch -- one pass of encrypt_big_many (its host threads over the
@@ -157,11 +161,23 @@ int biguint_encrypt_batch(fhe_ctx* c, fhe_client_key* ck, const std::vector<cons
         } else if (deferred) {
             // the encryption runs on a helper thread while the caller records the graph that reads the
             // blocks; the engine uploads them right before its next launch (Engine::upload_deferred)
-            auto job = std::make_shared<std::future<std::vector<uint64_t>>>(std::async(std::launch::async, [ck, pts] {
+            // The future is owned by the upload's closure alone, and a std::async future joins its thread when
+            // it is released: whether the closure runs, throws or is cancelled (Engine::cancel_deferred, which
+            // every exit of the signer goes through), the thread has run to its end -- the client key's stream
+            // is where the finished encryption leaves it -- before the closure is gone.
+            struct InFlight {  // fhe_ctx_pending_info's helper count: up here, down as the thread's last statement
+                std::shared_ptr<std::atomic<uint32_t>> n;
+                explicit InFlight(std::shared_ptr<std::atomic<uint32_t>> c) : n(std::move(c)) { ++*n; }
+                ~InFlight() { --*n; }
+            };
+            auto flight = std::make_shared<InFlight>(c->engine->helper_jobs);
+            auto job = std::make_shared<std::future<std::vector<uint64_t>>>(std::async(std::launch::async, [ck, pts, flight]() mutable {
+                std::shared_ptr<InFlight> done = std::move(flight);  // released when the thread's work is over
                 std::vector<uint64_t> ct(pts.size() * kBigCt);
                 encrypt_big_many(ck, pts.data(), pts.size(), ct.data());
                 return ct;
             }));
+            flight.reset();
             all = c->engine->upload_deferred(pts.size(), 3, [job] { return job->get(); });
         } else {
             std::vector<uint64_t> ct(total * kLimbBlocks * kBigCt);
@@ -550,6 +566,18 @@ int fhe_ctx_trace_read(fhe_ctx* c, uint64_t* buf, size_t cap, size_t* n, int res
     *n = t.size();
     if (cap && !t.empty()) std::memcpy(buf, t.data(), std::min(cap, t.size()) * 8);
     if (reset) e.trace_reset();
+    return FHE_OK;
+}
+
+// Test hook, read-only: out[0] = pending bootstraps, out[1] = 1 while a deferred upload is armed, out[2] = helper
+// jobs (the deferred encryptions' threads) in flight.  A context without an engine reports zeros.
+int fhe_ctx_pending_info(fhe_ctx* c, uint64_t out[3]) {
+    if (!c || !out) return FHE_ERR_INVALID;
+    out[0] = out[1] = out[2] = 0;
+    if (!c->engine) return FHE_OK;
+    out[0] = c->engine->pending_nodes();
+    out[1] = c->engine->deferred_armed() ? 1 : 0;
+    out[2] = c->engine->helper_jobs->load();
     return FHE_OK;
 }
 

@@ -20,6 +20,15 @@ Tuning& tuning() {
     return t;
 }
 
+void fault_cross(const char* site) {
+    Tuning& t = tuning();
+    const uint64_t n = ++t.fault_crossings;
+    if (t.fault_after && n == t.fault_after) {
+        t.fault_after = 0;  // one shot
+        throw EngineError(FHE_ERR_HIP, std::string("injected fault at ") + site);
+    }
+}
+
 const Debug& debug() {
     static const Debug d = [] {
         Debug x;
@@ -278,6 +287,7 @@ Blocks Engine::run(std::vector<PbsItem>& items) {
         std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
         ~Clock() { e->run_ns_ += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count(); }
     } clock{this};
+    fault_point(kFaultRecord, "RECORD");
     // ownership first: a refusal leaves no item processed, no slot allocated and no statistic moved
     for (const PbsItem& it : items)
         for (const Term& t : it.terms) check_owner(t.b);
@@ -522,20 +532,55 @@ void Engine::flush_tail(size_t k0) {
     const bool eager = eager_ok_;
     pending_dependent_ = 0;
     pending_depth_ = 1;
-    auto restore = [&] {
-        pending_ = std::move(keep);
-        pending_dependent_ = dependent;
-        pending_depth_ = depth;
-        eager_ok_ = eager;
-    };
     try {
         flush();
     } catch (...) {
-        for (auto& n : pending_) n.hold[0]->node = -1;  // the tail is abandoned with the error
-        restore();  // the earlier graph stays consistent for the caller's error path
+        // nothing is abandoned: the tail goes back behind the earlier graph, still pending (a node marked written
+        // that was never launched would read as computed); the caller's error path releases the tail's outputs,
+        // and the next flush sweeps it
+        restore_pending(std::move(keep), nullptr);
+        eager_ok_ = eager;
         throw;
     }
-    restore();
+    pending_ = std::move(keep);
+    pending_dependent_ = dependent;
+    pending_depth_ = depth;
+    eager_ok_ = eager;
+}
+
+// After a failed partial flush: `keep` (set aside by the split, in recording order) and what the failed flush left
+// in pending_ become one graph again.  need: flush_for's closure marks over the original order (keep and pending_
+// interleave by them); null: flush_tail (keep is the head, pending_ the tail).  Every node gets its index back
+// in its output slot, and its producers back from the slots it holds -- run() records exactly those: one
+// dependency per held input whose producer is pending -- so what flush_for resolved for a launch that did not
+// complete is a dependency again.
+void Engine::restore_pending(std::vector<Pending>&& keep, const std::vector<uint8_t>* need) {
+    std::vector<Pending> all;
+    all.reserve(keep.size() + pending_.size());
+    size_t n_need = 0;
+    if (need)
+        for (uint8_t b : *need) n_need += b != 0;
+    if (need && n_need == pending_.size() && need->size() - n_need == keep.size()) {
+        size_t is = 0, ik = 0;
+        for (uint8_t b : *need) all.push_back(std::move(b ? pending_[is++] : keep[ik++]));
+    } else if (need) {  // the failed flush dropped nodes of the closure: closure first (it reads nothing outside itself)
+        for (auto& n : pending_) all.push_back(std::move(n));
+        for (auto& n : keep) all.push_back(std::move(n));
+    } else {
+        for (auto& n : keep) all.push_back(std::move(n));
+        for (auto& n : pending_) all.push_back(std::move(n));
+    }
+    pending_ = std::move(all);
+    for (size_t i = 0; i < pending_.size(); ++i) pending_[i].hold[0]->node = (int64_t)i;
+    for (size_t i = 0; i < pending_.size(); ++i) {
+        Pending& n = pending_[i];
+        n.deps.clear();
+        for (size_t h = 1; h < n.hold.size(); ++h) {
+            const int64_t prod = n.hold[h]->node;
+            if (prod >= 0 && (size_t)prod < i) n.deps.push_back((int32_t)prod);
+        }
+    }
+    recount();
 }
 
 // flush() of the pending nodes `blocks` depend on (their ancestor closure); the others stay pending,
@@ -604,7 +649,9 @@ void Engine::flush_for(const std::vector<const Block*>& blocks) {
         flush();  // a host read, like a full flush: the next program's first large batch may launch
                   // eagerly (eager_ok_), once whatever stays pending has been swept as dead
     } catch (...) {
-        for (auto& n : keep) n.hold[0]->node = -1;  // abandoned with the error (they read the closure)
+        // what stayed outside the closure is NOT abandoned (-1 means written: a value the caller still holds
+        // would read as computed and return whatever its slots contain): it goes back, in recording order
+        restore_pending(std::move(keep), &need);
         throw;
     }
     pending_ = std::move(keep);
@@ -803,8 +850,12 @@ void Engine::flush() {
     const size_t round = (size_t)kRound * (size_t)std::max(1, ctx_->fanout_world());
     std::vector<std::vector<int32_t>> lv = schedule_levels(deps, 0, round);
     if (host_mode_ == kDry || host_mode_ == kSim) {  // the schedule's statistics, nothing launched
+        // level by level, as the device loop below: a level is fingerprinted, traced and counted when it is
+        // "launched", so a flush that fails at level i has counted and traced i - 1 levels, and its retry
+        // (the whole graph is still pending) counts and traces those again
         auto mix = [&](uint64_t v) { fingerprint = (fingerprint ^ v) * 1099511628211ull; };
         for (auto& l : lv) {
+            fault_point(kFaultLevel, "LEVEL");
             mix(l.size());
             for (int32_t k : l) {
                 const Pending& pn = pending_[k];
@@ -818,16 +869,13 @@ void Engine::flush() {
                     for (const TermExt& t : pn.ext) mix((uint64_t)(int64_t)t.coef);
                 for (int32_t dp : pn.deps) mix((uint64_t)(int64_t)dp);
             }
-        }
-        if (ltrace_on_)  // nothing is staged here: the pending nodes, in scheduled order
-            for (size_t li = 0; li < lv.size(); ++li) {
-                if (trace_room(4)) ltrace_.insert(ltrace_.end(), {kTraceLevel, levels + li + 1, (uint64_t)lv[li].size(), 0});
-                for (int32_t k : lv[li]) {
+            if (ltrace_on_) {  // nothing is staged here: the pending nodes, in scheduled order
+                if (trace_room(4)) ltrace_.insert(ltrace_.end(), {kTraceLevel, levels + 1, (uint64_t)l.size(), 0});
+                for (int32_t k : l) {
                     const Pending& pn = pending_[k];
                     trace_op(kTraceNode, pn.d, pn.d.dst, pn.ext.empty() ? nullptr : pn.ext.data());
                 }
             }
-        for (auto& l : lv) {
             pbs_count += l.size();
             levels += 1;
             rank_pbs += l.size();
@@ -860,9 +908,11 @@ void Engine::flush() {
     const size_t ext_at = ndesc;
     ndesc += (next * sizeof(TermExt) + sizeof(PbsDesc) - 1) / sizeof(PbsDesc);
     if (maxgather) engine_check(ctx_->ensure_gather(maxgather) == FHE_OK, "gather workspace");
+    fault_point(kFaultWorkspace, "WORKSPACE");
     engine_check(ctx_->ensure_ms(maxchunk) == FHE_OK, "workspace");
     engine_check(ctx_->sync_luts() == FHE_OK, "LUT upload");
     PbsDesc* dev = nullptr;
+    fault_point(kFaultStage, "STAGE");
     PbsDesc* h = stage_desc(ndesc, &dev);
     std::vector<size_t> at(lv.size());
     size_t o = 0;
@@ -892,35 +942,37 @@ void Engine::flush() {
     }
     hip_check(hipMemcpyAsync(dev, h, ndesc * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream), "desc copy");
     hip_check(hipEventRecord(desc_ev_[desc_turn_], ctx_->stream), "desc event");
-    if (ltrace_on_) {
-        // read back from the staged host buffer, i.e. what the copy above sends: a node's terms through its staged
-        // src[0] into the staged term tables, a split level's destinations from its staged scatter table
-        const size_t ext_cap = (ndesc - ext_at) * sizeof(PbsDesc) / sizeof(TermExt);
-        for (size_t li = 0; li < lv.size(); ++li) {
-            const auto [G, split, chunk, units] = shape[li];
-            if (trace_room(4)) ltrace_.insert(ltrace_.end(), {kTraceLevel, levels + li + 1, (uint64_t)G, (uint64_t)split});
-            uint64_t* const* scat = reinterpret_cast<uint64_t* const*>(h + at[li] + G);
-            for (size_t g = 0; g < G; ++g) {
-                const PbsDesc& d = h[at[li] + g];
-                const TermExt* wide = nullptr;
-                if (d.nterms > (uint32_t)kMaxTerms) {
-                    const uintptr_t a = reinterpret_cast<uintptr_t>(d.src[0]), a0 = reinterpret_cast<uintptr_t>(d_ext);
-                    const size_t off = (size_t)(a - a0) / sizeof(TermExt);
-                    engine_check(a >= a0 && (a - a0) % sizeof(TermExt) == 0 && d.nterms <= (uint32_t)kMaxWideTerms &&
-                                     off + d.nterms <= ext_cap,
-                                 "trace: a staged term table outside the staged copy");
-                    wide = h_ext + off;
-                }
-                trace_op(kTraceNode, d, split ? scat[g] : d.dst, wide);
+    // The launch trace of one level, recorded as the level is launched (a flush that fails midway has traced what
+    // it launched, and its retry traces those levels again): read back from the staged host buffer, i.e. what the
+    // copy above sends -- a node's terms through its staged src[0] into the staged term tables, a split level's
+    // destinations from its staged scatter table
+    const size_t ext_cap = (ndesc - ext_at) * sizeof(PbsDesc) / sizeof(TermExt);
+    auto trace_level = [&](size_t li) {
+        const auto [G, split, chunk, units] = shape[li];
+        if (trace_room(4)) ltrace_.insert(ltrace_.end(), {kTraceLevel, levels + 1, (uint64_t)G, (uint64_t)split});
+        uint64_t* const* scat = reinterpret_cast<uint64_t* const*>(h + at[li] + G);
+        for (size_t g = 0; g < G; ++g) {
+            const PbsDesc& d = h[at[li] + g];
+            const TermExt* wide = nullptr;
+            if (d.nterms > (uint32_t)kMaxTerms) {
+                const uintptr_t a = reinterpret_cast<uintptr_t>(d.src[0]), a0 = reinterpret_cast<uintptr_t>(d_ext);
+                const size_t off = (size_t)(a - a0) / sizeof(TermExt);
+                engine_check(a >= a0 && (a - a0) % sizeof(TermExt) == 0 && d.nterms <= (uint32_t)kMaxWideTerms &&
+                                 off + d.nterms <= ext_cap,
+                             "trace: a staged term table outside the staged copy");
+                wide = h_ext + off;
             }
+            trace_op(kTraceNode, d, split ? scat[g] : d.dst, wide);
         }
-    }
+    };
     if (trace_)
         fprintf(stderr, "[flush] %zu nodes (%llu dropped so far), %zu levels, scheduled in %.3f ms\n", N,
                 (unsigned long long)dead_nodes, lv.size(),
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count());
     for (size_t li = 0; li < lv.size(); ++li) {
+        fault_point(kFaultLevel, "LEVEL");
         const auto [G, split, chunk, units] = shape[li];
+        if (ltrace_on_) trace_level(li);
         PbsDesc* ld = dev + at[li];
         auto pbs = [&](size_t lo, size_t hi) {
             if (hi <= lo) return;

@@ -10,6 +10,7 @@
 // run as ONE batched keyswitch (with the linear combination fused in) + ONE blind-rotate launch.
 // Items whose LUT is constant over the reachable inputs fold to trivial blocks on the host.
 #pragma once
+#include <atomic>
 #include <cstdint>
 #include <functional>
 #include <memory>
@@ -42,8 +43,27 @@ struct Tuning {
     uint32_t div_r16_lead = 32;     // encrypted division: leading dividend blocks taken in radix-16 steps
     int scalar_div_residue = -1;    // public divisors: -1 size rule (dividends >= 64 blocks), 0 never, 1 where valid
     uint32_t flush_depth = 64;      // flush the deferred graph once it is this many levels deep (0: only on demand)
+    // Host-side fault point (test hook, off by default; fault_point below): a mask of kFault* sites, the crossing
+    // that throws (0: none), and the crossings of enabled sites since fault_after was last set
+    uint32_t fault_sites = 0;
+    uint64_t fault_after = 0;
+    uint64_t fault_crossings = 0;
 };
 Tuning& tuning();
+// The fault sites (FHE_TUNE_FAULT_SITES), all in engine code, one integer test per level or per call.  An enabled
+// site counts its crossings; the fault_after-th one throws EngineError(FHE_ERR_HIP, "injected fault at <site>") and
+// disarms.  It only throws on the host: no HIP call, synchronisation or launch argument is skipped or altered.
+enum : uint32_t {
+    kFaultLevel = 1,      // the top of each level's iteration in Engine::flush (device and host modes)
+    kFaultStage = 2,      // before the level descriptors are staged (device)
+    kFaultWorkspace = 4,  // before the bootstrap workspace is sized (device)
+    kFaultDeferred = 8,   // first statement of upload_deferred's closure
+    kFaultRecord = 16,    // the entry of Engine::run
+};
+void fault_cross(const char* site);
+inline void fault_point(uint32_t site, const char* name) {
+    if (tuning().fault_sites & site) fault_cross(name);
+}
 // Engine diagnostics on stderr, read once per process from FHE_DEBUG (comma-separated): levels (sync and
 // time every level), graph (graph statistics), chain (compat chain phases, flushed), chain-host (the
 // same, host time only), residue (the residue split's phases), nodes (a hash of every launched
@@ -202,7 +222,18 @@ public:
     // its result uploaded into the slots, right before the next flush launches anything -- so the graph
     // that reads the slots is recorded while the ciphertexts are being made, and the upload still
     // precedes every launch on the stream.  One pending deferred upload at a time.
+    // A closure that throws (its fill() included) is gone with the error: the engine is left without an armed
+    // upload, and whatever reads the slots belongs to the failed call.
     Blocks upload_deferred(size_t n, uint32_t degree, std::function<std::vector<uint64_t>()> fill);
+    // Drops an armed deferred upload without running it, and waits for what it holds: the closure owns its
+    // producer (the helper thread's future, whose release joins the thread), so on return nothing of it runs.
+    // The slots are never written; the caller's error path owns every value that reads them.
+    void cancel_deferred() { before_launch_ = nullptr; }
+    bool deferred_armed() const { return (bool)before_launch_; }
+    size_t pending_nodes() const { return pending_.size(); }
+    // helper jobs in flight (biguint_encrypt_batch's encryption threads): counted up where one is started, down
+    // as its last statement; shared with the thread, which may finish after a cancelled closure is gone
+    std::shared_ptr<std::atomic<uint32_t>> helper_jobs = std::make_shared<std::atomic<uint32_t>>(0);
     // A seeded ciphertext's blocks (fhe_seeded: public mask seed + one body per block) expanded on the
     // device: n fresh slots (degree 3, noise 1, as upload_many's), only the slot pointers and the bodies
     // (16 B per block) staged through the upload buffer, the masks regenerated by seeded.hip into the
@@ -404,6 +435,9 @@ private:
     void ensure_desc(size_t n);
     void graph_stats(const std::vector<std::vector<int32_t>>& deps);
     void flush_tail(size_t k0);
+    // a failed partial flush (flush_for, flush_tail): the nodes set aside go back into pending_ with what the
+    // failed flush left there -- indices, producers and counters as if the split had not been made
+    void restore_pending(std::vector<Pending>&& first_or_keep, const std::vector<uint8_t>* need);
     // drop the dead pending nodes (flush's first step; ranks agree by an all-reduce)
     void sweep_dead();
     void recount();  // pending_dependent_ / pending_depth_ / depths from pending_'s deps

@@ -164,6 +164,7 @@ Blocks Engine::upload_deferred(size_t n, uint32_t degree, std::function<std::vec
     std::vector<std::shared_ptr<Slot>> held(n);  // alive until the upload, whatever the caller drops
     for (size_t i = 0; i < n; ++i) held[i] = out[i].slot;
     before_launch_ = [this, held = std::move(held), dst = slot_ptrs(out), fill = std::move(fill)]() {
+        fault_point(kFaultDeferred, "DEFERRED");
         const std::vector<uint64_t> cts = fill();
         engine_check(cts.size() == dst.size() * kBigCt, "deferred upload: ciphertext count");
         if (ltrace_on_) trace_write(kWriteDeferred, dst.data(), dst.size());

@@ -416,6 +416,18 @@ namespace {
 // (sign_begin) records the FHE block in the engine's deferred graph; phase 2 (sign_end) decrypts,
 // which flushes the graph -- so a batch of signatures begun together runs as ONE schedule whose
 // levels hold every signature's bootstraps.
+// Every exit of a signer entry point, OK or error: no helper thread is running and no deferred upload is armed
+// (include/fhe_rocm.h, "Errors after validation").  After a successful call the upload has run and this does
+// nothing; after a failed one it waits for the encryption thread, so the client key's stream stands where the
+// finished encryption leaves it, and the key may be used or freed at once.
+struct DeferredGuard {
+    fhe_ctx* ctx;
+    explicit DeferredGuard(fhe_ctx* c) : ctx(c) {}
+    ~DeferredGuard() { engine_cancel_deferred(ctx); }
+    DeferredGuard(const DeferredGuard&) = delete;
+    DeferredGuard& operator=(const DeferredGuard&) = delete;
+};
+
 struct SignJob {
     SignCore c;
     fhe_biguint *e_fhe = nullptr, *k_fhe = nullptr;
@@ -558,6 +570,7 @@ static int sign_one(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t
     if (const int own = fhe::biguint_owned(ctx, privkey_fhe, "privkey_fhe")) return own;
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
+    DeferredGuard guard(ctx);
     SignJob j;
     j.reduced = reduced;
     // e and k are encrypted on a helper thread while sign_begin records the FHE block; their upload
@@ -648,6 +661,7 @@ static int sign_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, siz
     }
     if (!r) r = fhe_rerand_context_add_biguint(ctx, rc, privkey_fhe);
     if (!r) r = fhe_rerand_context_seed(rc, 0, seed);
+    DeferredGuard guard(ctx);
     if (!r) r = fhe_biguint_rerandomize(ctx, privkey_fhe, seed, &fresh);
     for (volatile uint8_t& b : seed) b = 0;  // used for this call, kept nowhere
     fhe_rerand_context_destroy(rc);
@@ -679,6 +693,7 @@ static int sign_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint
     if (count && (!msgs || !lens || !k0s || !privkeys || !privkeys_fhe || !sigs)) return FHE_ERR_INVALID;
     for (size_t i = 0; i < count; ++i)  // every key first: a refusal uploads nothing
         if (const int own = fhe::biguint_owned(ctx, privkeys_fhe[i], "privkeys_fhe")) return own;
+    DeferredGuard guard(ctx);
     std::vector<SignJob> jobs(count);
     for (SignJob& j : jobs) j.reduced = reduced;
     for (size_t i = 0; i < count; ++i) {  // uploads first: the engine graph is not started yet

@@ -171,6 +171,7 @@ _SIGNATURES = [
     ("fhe_host_sim_ctx_create", C.c_int, [C.POINTER(C.c_void_p)]),
     ("fhe_ctx_level_log", C.c_int, [C.c_void_p, u32p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]),
     ("fhe_ctx_trace", C.c_int, [C.c_void_p, C.c_int]),
+    ("fhe_ctx_pending_info", C.c_int, [C.c_void_p, u64p]),
     ("fhe_ctx_trace_read", C.c_int, [C.c_void_p, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]),
     ("fhe_radix_block_addrs", C.c_int, [C.c_void_p, C.c_void_p, u64p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("fhe_biguint_block_addrs", C.c_int, [C.c_void_p, C.c_void_p, u64p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -862,6 +862,19 @@ def noise_audit(ctx: Context, reset: bool = False):
 
 TUNE_KEYS = {"kara_min": 1, "kara_compat_min": 2, "kara_force": 3, "div_r16_lead": 4, "scalar_div_residue": 5,
              "flush_depth": 6}
+FAULT_SITES_KEY, FAULT_AFTER_KEY = 7, 8
+FAULT_LEVEL, FAULT_STAGE, FAULT_WORKSPACE, FAULT_DEFERRED, FAULT_RECORD = 1, 2, 4, 8, 16
+FAULT_ALL = 31
+
+
+def fault_arm(sites: int, after: int = 0) -> int:
+    """Test hook (FHE_TUNE_FAULT_SITES / FHE_TUNE_FAULT_AFTER): enable the sites and let their `after`-th crossing
+    from now on fail its call with FHE_ERR_HIP, "injected fault at <site>" (0: only count).  Returns the crossings
+    counted since the hook was last armed.  Process-wide; fault_arm(0) turns it off."""
+    prev = C.c_int64()
+    check(load().fhe_host_set_tuning(FAULT_SITES_KEY, int(sites), None))
+    check(load().fhe_host_set_tuning(FAULT_AFTER_KEY, int(after), C.byref(prev)))
+    return int(prev.value)
 
 
 @contextlib.contextmanager

@@ -1128,6 +1128,13 @@ def trace_enable(ctx, on: bool = True) -> None:
     check(load().fhe_ctx_trace(ctx.handle, 1 if on else 0))
 
 
+def pending_info(ctx) -> tuple[int, int, int]:
+    """(pending bootstraps, a deferred upload armed, helper jobs in flight) of a context (fhe_ctx_pending_info)"""
+    out = (C.c_uint64 * 3)()
+    check(load().fhe_ctx_pending_info(ctx.handle, out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def trace_read(ctx, reset: bool = True) -> np.ndarray:
     """the launch trace's u64 words since the last reset (fhe_ctx_trace_read; an overflowed trace raises)"""
     n = C.c_size_t()

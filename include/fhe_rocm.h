@@ -28,6 +28,26 @@
  * ThreadSanitizer build: tools/tsan_host.sh); tests/test_threads.py and tests/test_threads_gpu.py
  * pin the same on the Python layer and on device contexts.
  *
+ * Errors after validation: a call can fail after its arguments were accepted -- a HIP status, a bounded wait, an
+ * engine check.  What such a failure leaves behind:
+ *  - The context stays usable: the next call is served as if the failed one had not been made.
+ *  - Every handle made before the call reads the same value afterwards, its reference value.  A failed call never
+ *    makes a later read return anything else: a bootstrap that was recorded and not launched is still pending,
+ *    never marked written.
+ *  - Work recorded before the failure stays pending and is retried by the next flush, whole: levels the failed
+ *    flush had launched are launched again, from inputs that are held until a flush completes, and the retried
+ *    ciphertext words equal an unfailed run's.  fhe_ctx_stats, fhe_ctx_level_log and the launch trace count what
+ *    was launched: a level launched twice counts twice, the level at which a flush failed does not count.  What
+ *    the failed call itself recorded belongs to no handle and is dropped as dead.
+ *  - When a signer entry point returns, with FHE_OK or with an error: no helper thread is running, no deferred
+ *    upload is armed, and the client key's encryption stream is where a successful call with the same inputs
+ *    leaves it -- the key may be used, or freed, at once.
+ * Out of scope: under a communicator a failure is collective by design (the communicator is aborted), and a failed
+ * key install leaves the context without that key, as each install documents.
+ * tests/test_failure_paths.py and tests/test_failure_paths_gpu.py drive these paths through the host-side fault
+ * point below (FHE_TUNE_FAULT_SITES); tools/faults_host_check.c does so under the host AddressSanitizer build
+ * (tools/asan_faults_host.sh).
+ *
  * Ciphertext layout (one radix block = one LWE ciphertext under the big key):
  *   uint64_t[2049] = mask[2048] then body.  A radix integer of B bits has B/2 blocks, LSB first.
  */
@@ -458,6 +478,10 @@ int fhe_ctx_level_log(fhe_ctx* ctx, uint32_t* sizes, size_t cap, size_t* n, int 
 #define FHE_TRACE_WRITE 4
 int fhe_ctx_trace(fhe_ctx* ctx, int enable);
 int fhe_ctx_trace_read(fhe_ctx* ctx, uint64_t* buf, size_t cap, size_t* n, int reset);
+/* TEST HOOK, read-only: out[0] = bootstraps recorded and not launched, out[1] = 1 while a deferred upload is armed
+ * (the signer's encryptions of e and k, uploaded before the next launch), out[2] = helper threads of such
+ * encryptions still running.  A context without a key reports zeros. */
+int fhe_ctx_pending_info(fhe_ctx* ctx, uint64_t out[3]);
 /* Read-only hooks of the same tests.  *_block_addrs: *n = the value's block count (a BigUintFHE: its limbs' blocks,
  * 16 per limb, LSB first); with cap >= *n, addrs[k] = block k's device address (a simulated context: its
  * placeholder address), 0 for a trivial block, whose value goes to values[k] (optional).  cap == 0 only asks
@@ -523,6 +547,19 @@ int fhe_host_biguint_mul_fingerprint(size_t la, size_t lb, size_t lk, int mode, 
 #define FHE_TUNE_DIV_R16_LEAD 4        /* encrypted division: leading radix-16 dividend blocks (default 32) */
 #define FHE_TUNE_SCALAR_DIV_RESIDUE 5  /* public divisors: -1 size rule (default), 0 never, 1 where valid */
 #define FHE_TUNE_FLUSH_DEPTH 6         /* launch the deferred graph in slices of this many levels (default 64; 0: on demand) */
+/* TEST HOOK -- a host-side fault point, off by default.  FHE_TUNE_FAULT_SITES: a mask of the sites below.
+ * FHE_TUNE_FAULT_AFTER = k > 0: the k-th crossing of an enabled site from now on fails the call it is in with
+ * FHE_ERR_HIP and the message "injected fault at <site>", and disarms; 0: off.  *previous of FHE_TUNE_FAULT_AFTER
+ * is the number of crossings of enabled sites since the key was last set, so a clean run with k = 0 gives the
+ * count to sweep.  A crossing that fires only throws on the host: no HIP call, synchronisation or launch argument
+ * is skipped, replaced or altered.  One integer test per level or per call, none per bootstrap. */
+#define FHE_TUNE_FAULT_SITES 7
+#define FHE_TUNE_FAULT_AFTER 8
+#define FHE_FAULT_LEVEL 1      /* before each level of a flush is launched (a simulated context: scheduled) */
+#define FHE_FAULT_STAGE 2      /* before a flush stages its level descriptors (device contexts) */
+#define FHE_FAULT_WORKSPACE 4  /* before a flush sizes the bootstrap workspace (device contexts) */
+#define FHE_FAULT_DEFERRED 8   /* first statement of a deferred upload (the signer's e and k), before its data is taken */
+#define FHE_FAULT_RECORD 16    /* the entry of the engine's recording call: an op fails before it records */
 int fhe_host_set_tuning(int key, int64_t value, int64_t* previous);
 int fhe_host_biguint_mul_stats(size_t la, size_t lb, size_t lk, int mode, uint64_t* pbs, uint64_t* levels,
                                uint32_t* level_sizes, size_t cap);

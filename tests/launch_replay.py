@@ -70,7 +70,7 @@ class Write:
 
 def parse(words):
     """the records of a trace, in order; a malformed stream raises"""
-    w = [int(x) for x in words]
+    w = words.tolist() if isinstance(words, np.ndarray) else [int(x) for x in words]
     out, i = [], 0
 
     def op(i, with_lut):
@@ -80,7 +80,8 @@ def parse(words):
         cst, nt = w[j], w[j + 1]
         if nt > 64 or j + 2 + 2 * nt > len(w):
             raise ReplayError(f"trace: a record of {nt} terms at word {i}")
-        terms = [(w[j + 2 + 2 * t], _i64(w[j + 3 + 2 * t])) for t in range(nt)]
+        seg = w[j + 2:j + 2 + 2 * nt]
+        terms = list(zip(seg[0::2], map(_i64, seg[1::2])))
         return dst, lut, cst, terms, j + 2 + 2 * nt
 
     while i < len(w):

@@ -33,8 +33,14 @@ def test_launch_trace_entry_points():
     from fhe_sign import FheUint, SimContext, SimKey, set_server_key
     lib = _lib.load()
     for name in ("fhe_ctx_trace", "fhe_ctx_trace_read", "fhe_radix_block_addrs", "fhe_biguint_block_addrs",
-                 "fhe_ctx_lut_table", "fhe_ctx_export_luts"):
+                 "fhe_ctx_lut_table", "fhe_ctx_export_luts", "fhe_ctx_pending_info", "fhe_host_set_tuning"):
         assert name in _lib.declared_symbols() and hasattr(lib, name)
+    # the fault point's keys exist and are off: no site enabled, nothing armed, nothing counted
+    prev = C.c_int64(-1)
+    assert lib.fhe_host_set_tuning(7, 0, C.byref(prev)) == 0 and prev.value == 0  # FHE_TUNE_FAULT_SITES
+    assert lib.fhe_host_set_tuning(8, 0, C.byref(prev)) == 0 and prev.value == 0  # FHE_TUNE_FAULT_AFTER
+    assert lib.fhe_host_set_tuning(9, 0, C.byref(prev)) != 0
+    assert lib.fhe_ctx_pending_info(None, (C.c_uint64 * 3)()) != 0
     n, kind, entries = C.c_size_t(7), C.c_int(), (C.c_int32 * 16)()
     assert lib.fhe_ctx_trace(None, 1) != 0
     assert lib.fhe_ctx_trace_read(None, None, 0, C.byref(n), 0) != 0
