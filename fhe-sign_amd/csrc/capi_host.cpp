@@ -227,7 +227,7 @@ int fhe_host_set_tuning(int key, int64_t value, int64_t* previous) {
     case FHE_TUNE_KARA_FORCE: old = t.kara_force; t.kara_force = value != 0; break;
     case FHE_TUNE_DIV_R16_LEAD: old = t.div_r16_lead; t.div_r16_lead = (uint32_t)std::max<int64_t>(0, value); break;
     case FHE_TUNE_FLUSH_DEPTH: old = t.flush_depth; t.flush_depth = (uint32_t)std::max<int64_t>(0, value); break;
-    case FHE_TUNE_FAULT_SITES: old = t.fault_sites; t.fault_sites = (uint32_t)std::max<int64_t>(0, value) & 31u; break;
+    case FHE_TUNE_FAULT_SITES: old = t.fault_sites; t.fault_sites = (uint32_t)std::max<int64_t>(0, value) & 63u; break;
     case FHE_TUNE_FAULT_AFTER:  // previous: the crossings of enabled sites since this key was last set
         old = (int64_t)t.fault_crossings;
         t.fault_crossings = 0;

@@ -75,11 +75,23 @@ std::vector<int64_t> read_blocks(fhe_ctx* c, const fhe_client_key* ck, const std
         }
         return vals;
     }
+    if (c->client_resident(ck)) {  // the phases on the device, 8 bytes per block back (Engine::phases_many)
+        std::vector<uint64_t> phases(enc.size());
+        c->engine->phases_many(enc, phases.data(), only_needed);
+        for (size_t i = 0; i < enc.size(); ++i) vals[i] = (int64_t)decode_block(ck->params, phases[i]);
+        return vals;
+    }
     std::vector<uint64_t> cts(enc.size() * kBigCt);
     c->engine->download_many(enc, cts.data(), only_needed);
     for (size_t i = 0; i < enc.size(); ++i)
         vals[i] = (int64_t)decode_block(ck->params, decrypt_phase_big(ck, cts.data() + i * kBigCt));
     return vals;
+}
+
+// the device path of a batch of client encryptions: taken when ck is the context's resident key and the batch
+// stays in the stream's counter epoch; otherwise false, and the caller's host path runs as ever
+bool encrypt_resident(fhe_ctx* c, fhe_client_key* ck, const std::vector<uint64_t>& pts, Blocks* out) {
+    return c->client_resident(ck) && c->engine->encrypt_resident(ck, pts.data(), pts.size(), out);
 }
 
 // nblocks client-encrypted blocks of the given 2-bit digits; a simulated context makes sim_blocks of them
@@ -89,8 +101,10 @@ Blocks encrypt_digits(fhe_ctx* c, fhe_client_key* ck, const std::vector<uint32_t
         for (uint32_t v : digits) out.push_back(c->engine->sim_block(v, 3));
         return out;
     }
-    std::vector<uint64_t> ct(digits.size() * kBigCt), pts(digits.size());
+    std::vector<uint64_t> pts(digits.size());
     for (size_t k = 0; k < digits.size(); ++k) pts[k] = (uint64_t)digits[k] * ck->params.delta();
+    if (encrypt_resident(c, ck, pts, &out)) return out;
+    std::vector<uint64_t> ct(digits.size() * kBigCt);
     encrypt_big_many(ck, pts.data(), pts.size(), ct.data());
     return c->engine->upload_many(ct.data(), digits.size(), 3);
 }
@@ -158,6 +172,9 @@ int biguint_encrypt_batch(fhe_ctx* c, fhe_client_key* ck, const std::vector<cons
         Blocks all;
         if (c->simulated) {  // shadowed blocks of the digits, at once: there is no encryption to overlap
             all = encrypt_digits(c, ck, digits);
+        } else if (encrypt_resident(c, ck, pts, &all)) {
+            // a resident client key: encrypted on the context's stream, nothing to hide behind a helper thread --
+            // none is started and no deferred upload is armed
         } else if (deferred) {
             // the encryption runs on a helper thread while the caller records the graph that reads the
             // blocks; the engine uploads them right before its next launch (Engine::upload_deferred)

@@ -150,6 +150,7 @@ fhe_ctx::~fhe_ctx() {
     }
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
+    (void)release_client_key();  // zeros over the resident secret before its memory goes back
     delete engine;
     release_comm();
     for (auto e : ev)
@@ -182,6 +183,13 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
     if (has_rekey) {  // nor a re-keying key
         const int rc = release_rekey();
         if (rc) return rc;
+    }
+    if (has_client) {  // a resident client key stays across a re-key to the same parameters only
+        uint32_t have = 0, want = 0;
+        if (params_differ(p, np, &have, &want)) {
+            const int rc = release_client_key();
+            if (rc) return rc;
+        }
     }
     if (d_ms) FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read it
     ms_cap = 0;

@@ -261,4 +261,20 @@ struct fhe_ctx {
     int rk_ms_stride = 0;
     int ensure_rk_ms(size_t count);
     int release_rekey();  // waits for the stream, frees all of the above
+
+    // Resident client key (fhe_ctx_set_client_key, client_ops.cpp): for a process that holds the
+    // client key anyway.  d_client = client_ops::kClientWords u32: the big secret key as 2048 packed bits, then the
+    // encryption stream's parameters of the call in flight (its key is as secret as the bits).  h_client is the
+    // host copy in the same layout, pinned so that the copies go from it directly.  Nothing points at the
+    // fhe_client_key the bits came from.  release_client_key overwrites both with zeros before it frees them; the
+    // destructor and an install of a server key with other parameters (adopt_key_params) go through it.
+    bool has_client = false;
+    fhe::DeviceBuf<uint32_t> d_client;
+    fhe::PinnedBuf<uint32_t> h_client;
+    uint64_t client_enc_blocks = 0, client_phase_blocks = 0;  // blocks that took each device path
+    // the device paths are taken only for the key whose packed bits are the resident ones
+    bool client_resident(const fhe_client_key* ck) const;
+    // the stream parameters of a call (the stream as it stands BEFORE the call's words) into h_client and d_client
+    hipError_t client_stage_stream(const fhe::ChaChaStream& at, uint32_t noise_log2);
+    int release_client_key();  // waits for the stream, wipes, frees
 };

@@ -59,6 +59,7 @@ enum : uint32_t {
     kFaultWorkspace = 4,  // before the bootstrap workspace is sized (device)
     kFaultDeferred = 8,   // first statement of upload_deferred's closure
     kFaultRecord = 16,    // the entry of Engine::run
+    kFaultClient = 32,    // encrypt_resident before it stages anything; phases_many after its flush, before its launch
 };
 void fault_cross(const char* site);
 inline void fault_point(uint32_t site, const char* name) {
@@ -317,6 +318,19 @@ public:
     // the rows are the destination key's: switched_row_bytes(rkp.n) bytes each.
     void switched_compress(const std::vector<const Block*>& blocks, uint8_t* rows, bool rekey = false);
     Blocks switched_decompress(const fhe_switched_list& x);
+    // Client-key encryption on the device under the context's resident key (client_ops.h; the caller
+    // has checked fhe_ctx::client_resident(ck)): n fresh slots (degree 3, noise 1, as upload_many's) filled by
+    // client_ops.hip with, word for word, what encrypt_big_many(ck, pts, n, ..) writes.  ck's stream is moved past
+    // the n encryptions first (encrypt_big_skip), then the kFaultClient site is crossed, then the slot pointers and
+    // the scaled plaintexts (16 B per block) and the stream's parameters are staged: a call that fails later leaves
+    // the stream where the host path's failed upload leaves it.  Stream-ordered like expand_seeded: no flush, a
+    // pending upload_deferred stays pending, no collective.  False, with nothing changed, if the batch leaves the
+    // stream's counter epoch: the caller takes the host path.
+    bool encrypt_resident(fhe_client_key* ck, const uint64_t* pts, size_t n, Blocks* out);
+    // The decryption phases body - <mask, key> of slot blocks under the resident key, one u64 per block: the same
+    // flush or flush_for as download_many, the kFaultClient site, the slot pointers staged, client_ops.hip's phase
+    // kernel, one copy of 8 n bytes, one wait.  Word for word decrypt_phase_big of the blocks' rows.
+    void phases_many(const std::vector<const Block*>& blocks, uint64_t* phases, bool only_needed = false);
     void download(const Block& b, uint64_t* ct);
     // the slot blocks' ciphertexts -> host, contiguous (one gather + one copy + one wait instead of a
     // round trip per block: the decryption of a 256-bit result is 128-144 blocks)

@@ -7,6 +7,7 @@
 //     hands back the typed device pointer and checks the total the operation asked staging() for;
 //   * blocks that are read are made real first (realize), a trivial one enters as the body trivial_body().
 #include "engine.h"
+#include "client_ops.h"
 #include "compress_kernels.h"
 #include "ct_digest.h"
 #include "keygen.h"
@@ -571,6 +572,51 @@ void Engine::download_many(const std::vector<const Block*>& blocks, uint64_t* ct
     hip_check(launch_gather_blocks(d_src, d_cts, (int)n, ctx_->stream), "download gather");
     hip_check(hipMemcpyAsync(cts, d_cts, n * kBigCt * 8, hipMemcpyDeviceToHost, ctx_->stream), "download");
     wait_check(ctx_, "download");
+}
+
+// ------------------------------------------------------------------ resident client key
+bool Engine::encrypt_resident(fhe_client_key* ck, const uint64_t* pts, size_t n, Blocks* out) {
+    engine_check(host_mode_ == kDevice, "encrypt_resident on a host-only engine");
+    engine_check(ctx_->has_client, "encrypt_resident without a resident client key");
+    out->clear();
+    if (n == 0) return true;
+    const ChaChaStream before = ck->enc_rng;
+    engine_check(before.word_pos() % 2 == 0, "encryption stream off a 64-bit word");
+    if (!encrypt_big_skip(ck, n)) return false;
+    fault_point(kFaultClient, "CLIENT");
+    const size_t words = 2 * n;  // the scaled plaintexts, then the slot pointers
+    Stage st(ctx_->stream, staging(words), words);
+    *out = fresh_blocks(n, 3);
+    const std::vector<uint64_t*> dst = slot_ptrs(*out);
+    const uint64_t* d_pts = st.put(pts, n, "client plaintexts");
+    uint64_t** d_dst = st.put(dst.data(), n, "client slots");
+    hip_check(ctx_->client_stage_stream(before, ck->params.glwe_noise_log2), "client stream parameters");
+    hip_check(launch_client_encrypt(ctx_->d_client, d_dst, d_pts, n, ctx_->stream), "client encryption");
+    hip_check(hipStreamSynchronize(ctx_->stream), "upload sync");  // host buffers may go, the staging be reused
+    ctx_->client_enc_blocks += n;
+    return true;
+}
+
+void Engine::phases_many(const std::vector<const Block*>& blocks, uint64_t* phases, bool only_needed) {
+    engine_check(host_mode_ == kDevice, "phases_many on a host-only engine");
+    engine_check(ctx_->has_client, "phases_many without a resident client key");
+    const size_t n = blocks.size();
+    if (n == 0) return;
+    check_owner(blocks);  // before the flush: a refusal leaves what is pending pending
+    if (only_needed)
+        flush_for(blocks);
+    else
+        flush();
+    fault_point(kFaultClient, "CLIENT");
+    const size_t words = 2 * n;  // the slot pointers, then the phases
+    Stage st(ctx_->stream, staging(words), words);
+    const std::vector<const uint64_t*> src = source_ptrs(*this, blocks, "decryption of a trivial or lazy block");
+    const uint64_t** d_src = st.put(src.data(), n, "phase slots");
+    uint64_t* d_ph = st.reserve<uint64_t>(n);
+    hip_check(launch_client_phase(ctx_->d_client, d_src, d_ph, n, ctx_->stream), "decryption phases");
+    hip_check(hipMemcpyAsync(phases, d_ph, n * 8, hipMemcpyDeviceToHost, ctx_->stream), "phase download");
+    wait_check(ctx_, "decryption phases");
+    ctx_->client_phase_blocks += n;
 }
 
 void Engine::sync() {

@@ -485,11 +485,32 @@ static void encrypt_with(ChaChaStream& rng, const fhe_client_key* ck, uint64_t p
 
 void encrypt_big(fhe_client_key* ck, uint64_t pt, uint64_t* ct) { encrypt_with(ck->enc_rng, ck, pt, ct); }
 
-void encrypt_big_many(fhe_client_key* ck, const uint64_t* pts, size_t n, uint64_t* cts) {
-    constexpr uint64_t kWords = 2 * (uint64_t)kBigCt;  // 32-bit stream words one encryption consumes
-    const uint64_t w0 = ck->enc_rng.word_pos();
+namespace {
+constexpr uint64_t kWords = 2 * (uint64_t)kBigCt;  // 32-bit stream words one encryption consumes
+// host threads of a batch encryption: >= 8 blocks (16 KB of stream each) per thread
+size_t encrypt_threads(size_t n) {
     const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-    const size_t T = std::min<size_t>(std::min<size_t>(hw, 16), n / 8);  // >= 8 blocks (16 KB of stream each) per thread
+    return std::min<size_t>(std::min<size_t>(hw, 16), n / 8);
+}
+}  // namespace
+
+bool encrypt_big_skip(fhe_client_key* ck, size_t n) {
+    if (n == 0) return true;
+    const uint64_t end = ck->enc_rng.word_pos() + kWords * n;
+    ChaChaStream probe = ck->enc_rng;
+    if (!probe.seek(end)) return false;
+    if (encrypt_threads(n) <= 1) {
+        // the word-by-word path ends on the block of its last word, buffered: draw that word again
+        probe.seek(end - 2);
+        (void)probe.next_u64();
+    }
+    ck->enc_rng = probe;
+    return true;
+}
+
+void encrypt_big_many(fhe_client_key* ck, const uint64_t* pts, size_t n, uint64_t* cts) {
+    const uint64_t w0 = ck->enc_rng.word_pos();
+    const size_t T = encrypt_threads(n);
     ChaChaStream probe = ck->enc_rng;
     if (T <= 1 || !probe.seek(w0 + kWords * n)) {
         for (size_t i = 0; i < n; ++i) encrypt_with(ck->enc_rng, ck, pts[i], cts + i * kBigCt);

@@ -75,6 +75,10 @@ public:
     // batch run in parallel on copies of the stream with exactly the sequential outputs
     uint64_t word_pos() const { return (uint64_t)counter_ * 16 - (16 - pos_); }
     bool seek(uint64_t word);
+    // the key and nonce of the current epoch: with word_pos() all a device restatement of the stream needs
+    // (client_ops.hip); secret where the stream's key is
+    const std::array<uint32_t, 8>& key_words() const { return key_; }
+    const std::array<uint32_t, 3>& nonce_words() const { return nonce_; }
     // full state (key, nonce, counter, buffered block, position) for serialization (serial.cpp)
     static constexpr size_t kStateWords = 8 + 3 + 1 + 16 + 1;
     void save(uint32_t* out) const;
@@ -220,6 +224,10 @@ void encrypt_big(fhe_client_key* ck, uint64_t plaintext, uint64_t* ct);
 // n encryptions (plaintexts already scaled), outputs and stream state identical to n encrypt_big
 // calls; large batches run on several host threads over seeked copies of the stream
 void encrypt_big_many(fhe_client_key* ck, const uint64_t* plaintexts, size_t n, uint64_t* cts);
+// The stream state encrypt_big_many(ck, .., n, ..) leaves, without drawing its words: ck->enc_rng stands after the
+// n-th encryption, byte for byte (buffered block included) as that call would leave it on this host.  False, and
+// nothing changed, if the batch leaves the stream's counter epoch (encrypt_big_many then runs word by word).
+bool encrypt_big_skip(fhe_client_key* ck, size_t n);
 // Seeded encryption of n scaled plaintexts: bodies[i] as in fhe_seeded, masks from the PUBLIC `seed`
 // (32 bytes), noise e_i = tuniform_of(w_i, glwe_noise_log2) with w_i the next u64 of ck->enc_rng -- exactly
 // one stream word per block, in block order, whatever the number of host threads.  n <= kSeededMaxBlocks

@@ -38,7 +38,7 @@ All ciphertext arithmetic runs on the GPU through lib/libfhe_rocm.so; this packa
 from ._lib import CompressionParams, FheError, FheParams, load  # noqa: F401
 from .core import (ClientKey, RekeyKey, CompactPublicKey, CompressedCompressionKey, CompressedServerKey, CompressionKey, CompressionKeys, CompressionPrivateKey, Context, ServerKey, comm_unique_id, default_params,  # noqa: F401
                    default_compression_params, generate_keys, ms_center_host, ms_stride, multi_bit_params, oprf_lut_host, oprf_rows_host, tuning, fault_arm, FAULT_LEVEL, FAULT_STAGE,
-                   FAULT_WORKSPACE, FAULT_DEFERRED, FAULT_RECORD, FAULT_ALL,
+                   FAULT_WORKSPACE, FAULT_DEFERRED, FAULT_RECORD, FAULT_CLIENT, FAULT_ALL,
                    switched_pack_host, switched_row_bytes, switched_unpack_host, SimContext, SimKey, noise_audit)
 from .integer import (  # noqa: F401,E402
     COMPAT, FAST, PUBLIC, BigUintFHE, FheBool, FheUint, FheUint8, FheUint32, FheUint64, FheUint128, FheUint256, set_server_key,

@@ -392,6 +392,14 @@ _SIGNATURES = [
     ("fhe_schnorr_eval_s_public", C.c_int, [C.c_void_p, u8p, u8p, C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fhe_schnorr_sign_fhe", C.c_int, [C.c_void_p, C.c_void_p, u8p, C.c_size_t, u8p, u8p, C.c_int, u8p]),
     ("fhe_schnorr_verify", C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, u8p, C.c_size_t]),
+    ("fhe_ctx_set_client_key", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fhe_ctx_clear_client_key", C.c_int, [C.c_void_p]),
+    ("fhe_ctx_client_ops_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int), u64p, u64p]),
+    ("fhe_client_encrypt_rows_indexed_host", C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
+    ("fhe_decrypt_phase_host", C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
+    ("fhe_client_encrypt_rows", C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_size_t, u64p]),
+    ("fhe_client_phase_rows", C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
+    ("fhe_ctx_time_client_ops", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 ]
 
 _lib = None

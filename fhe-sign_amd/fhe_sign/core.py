@@ -78,6 +78,21 @@ class ClientKey:
         check(load().fhe_decrypt_block(self._h, ptr(ct), C.byref(out)))
         return int(out.value)
 
+    def encrypt_rows_indexed_host(self, values) -> np.ndarray:
+        """host definition (fhe_client_encrypt_rows_indexed_host): encrypt_blocks restated from counter-indexed
+        ChaCha blocks through the device kernel's index arithmetic; same words, same stream state afterwards"""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.uint64))
+        out = np.zeros((v.size, BIG_CT), np.uint64)
+        check(load().fhe_client_encrypt_rows_indexed_host(self._h, ptr(v), v.size, ptr(out)))
+        return out
+
+    def decrypt_phase_host(self, cts) -> np.ndarray:
+        """host definition (fhe_decrypt_phase_host): body - <mask, key> of every row, the word decrypt_block decodes"""
+        cts = np.ascontiguousarray(np.asarray(cts, dtype=np.uint64).reshape(-1, BIG_CT))
+        out = np.zeros(cts.shape[0], np.uint64)
+        check(load().fhe_decrypt_phase_host(self._h, ptr(cts), cts.shape[0], ptr(out)))
+        return out
+
 
 class ServerKey:
     def __init__(self, handle, params: FheParams):
@@ -776,6 +791,44 @@ class Context:
         check(load().fhe_ctx_time_switched(self._h, int(count), int(n), int(reps), C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
+    def set_client_key(self, ck: "ClientKey") -> None:
+        """after set_server_key, for a process that holds the client key anyway (fhe_ctx_set_client_key): the big
+        secret key's 2048 bits become resident on the GPU, and encryptions and decryptions that pass this key run
+        there.  A server that only evaluates never calls it."""
+        check(load().fhe_ctx_set_client_key(self._h, ck.handle))
+
+    def clear_client_key(self) -> None:
+        """zeros over the resident key's device and host copies, then frees them (fhe_ctx_clear_client_key)"""
+        check(load().fhe_ctx_clear_client_key(self._h))
+
+    def client_ops_info(self):
+        """(a key is resident, blocks encrypted on the device path, blocks whose phase was taken there)"""
+        r, a, b = C.c_int(), C.c_uint64(), C.c_uint64()
+        check(load().fhe_ctx_client_ops_info(self._h, C.byref(r), C.byref(a), C.byref(b)))
+        return bool(r.value), int(a.value), int(b.value)
+
+    def client_encrypt_rows(self, ck: "ClientKey", values) -> np.ndarray:
+        """test hook (fhe_client_encrypt_rows): the encryption kernel into scratch rows under the resident key,
+        returned as ClientKey.encrypt_blocks returns its rows; ck's stream advances the same way"""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.uint64))
+        out = np.zeros((v.size, BIG_CT), np.uint64)
+        check(load().fhe_client_encrypt_rows(self._h, ck.handle, ptr(v), v.size, ptr(out)))
+        return out
+
+    def client_phase_rows(self, cts) -> np.ndarray:
+        """test hook (fhe_client_phase_rows): the phase kernel over a scratch copy of the rows"""
+        cts = np.ascontiguousarray(np.asarray(cts, dtype=np.uint64).reshape(-1, BIG_CT))
+        out = np.zeros(cts.shape[0], np.uint64)
+        check(load().fhe_client_phase_rows(self._h, ptr(cts), cts.shape[0], ptr(out)))
+        return out
+
+    def time_client_ops(self, count: int, iters: int = 30):
+        """measurement hook (fhe_ctx_time_client_ops): mean ms of one encryption and of one phase kernel launch
+        over count scratch rows"""
+        a, b = C.c_float(), C.c_float()
+        check(load().fhe_ctx_time_client_ops(self._h, int(count), int(iters), C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     def set_wide_threshold(self, threshold: int) -> None:
         check(load().fhe_ctx_set_wide_threshold(self._h, int(threshold)))
 
@@ -863,8 +916,8 @@ def noise_audit(ctx: Context, reset: bool = False):
 TUNE_KEYS = {"kara_min": 1, "kara_compat_min": 2, "kara_force": 3, "div_r16_lead": 4, "scalar_div_residue": 5,
              "flush_depth": 6}
 FAULT_SITES_KEY, FAULT_AFTER_KEY = 7, 8
-FAULT_LEVEL, FAULT_STAGE, FAULT_WORKSPACE, FAULT_DEFERRED, FAULT_RECORD = 1, 2, 4, 8, 16
-FAULT_ALL = 31
+FAULT_LEVEL, FAULT_STAGE, FAULT_WORKSPACE, FAULT_DEFERRED, FAULT_RECORD, FAULT_CLIENT = 1, 2, 4, 8, 16, 32
+FAULT_ALL = 63
 
 
 def fault_arm(sites: int, after: int = 0) -> int:

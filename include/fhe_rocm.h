@@ -560,6 +560,7 @@ int fhe_host_biguint_mul_fingerprint(size_t la, size_t lb, size_t lk, int mode, 
 #define FHE_FAULT_WORKSPACE 4  /* before a flush sizes the bootstrap workspace (device contexts) */
 #define FHE_FAULT_DEFERRED 8   /* first statement of a deferred upload (the signer's e and k), before its data is taken */
 #define FHE_FAULT_RECORD 16    /* the entry of the engine's recording call: an op fails before it records */
+#define FHE_FAULT_CLIENT 32    /* resident client key: an encryption before it stages anything, a decryption after its flush and before its launch */
 int fhe_host_set_tuning(int key, int64_t value, int64_t* previous);
 int fhe_host_biguint_mul_stats(size_t la, size_t lb, size_t lk, int mode, uint64_t* pbs, uint64_t* levels,
                                uint32_t* level_sizes, size_t cap);
@@ -1392,6 +1393,51 @@ int fhe_schnorr_sign_fhe(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, s
 /* Schnorr::verify (src/schnorr.rs:301-347): 1 valid, 0 invalid */
 int fhe_schnorr_verify(const uint8_t* msg, size_t msg_len, const uint8_t* pubkey, size_t pubkey_len,
                        const uint8_t* sig, size_t sig_len);
+
+/* ---- resident client key: encryption and decryption on the GPU ----
+ *
+ * For a process that holds the client key ANYWAY, as the reference's signer does (sign_fhe_with_k0 takes the
+ * client key, encrypts e and k with it and decrypts the sum).  A server that only evaluates never calls this: it
+ * has no client key, and nothing here gives it one.
+ *
+ * fhe_ctx_set_client_key copies the big secret key, as 2048 packed bits, to the device and keeps a host copy of
+ * those bits; it keeps no pointer to ck.  It is the opt-in: with no key resident every path is byte for byte what
+ * it is without this section.  With one, every call that takes a client key still takes it, and goes to the device
+ * only when ck's packed key bits equal the resident ones:
+ *   - fhe_radix_encrypt, fhe_biguint_encrypt and the signers' encryptions of e and k: only the scaled plaintexts,
+ *     the slot pointers (16 B per block) and the encryption stream's key, nonce and position go up; the masks are
+ *     generated, and the bodies computed, on the context's stream -- word for word fhe_encrypt_blocks' rows, and
+ *     ck's encryption stream stands afterwards where the host path leaves it.  The signers start no helper thread
+ *     and arm no deferred upload in this case.
+ *   - fhe_radix_decrypt, fhe_biguint_decrypt, fhe_columns_decrypt and the signers' last step: body - <mask, key>
+ *     is computed on the device and 8 bytes per block come back; the decoding stays on the host.
+ * With another key (or a batch that would leave the stream's 32-bit block counter) the host path runs, as without
+ * a resident key: same words, no error.  The seeded, compact, compressed and stored client paths take no context
+ * and do not change.  Under a communicator every rank installs the key itself.
+ * Errors: FHE_ERR_INVALID for a NULL argument, a simulated context, or a client key whose parameters differ from
+ * the installed server key's; FHE_ERR_NO_KEY without a server key.
+ * fhe_ctx_clear_client_key overwrites the device copy and the host copy with zeros, then frees them (FHE_OK when
+ * none is resident); fhe_ctx_destroy and an install of a server key with other parameters do the same. */
+int fhe_ctx_set_client_key(fhe_ctx* ctx, const fhe_client_key* ck);
+int fhe_ctx_clear_client_key(fhe_ctx* ctx);
+/* *resident: 1 while a key is resident; the blocks that took the device encryption / the device phase path
+ * since the context was made */
+int fhe_ctx_client_ops_info(fhe_ctx* ctx, int* resident, uint64_t* enc_blocks, uint64_t* phase_blocks);
+/* HOST DEFINITIONS (no context, no GPU).  fhe_client_encrypt_rows_indexed_host: fhe_encrypt_blocks restated from
+ * counter-indexed ChaCha blocks through the index arithmetic the kernel uses (csrc/client_ops_index.h) -- the same
+ * n x 2049 words and the same stream state afterwards.  fhe_decrypt_phase_host: phases[i] = body - <mask, key> of
+ * row i, the word fhe_decrypt_block decodes. */
+int fhe_client_encrypt_rows_indexed_host(fhe_client_key* ck, const uint64_t* values, size_t n, uint64_t* cts);
+int fhe_decrypt_phase_host(const fhe_client_key* ck, const uint64_t* cts, size_t n, uint64_t* phases);
+/* TEST HOOKS: the two kernels over scratch rows under the resident key (FHE_ERR_NO_KEY without one).
+ * fhe_client_encrypt_rows: n rows of 2049 words for the block values, downloaded; ck must be the resident key
+ * (FHE_ERR_INVALID otherwise) and its stream advances as fhe_encrypt_blocks'.  fhe_client_phase_rows: the phases
+ * of n uploaded rows.  At most 2^20 rows. */
+int fhe_client_encrypt_rows(fhe_ctx* ctx, fhe_client_key* ck, const uint64_t* values, size_t n, uint64_t* cts);
+int fhe_client_phase_rows(fhe_ctx* ctx, const uint64_t* cts, size_t n, uint64_t* phases);
+/* MEASUREMENT HOOK: mean ms of one launch of each kernel over n scratch rows, `iters` launches each, under a fixed
+ * public key of its own (needs no installed key) */
+int fhe_ctx_time_client_ops(fhe_ctx* ctx, size_t n, uint32_t iters, float* enc_ms, float* phase_ms);
 
 #ifdef __cplusplus
 }
