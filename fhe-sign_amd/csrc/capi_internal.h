@@ -1,7 +1,9 @@
-// capi_internal.h -- what the C-API files of the radix layer share (capi_radix.cpp: the device entry points,
-// capi_host.cpp: the host-only hooks).  Private to csrc/.
+// capi_internal.h -- what the files that define C entry points share: the handle types and ownership checks of
+// the radix layer (capi_radix.cpp: the device entry points, capi_host.cpp: the host-only hooks), and the two
+// exception guards and invalid() that every such file uses.  Private to csrc/.
 #pragma once
 #include <exception>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -35,6 +37,26 @@ int guarded(F&& f) {
         set_error(e.what());
         return FHE_ERR_INVALID;
     }
+}
+
+// The entry points outside the radix layer (keys, lists, hooks): an allocation that fails is FHE_ERR_ALLOC there.
+// Kept apart from guarded(): a radix entry point answers FHE_ERR_INVALID on bad_alloc, and keeps doing so.
+template <class F>
+int guarded_alloc(F&& f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        set_error("out of memory");
+        return FHE_ERR_ALLOC;
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return FHE_ERR_INVALID;
+    }
+}
+
+inline int invalid(const std::string& why) {
+    set_error(why);
+    return FHE_ERR_INVALID;
 }
 
 // Ownership at the C boundary (Engine::check_owner): every entry point that takes a context and a handle asks

@@ -1124,10 +1124,6 @@ int fhe_biguint_deserialize(fhe_ctx* c, const uint8_t* buf, size_t len, fhe_bigu
 // are regenerated at expansion, on the host (expand_seeded_host) or on the GPU (Engine::expand_seeded).
 // Payload of ser::kSeeded: params, u32 form, u32 count, 32 seed bytes, nblocks u64 bodies.
 namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
 // blocks of a form/count pair; false if the pair is malformed or exceeds the ChaCha counter range
 bool seeded_nblocks(uint32_t form, uint32_t count, size_t* nblocks, std::string* why) {
     if (form == FHE_SEEDED_RADIX) {

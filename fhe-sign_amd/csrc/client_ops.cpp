@@ -10,6 +10,7 @@
 #include "client_ops.h"
 #include "client_ops_index.h"
 #include "engine.h"
+#include "capi_internal.h"
 
 namespace fhe {
 
@@ -143,10 +144,6 @@ int fhe_ctx::release_client_key() {
 }
 
 namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
 int no_key(const char* why) {
     set_error(why);
     return FHE_ERR_NO_KEY;
@@ -174,13 +171,8 @@ constexpr size_t kMaxHookRows = (size_t)1 << 20;
 extern "C" {
 
 int fhe_ctx_set_client_key(fhe_ctx* c, const fhe_client_key* ck) {
-    if (const int sim = refuse_simulated(c, "fhe_ctx_set_client_key")) return sim;
-    if (!c || !ck) return invalid("null argument to fhe_ctx_set_client_key");
-    if (!c->has_key || !c->engine) return no_key("no server key installed: fhe_ctx_set_client_key comes after fhe_set_server_key");
-    uint32_t have = 0, want = 0;
-    if (const char* f = params_differ(ck->params, c->p, &have, &want))
-        return invalid(std::string("client key's ") + f + " (" + std::to_string(have) + ") differs from the context's server key (" +
-                       std::to_string(want) + ")");
+    if (const int rc = dependent_key_preamble(c, ck != nullptr, "fhe_ctx_set_client_key", ck ? &ck->params : nullptr, "client key"))
+        return rc;
     if (ck->glwe_sk.size() != kMaskWords) return invalid("client key: the big secret key is not 2048 bits");
     FHE_HIP_CHECK(hipSetDevice(c->device));
     int rc = c->release_client_key();

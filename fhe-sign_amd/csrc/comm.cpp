@@ -157,10 +157,10 @@ int comm_wait(fhe_ctx* c, const char* what) { return c->wait_stream(what); }
 }  // namespace
 
 int fhe_ctx::ensure_gather(size_t n) {
-    if (d_gather.fits(n * 2049)) return FHE_OK;
+    if (gather_cap.fits(n)) return FHE_OK;
     FHE_HIP_CHECK(hipSetDevice(device));
     FHE_HIP_CHECK(hipStreamSynchronize(stream));  // a previous level may still read it
-    FHE_HIP_CHECK(d_gather.grow(std::max<size_t>(n, 4096) * 2049));
+    FHE_HIP_CHECK(gather_cap.regrow(n, 4096, [&](size_t cap) { return d_gather.grow(cap * 2049); }));
     return FHE_OK;
 }
 
@@ -608,23 +608,17 @@ int fhe_ctx_broadcast_server_key(fhe_ctx* c, int root) {
     const size_t ksk_words = (size_t)kBigDim * p.ks_level * (p.n + 1);
     const int npoly = (int)(p.ggsw_count() * 4);
     const size_t bsk_doubles = (size_t)npoly * 1024 * 2;
-    // Receivers: the new key lands in fresh buffers; the installed key (if any) stays in place and
+    // Receivers: the new key lands in a fresh set; the installed key (if any) stays in place and
     // usable until every collective and conversion has succeeded, then the two are swapped.
-    DeviceBuf<uint64_t> n_ksk;
-    DeviceBuf<int8_t> n_planes;
-    DeviceBuf<double2> n_bsk, n_e;
+    ServerKeySet nk;
     auto drop_new = [&] {
         (void)hipStreamSynchronize(c->stream);
-        (void)n_ksk.reset();
-        (void)n_planes.reset();
-        (void)n_bsk.reset();
-        (void)n_e.reset();
+        nk.drop();
+        return (int)FHE_OK;
     };
     if (!is_root && local_ok) {
-        hipError_t he = n_ksk.grow(ksk_words);
-        if (he == hipSuccess) he = n_planes.grow(fhe::ks_planes_bytes((int)p.n));
-        if (he == hipSuccess) he = n_bsk.grow(bsk_doubles / 2);
-        if (he == hipSuccess) he = n_e.grow(bsk_doubles / 2);
+        hipError_t he = nk.ks.size((int)p.n, (int)p.ks_level);
+        if (he == hipSuccess) he = nk.br.size((int)p.n, (int)p.grouping, npoly);
         if (he != hipSuccess) {
             drop_new();
             local_ok = 0;
@@ -639,8 +633,9 @@ int fhe_ctx_broadcast_server_key(fhe_ctx* c, int root) {
         set_error(local_ok ? std::string("broadcast_server_key: another rank could not take the key") : local_why);
         return local_ok ? FHE_ERR_INVALID : FHE_ERR_ALLOC;
     }
-    uint64_t* ksk_buf = is_root ? c->d_ksk : n_ksk;
-    double2* bsk_buf = is_root ? c->d_bsk : n_bsk;
+    const ServerKeySet& from = is_root ? c->key : nk;
+    uint64_t* ksk_buf = from.ks.ksk;
+    double2* bsk_buf = from.br.bsk;
     if (c->has_tx) {
         rc = tx_bcast_device(c, ksk_buf, ksk_words * 8, root);
         if (!rc) rc = tx_bcast_device(c, bsk_buf, bsk_doubles * 8, root);
@@ -658,29 +653,16 @@ int fhe_ctx_broadcast_server_key(fhe_ctx* c, int root) {
         if (rc) drop_new();
         return rc;
     }
-    rc = launch_ksk_to_planes(n_ksk, (int)p.n, n_planes, c->stream) == hipSuccess ? FHE_OK : FHE_ERR_HIP;
-    if (!rc) rc = launch_bsk_to_e(n_bsk, npoly, n_e, c->stream) == hipSuccess ? FHE_OK : FHE_ERR_HIP;
-    if (!rc) rc = hipStreamSynchronize(c->stream) == hipSuccess ? FHE_OK : FHE_ERR_HIP;
-    if (rc) {
-        drop_new();
-        return rc;
-    }
-    if (!c->engine) {
-        try {
-            c->engine = new fhe::Engine(c);
-        } catch (const std::exception& ex) {
-            drop_new();
-            set_error(ex.what());
-            return FHE_ERR_HIP;
-        }
-    }
-    // commit: swap in the new key, release the old one
-    c->d_ksk.swap(n_ksk);
-    c->d_ksk_planes.swap(n_planes);
-    c->d_bsk.swap(n_bsk);
-    c->d_bsk_e.swap(n_e);
-    drop_new();  // frees the previous key's buffers (null when there was none)
-    return c->adopt_key_params(p, c->has_key);
+    // the collectives were the fill: the rest is the install outline, committing by a swap
+    return install_key(
+        c, nk, [] { return (int)FHE_OK; },
+        [&]() -> int {
+            if (const int e = c->ensure_engine()) return e;
+            std::swap(c->key, nk);
+            drop_new();  // frees the previous key's buffers (none when there was no key)
+            return c->adopt_key_params(p, c->has_key);
+        },
+        drop_new);
 }
 
 int fhe_ctx_set_fanout(fhe_ctx* c, uint32_t min_level, int emulate_ranks) {

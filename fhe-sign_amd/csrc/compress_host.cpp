@@ -10,6 +10,7 @@
 #include "context.h"
 #include "fhe_rocm.h"
 #include "serial.h"
+#include "capi_internal.h"
 
 namespace fhe {
 
@@ -315,22 +316,6 @@ void pack_keyswitch_host(const fhe_compression_key& key, const uint64_t* cts, si
 using namespace fhe;
 
 namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
-template <class F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        set_error("out of memory");
-        return FHE_ERR_ALLOC;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return FHE_ERR_INVALID;
-    }
-}
 void write_cp(ser::Writer& w, const CompParams& c) {
     for (uint32_t v : {c.k, c.N, c.L, c.beta, c.ell, c.pks_noise_log2, c.storage_log_modulus}) w.u32(v);
 }
@@ -378,7 +363,7 @@ int fhe_compression_keys_generate(fhe_client_key* ck, const fhe_compression_para
         set_error(why);
         return FHE_ERR_UNSUPPORTED;
     }
-    return guarded([&] {
+    return guarded_alloc([&] {
         auto a = std::make_unique<fhe_compression_private_key>();
         auto b = std::make_unique<fhe_compression_key>();
         generate_compression_keys(ck, cp, a.get(), b.get());
@@ -424,7 +409,7 @@ void fhe_compression_key_destroy(fhe_compression_key* key) { delete key; }
 int fhe_compression_private_key_serialize(const fhe_compression_private_key* priv, uint8_t* buf, size_t cap,
                                           size_t* len) {
     if (!priv || !len) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Writer w;
         w.params(priv->params);
         write_cp(w, priv->cp);
@@ -435,7 +420,7 @@ int fhe_compression_private_key_serialize(const fhe_compression_private_key* pri
 
 int fhe_compression_private_key_deserialize(const uint8_t* buf, size_t len, fhe_compression_private_key** out) {
     if (!out) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Reader r;
         std::string why;
         Params p;
@@ -458,7 +443,7 @@ int fhe_compression_private_key_deserialize(const uint8_t* buf, size_t len, fhe_
 
 int fhe_compression_key_serialize(const fhe_compression_key* key, uint8_t* buf, size_t cap, size_t* len) {
     if (!key || !len) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Writer w;
         w.b.reserve(80 + (key->pksk.size() + key->bsk.size()) * 8);
         w.params(key->params);
@@ -471,7 +456,7 @@ int fhe_compression_key_serialize(const fhe_compression_key* key, uint8_t* buf, 
 
 int fhe_compression_key_deserialize(const uint8_t* buf, size_t len, fhe_compression_key** out) {
     if (!out) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Reader r;
         std::string why;
         Params p;
@@ -513,7 +498,7 @@ int fhe_compression_keys_generate_seeded(fhe_client_key* ck, const fhe_compressi
         set_error("getrandom failed: no mask seed");
         return FHE_ERR_UNSUPPORTED;
     }
-    return guarded([&] {
+    return guarded_alloc([&] {
         auto a = std::make_unique<fhe_compression_private_key>();
         auto b = std::make_unique<fhe_seeded_compression_key>();
         generate_seeded_compression_keys(ck, cp, seed, a.get(), b.get());
@@ -534,7 +519,7 @@ int fhe_seeded_compression_key_params(const fhe_seeded_compression_key* sck, fhe
 int fhe_seeded_compression_key_serialize(const fhe_seeded_compression_key* sck, uint8_t* buf, size_t cap,
                                          size_t* len) {
     if (!sck || !len) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Writer w;
         w.b.reserve(112 + (sck->pksk_bodies.size() + sck->bsk_bodies.size()) * 8);
         w.params(sck->params);
@@ -548,7 +533,7 @@ int fhe_seeded_compression_key_serialize(const fhe_seeded_compression_key* sck, 
 
 int fhe_seeded_compression_key_deserialize(const uint8_t* buf, size_t len, fhe_seeded_compression_key** out) {
     if (!out) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Reader r;
         std::string why;
         Params p;
@@ -576,7 +561,7 @@ int fhe_seeded_compression_key_expand_host(const fhe_seeded_compression_key* sck
     if (!sck || !out) return invalid("null argument");
     if (sck->pksk_bodies.size() != sck->cp.pksk_body_words() || sck->bsk_bodies.size() != sck->cp.bsk_body_words())
         return invalid("seeded compression key: body counts differ from what its parameters need");
-    return guarded([&] {
+    return guarded_alloc([&] {
         auto k = std::make_unique<fhe_compression_key>();
         expand_seeded_compression_key_host(*sck, k.get());
         *out = k.release();
@@ -595,7 +580,7 @@ int fhe_compress_host(const fhe_compression_key* key, const uint64_t* cts, size_
     if (want != nblocks) return invalid("fhe_compress_host: nblocks does not match form / count");
     for (size_t i = 0; i < nblocks; ++i)
         if (degrees[i] >= 16) return invalid("fhe_compress_host: block degree >= 16");
-    return guarded([&] {
+    return guarded_alloc([&] {
         auto x = std::make_unique<fhe_compressed_list>();
         x->params = key->params;
         x->cp = key->cp;
@@ -626,7 +611,7 @@ int fhe_compressed_params(const fhe_compressed_list* x, fhe_params* main, fhe_co
 
 int fhe_compressed_serialize(const fhe_compressed_list* x, uint8_t* buf, size_t cap, size_t* len) {
     if (!x || !len) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Writer w;
         w.b.reserve(96 + x->degrees.size() + x->packed.size());
         w.params(x->params);
@@ -642,7 +627,7 @@ int fhe_compressed_serialize(const fhe_compressed_list* x, uint8_t* buf, size_t 
 
 int fhe_compressed_deserialize(const uint8_t* buf, size_t len, fhe_compressed_list** out) {
     if (!out) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Reader r;
         std::string why;
         Params p;
@@ -687,7 +672,7 @@ int fhe_compressed_decrypt(const fhe_compression_private_key* priv, const fhe_co
     const size_t B = x->degrees.size();
     const uint32_t bits = x->form == FHE_SEEDED_RADIX ? x->count : 32 * x->count;
     if ((uint64_t)nwords * 64 < bits) return invalid("fhe_compressed_decrypt: output too small");
-    return guarded([&] {
+    return guarded_alloc([&] {
         const CompParams& cp = x->cp;
         const uint32_t Np = cp.N, kN = cp.lwe_dim();
         std::vector<uint32_t> vals(B);

@@ -160,18 +160,14 @@ fhe_ctx::~fhe_ctx() {
     if (stream) (void)hipStreamDestroy(stream);
 }
 
-int fhe_ctx::ensure_ms(size_t count) {
-    if (count <= ms_cap) return FHE_OK;
-    if (d_ms) FHE_HIP_CHECK(hipStreamSynchronize(stream));  // previous levels may still read it
-    ms_cap = 0;
-    size_t cap = count < 256 ? 256 : count;
-    ms_stride = (int)((p.n + 1 + 7) / 8 * 8);
-    FHE_HIP_CHECK(d_ms.grow(cap * ms_stride));
-    ms_cap = cap;
+int fhe_ctx::ensure_rows(RowSpace& rs, size_t n, size_t count) {
+    if (rs.fits(count)) return FHE_OK;
+    FHE_HIP_CHECK(hipStreamSynchronize(stream));  // previous levels may still read the rows
+    FHE_HIP_CHECK(rs.regrow(count, n));
     return FHE_OK;
 }
 
-int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
+int fhe_ctx::release_dependants() {
     if (has_comp) {  // a compression key does not outlive the server key it was installed after
         const int rc = release_compression();
         if (rc) return rc;
@@ -184,6 +180,22 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
         const int rc = release_rekey();
         if (rc) return rc;
     }
+    return FHE_OK;
+}
+
+int fhe_ctx::ensure_engine() {
+    if (engine) return FHE_OK;
+    try {
+        engine = new fhe::Engine(this);
+    } catch (const std::exception& ex) {
+        set_error(ex.what());
+        return FHE_ERR_HIP;
+    }
+    return FHE_OK;
+}
+
+int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
+    if (const int rc = release_dependants()) return rc;
     if (has_client) {  // a resident client key stays across a re-key to the same parameters only
         uint32_t have = 0, want = 0;
         if (params_differ(p, np, &have, &want)) {
@@ -191,10 +203,8 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
             if (rc) return rc;
         }
     }
-    if (d_ms) FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read it
-    ms_cap = 0;
-    FHE_HIP_CHECK(d_ms.reset());
-    ms_stride = 0;
+    if (rows.rows()) FHE_HIP_CHECK(hipStreamSynchronize(stream));  // levels of the previous key may still read them
+    FHE_HIP_CHECK(rows.drop());
     if (!had_key || !(p.msg_carry() == np.msg_carry() && p.delta() == np.delta())) {
         lut_ids.clear();
         h_luts.clear();
@@ -207,59 +217,46 @@ int fhe_ctx::adopt_key_params(const Params& np, bool had_key) {
 
 int fhe_ctx::release_compression() {
     if (stream) FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    pk_cap = cms_cap = 0;
+    pk_cap.drop();
     (void)d_pk_planes.reset();
-    (void)d_cbsk.reset();
-    (void)d_cbsk_e.reset();
+    comp_br.drop();
     (void)d_pk_src.reset();
     (void)d_pk_digits.reset();
     (void)d_pk_body.reset();
     (void)d_pk_P.reset();
     (void)d_pk_out.reset();
-    (void)d_cms.reset();
+    (void)comp_rows.drop();
     (void)d_cpacked.reset();
     (void)d_cdesc.reset();
-    cms_stride = 0;
     has_comp = false;
     return FHE_OK;
 }
 
 int fhe_ctx::ensure_pk(size_t count) {
-    if (count <= pk_cap) return FHE_OK;
+    if (pk_cap.fits(count)) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    pk_cap = 0;
-    const size_t cap = std::max<size_t>(count, 256);
-    FHE_HIP_CHECK(d_pk_src.grow(cap));
-    FHE_HIP_CHECK(d_pk_digits.grow(fhe::pk_digits_bytes((int)cap, (int)cp.ell)));
-    FHE_HIP_CHECK(d_pk_body.grow(cap));
-    FHE_HIP_CHECK(d_pk_P.grow(cap * cp.cols()));
-    FHE_HIP_CHECK(d_pk_out.grow(cp.glwes(cap) * (size_t)fhe::pk_out_stride((int)cp.k, (int)cp.N)));
-    pk_cap = cap;
+    FHE_HIP_CHECK(pk_cap.regrow(count, 256, [&](size_t cap) {
+        return grow_each(d_pk_src, cap, d_pk_digits, fhe::pk_digits_bytes((int)cap, (int)cp.ell), d_pk_body, cap, d_pk_P,
+                         cap * cp.cols(), d_pk_out, cp.glwes(cap) * (size_t)fhe::pk_out_stride((int)cp.k, (int)cp.N));
+    }));
     return FHE_OK;
 }
 
 int fhe_ctx::ensure_cms(size_t count) {
-    if (count <= cms_cap) return FHE_OK;
+    if (comp_rows.fits(count)) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    cms_cap = 0;
-    const size_t cap = std::max<size_t>(count, 256);
-    cms_stride = (int)((cp.lwe_dim() + 1 + 7) / 8 * 8);
-    FHE_HIP_CHECK(d_cms.grow(cap * cms_stride));
-    FHE_HIP_CHECK(d_cpacked.grow(cp.glwes(cap) * cp.glwe_bytes(cp.L)));
-    FHE_HIP_CHECK(d_cdesc.grow(cap));
-    cms_cap = cap;
+    FHE_HIP_CHECK(comp_rows.regrow(count, (size_t)comp_br.n, [&](size_t cap) {
+        return grow_each(d_cpacked, cp.glwes(cap) * cp.glwe_bytes(cp.L), d_cdesc, cap);
+    }));
     return FHE_OK;
 }
 
 int fhe_ctx::ensure_stage(size_t count) {
-    if (count <= stage_cap) return FHE_OK;
+    if (stage_cap.fits(count)) return FHE_OK;
     FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    stage_cap = 0;
-    size_t cap = count < 256 ? 256 : count;
-    FHE_HIP_CHECK(d_stage_in.grow(cap * kBigCt));
-    FHE_HIP_CHECK(d_stage_out.grow(cap * kBigCt));
-    FHE_HIP_CHECK(d_stage_lut.grow(cap));
-    stage_cap = cap;
+    FHE_HIP_CHECK(stage_cap.regrow(count, 256, [&](size_t cap) {
+        return grow_each(d_stage_in, cap * kBigCt, d_stage_out, cap * kBigCt, d_stage_lut, cap);
+    }));
     return FHE_OK;
 }
 
@@ -353,14 +350,12 @@ int fhe_ctx::pbs_device(const uint64_t* d_in, size_t count, const uint32_t* d_lu
 }
 
 int fhe_ctx::ensure_ks(size_t count) {
-    if (count <= ks_cap) return FHE_OK;
+    if (ks_cap.fits(count)) return FHE_OK;
     FHE_HIP_CHECK(hipSetDevice(device));
     FHE_HIP_CHECK(hipStreamSynchronize(stream));  // previous levels may still read them
-    ks_cap = 0;
-    const size_t cap = std::max<size_t>(count, 1024);
-    FHE_HIP_CHECK(d_ks_digits.grow(fhe::ks_digits_bytes((int)cap)));
-    FHE_HIP_CHECK(d_ks_body.grow(cap));
-    ks_cap = cap;
+    FHE_HIP_CHECK(ks_cap.regrow(count, 1024, [&](size_t cap) {
+        return grow_each(d_ks_digits, fhe::ks_digits_bytes((int)cap), d_ks_body, cap);
+    }));
     return FHE_OK;
 }
 
@@ -382,24 +377,10 @@ hipError_t fhe_ctx::keyswitch(const KsKeys& ks, const uint64_t* in, const fhe::P
     return launch_ms_center(ks.ms, count, (uint32_t)ks.n, (size_t)ks.ms_stride, stream);
 }
 
-int fhe_ctx::ensure_rk_ms(size_t count) {
-    if (count <= rk_ms_cap) return FHE_OK;
-    if (d_rk_ms) FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    rk_ms_cap = 0;
-    const size_t cap = std::max<size_t>(count, 256);
-    rk_ms_stride = (int)((rkp.n + 1 + 7) / 8 * 8);
-    FHE_HIP_CHECK(d_rk_ms.grow(cap * rk_ms_stride));
-    rk_ms_cap = cap;
-    return FHE_OK;
-}
-
 int fhe_ctx::release_rekey() {
     if (stream) FHE_HIP_CHECK(hipStreamSynchronize(stream));
-    rk_ms_cap = 0;
-    rk_ms_stride = 0;
-    (void)d_rk_ksk.reset();
-    (void)d_rk_planes.reset();
-    (void)d_rk_ms.reset();
+    rekey.drop();
+    (void)rekey_rows.drop();
     has_rekey = false;
     return FHE_OK;
 }
@@ -688,107 +669,107 @@ int fhe_ctx_create(int device, fhe_ctx** out) {
 
 void fhe_ctx_destroy(fhe_ctx* c) { delete c; }
 
+}  // extern "C"
+
 namespace {
-// The two ends every key install shares.  release_key: the stream is drained and the previous key's
-// buffers are freed, also those a failed install left behind -- from here until install_tail succeeds
-// the context has no key.
+// release_key: the stream is drained and the previous key's buffers are freed, also those a failed install
+// left behind -- from here until the install commits the context has no key.
 int release_key(fhe_ctx* c) {
-    if (c->has_comp) {  // a compression key belongs to the server key it was installed after
-        const int rc = c->release_compression();
-        if (rc) return rc;
-    }
-    if (c->has_pk) {  // so does a public key
-        const int rc = c->release_public_key();
-        if (rc) return rc;
-    }
-    if (c->has_rekey) {  // and a re-keying key
-        const int rc = c->release_rekey();
-        if (rc) return rc;
-    }
+    if (const int rc = c->release_dependants()) return rc;  // they belong to the server key they came after
     if (c->has_key) FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->has_key = false;
-    FHE_HIP_CHECK(c->d_ksk.reset());
-    FHE_HIP_CHECK(c->d_bsk.reset());
-    FHE_HIP_CHECK(c->d_bsk_e.reset());
-    FHE_HIP_CHECK(c->d_ksk_planes.reset());
+    c->key.drop();
     return FHE_OK;
 }
-// Error end of a server-key install: waits for what the install queued, then frees the half-built key
-int drop_key(fhe_ctx* c, int rc) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)release_key(c);
-    return rc;
-}
-// install_tail: d_ksk and the Fourier d_bsk are filled (or being filled on the stream); derive the byte
-// planes and the E layout, wait, adopt the parameters, create the engine.
-int install_tail(fhe_ctx* c, const Params& p, bool had_key) {
-    const int npoly = (int)(p.ggsw_count() * 4);
-    FHE_HIP_CHECK(c->d_ksk_planes.grow(fhe::ks_planes_bytes((int)p.n)));
-    FHE_HIP_CHECK(launch_ksk_to_planes(c->d_ksk, (int)p.n, c->d_ksk_planes, c->stream));
-    // two resident layouts: d_bsk for the latency kernel (br_wide.hip), d_bsk_e for the throughput
-    // kernel (br_qy.hip); rounds 1-4 also kept br_quad.hip's and ran br_qx.hip (both retired in r5)
-    FHE_HIP_CHECK(c->d_bsk_e.grow((size_t)npoly * 1024));
-    FHE_HIP_CHECK(launch_bsk_to_e(c->d_bsk, npoly, c->d_bsk_e, c->stream));
-    FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
-    // the LUT tables survive a re-key with the same message space and delta (ids stay valid)
-    const int rc = c->adopt_key_params(p, had_key);
-    if (rc) return rc;
-    if (!c->engine) {
-        try {
-            c->engine = new fhe::Engine(c);
-        } catch (const std::exception& ex) {
-            set_error(ex.what());
-            return FHE_ERR_HIP;
-        }
-    }
-    return FHE_OK;
+// A direct server-key install (fhe_set_server_key*): the old key goes first, then the outline (install_key)
+// with `fill` as the only part that differs.  It commits by adopting the parameters -- the LUT tables survive
+// a re-key with the same message space and delta (ids stay valid) -- and creating the engine; on an error the
+// stream is drained and the half-built key freed.
+template <class Fill>
+int install_server_key(fhe_ctx* c, const Params& p, Fill&& fill) {
+    FHE_HIP_CHECK(hipSetDevice(c->device));
+    const bool had_key = c->has_key;
+    if (const int rc = release_key(c)) return rc;
+    return install_key(
+        c, c->key,
+        [&]() -> int {
+            FHE_HIP_CHECK(c->key.ks.size((int)p.n, (int)p.ks_level));
+            FHE_HIP_CHECK(c->key.br.size((int)p.n, (int)p.grouping, (int)(p.ggsw_count() * 4)));
+            return fill();
+        },
+        [&]() -> int {
+            const int rc = c->adopt_key_params(p, had_key);
+            return rc ? rc : c->ensure_engine();
+        },
+        [&] {
+            (void)hipStreamSynchronize(c->stream);
+            return release_key(c);
+        });
 }
 }  // namespace
 
-int fhe_set_compression_key(fhe_ctx* c, const fhe_compression_key* key) {
-    if (const int sim = refuse_simulated(c, "fhe_set_compression_key")) return sim;
-    if (!c || !key) {
-        set_error("null argument to fhe_set_compression_key");
+namespace fhe {
+int dependent_key_preamble(const fhe_ctx* c, bool args, const char* fn, const Params* kp, const char* what) {
+    if (const int sim = refuse_simulated(c, fn)) return sim;
+    if (!c || !args) {
+        set_error(std::string("null argument to ") + fn);
         return FHE_ERR_INVALID;
     }
-    if (!c->has_key || !c->engine) {
-        set_error("no server key installed: fhe_set_compression_key comes after fhe_set_server_key");
+    if (!c->has_key || (what && !c->engine)) {
+        set_error(what ? std::string("no server key installed: ") + fn + " comes after fhe_set_server_key"
+                       : std::string("no server key installed (fhe_set_server_key)"));
         return FHE_ERR_NO_KEY;
     }
     uint32_t have = 0, want = 0;
-    // the decompression key is classic whatever the main grouping: compare the main sets field by field
-    if (const char* f = params_differ(key->params, c->p, &have, &want)) {
-        set_error(std::string("compression key's ") + f + " (" + std::to_string(have) +
-                  ") differs from the context's server key (" + std::to_string(want) + ")");
+    // (a decompression key is classic whatever the main grouping: the main sets are compared field by field)
+    if (const char* f = kp ? params_differ(*kp, c->p, &have, &want) : nullptr) {
+        set_error(std::string(what) + "'s " + f + " (" + std::to_string(have) + ") differs from the context's server key (" +
+                  std::to_string(want) + ")");
         return FHE_ERR_INVALID;
     }
+    return FHE_OK;
+}
+}  // namespace fhe
+
+namespace {
+// A compression-key install (full or seeded): the old one goes first, then the outline with `fill` as the only
+// part that differs; the decompression key is classic, of dimension k' N'
+template <class Fill>
+int install_compression_key(fhe_ctx* c, const CompParams& cp, Fill&& fill) {
     FHE_HIP_CHECK(hipSetDevice(c->device));
-    int rc = c->release_compression();
-    if (rc) return rc;
-    const CompParams& cp = key->cp;
+    if (const int rc = c->release_compression()) return rc;
     c->cp = cp;
-    DeviceBuf<uint64_t> d_std;  // freed on return, behind body's wait
-    FHE_HIP_CHECK(d_std.grow(std::max(key->pksk.size(), key->bsk.size())));
-    auto body = [&]() -> int {
-        FHE_HIP_CHECK(c->d_pk_planes.grow(fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
+    return install_key(
+        c, c->comp_br,
+        [&]() -> int {
+            FHE_HIP_CHECK(c->d_pk_planes.grow(fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
+            FHE_HIP_CHECK(c->comp_br.size((int)cp.lwe_dim(), 1, (int)(cp.lwe_dim() * 4)));
+            return fill();
+        },
+        [&]() -> int {
+            c->has_comp = true;
+            return FHE_OK;
+        },
+        [&] { return c->release_compression(); });
+}
+}  // namespace
+
+extern "C" {
+
+int fhe_set_compression_key(fhe_ctx* c, const fhe_compression_key* key) {
+    if (const int rc = dependent_key_preamble(c, key != nullptr, "fhe_set_compression_key", key ? &key->params : nullptr,
+                                              "compression key"))
+        return rc;
+    const CompParams& cp = key->cp;
+    DeviceBuf<uint64_t> d_std;  // freed on return, behind the install's wait
+    return install_compression_key(c, cp, [&]() -> int {
+        FHE_HIP_CHECK(d_std.grow(std::max(key->pksk.size(), key->bsk.size())));
         FHE_HIP_CHECK(hipMemcpyAsync(d_std, key->pksk.data(), key->pksk.size() * 8, hipMemcpyHostToDevice, c->stream));
         FHE_HIP_CHECK(launch_pksk_to_planes(d_std, (int)cp.ell, (int)cp.cols(), c->d_pk_planes, c->stream));
-        const int npoly = (int)(cp.lwe_dim() * 4);
-        FHE_HIP_CHECK(c->d_cbsk.grow((size_t)npoly * 1024));
-        FHE_HIP_CHECK(c->d_cbsk_e.grow((size_t)npoly * 1024));
         FHE_HIP_CHECK(hipMemcpyAsync(d_std, key->bsk.data(), key->bsk.size() * 8, hipMemcpyHostToDevice, c->stream));
-        FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, npoly, c->d_W, c->d_psi, c->d_cbsk, c->stream));
-        FHE_HIP_CHECK(launch_bsk_to_e(c->d_cbsk, npoly, c->d_cbsk_e, c->stream));
-        FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+        FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, c->comp_br.npoly, c->d_W, c->d_psi, c->comp_br.bsk, c->stream));
         return FHE_OK;
-    };
-    rc = body();
-    if (rc) {
-        (void)c->release_compression();
-        return rc;
-    }
-    c->has_comp = true;
-    return FHE_OK;
+    });
 }
 
 // The seeded install: the bodies are the only upload.  seeded_compression.hip writes the packing key's byte
@@ -796,21 +777,9 @@ int fhe_set_compression_key(fhe_ctx* c, const fhe_compression_key* key) {
 // generates the BSK mask polynomials inside the Fourier conversion.  Same device state as
 // fhe_set_compression_key of the host-expanded key.
 int fhe_set_compression_key_seeded(fhe_ctx* c, const fhe_seeded_compression_key* sck) {
-    if (const int sim = refuse_simulated(c, "fhe_set_compression_key_seeded")) return sim;
-    if (!c || !sck) {
-        set_error("null argument to fhe_set_compression_key_seeded");
-        return FHE_ERR_INVALID;
-    }
-    if (!c->has_key || !c->engine) {
-        set_error("no server key installed: fhe_set_compression_key_seeded comes after fhe_set_server_key");
-        return FHE_ERR_NO_KEY;
-    }
-    uint32_t have = 0, want = 0;
-    if (const char* f = params_differ(sck->params, c->p, &have, &want)) {
-        set_error(std::string("seeded compression key's ") + f + " (" + std::to_string(have) +
-                  ") differs from the context's server key (" + std::to_string(want) + ")");
-        return FHE_ERR_INVALID;
-    }
+    if (const int rc = dependent_key_preamble(c, sck != nullptr, "fhe_set_compression_key_seeded",
+                                              sck ? &sck->params : nullptr, "seeded compression key"))
+        return rc;
     CompParams cp;
     const char* why = nullptr;
     if (!CompParams::from_c(sck->cp.to_c(), &cp, &why) || sck->pksk_bodies.size() != cp.pksk_body_words() ||
@@ -818,38 +787,20 @@ int fhe_set_compression_key_seeded(fhe_ctx* c, const fhe_seeded_compression_key*
         set_error(why ? why : "seeded compression key: body counts differ from what its parameters need");
         return FHE_ERR_UNSUPPORTED;
     }
-    FHE_HIP_CHECK(hipSetDevice(c->device));
-    int rc = c->release_compression();
-    if (rc) return rc;
-    c->cp = cp;
     const KeyWords key = bytes_key(sck->seed);
-    DeviceBuf<uint64_t> d_pb, d_bb;  // both freed on return, behind body's wait
-    FHE_HIP_CHECK(d_pb.grow(sck->pksk_bodies.size()));
-    FHE_HIP_CHECK(d_bb.grow(sck->bsk_bodies.size()));
-    auto body = [&]() -> int {
-        FHE_HIP_CHECK(c->d_pk_planes.grow(fhe::pk_planes_bytes((int)cp.ell, (int)cp.cols())));
+    DeviceBuf<uint64_t> d_pb, d_bb;  // both freed on return, behind the install's wait
+    return install_compression_key(c, cp, [&]() -> int {
+        FHE_HIP_CHECK(grow_each(d_pb, sck->pksk_bodies.size(), d_bb, sck->bsk_bodies.size()));
         FHE_HIP_CHECK(hipMemcpyAsync(d_pb, sck->pksk_bodies.data(), sck->pksk_bodies.size() * 8, hipMemcpyHostToDevice,
                                      c->stream));
         FHE_HIP_CHECK(launch_expand_pksk_planes(chacha_stream_key(key.data(), kStreamSeededPksk), d_pb, (int)cp.ell,
                                                 (int)cp.k, (int)cp.N, c->d_pk_planes, c->stream));
-        const int npoly = (int)(cp.lwe_dim() * 4);
-        FHE_HIP_CHECK(c->d_cbsk.grow((size_t)npoly * 1024));
-        FHE_HIP_CHECK(c->d_cbsk_e.grow((size_t)npoly * 1024));
         FHE_HIP_CHECK(hipMemcpyAsync(d_bb, sck->bsk_bodies.data(), sck->bsk_bodies.size() * 8, hipMemcpyHostToDevice,
                                      c->stream));
-        FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededCbsk), d_bb, npoly, c->d_W,
-                                                c->d_psi, c->d_cbsk, c->stream));
-        FHE_HIP_CHECK(launch_bsk_to_e(c->d_cbsk, npoly, c->d_cbsk_e, c->stream));
-        FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+        FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededCbsk), d_bb, c->comp_br.npoly,
+                                                c->d_W, c->d_psi, c->comp_br.bsk, c->stream));
         return FHE_OK;
-    };
-    rc = body();
-    if (rc) {
-        (void)c->release_compression();
-        return rc;
-    }
-    c->has_comp = true;
-    return FHE_OK;
+    });
 }
 
 int fhe_ctx_export_compression_state(fhe_ctx* c, int8_t* planes, size_t planes_bytes, double* bsk, size_t bsk_doubles,
@@ -868,32 +819,23 @@ int fhe_ctx_export_compression_state(fhe_ctx* c, int8_t* planes, size_t planes_b
     FHE_HIP_CHECK(hipSetDevice(c->device));
     FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (planes) FHE_HIP_CHECK(hipMemcpy(planes, c->d_pk_planes, pb, hipMemcpyDeviceToHost));
-    if (bsk) FHE_HIP_CHECK(hipMemcpy(bsk, c->d_cbsk, nd * 8, hipMemcpyDeviceToHost));
-    if (bsk_e) FHE_HIP_CHECK(hipMemcpy(bsk_e, c->d_cbsk_e, nd * 8, hipMemcpyDeviceToHost));
+    if (bsk) FHE_HIP_CHECK(hipMemcpy(bsk, c->comp_br.bsk, nd * 8, hipMemcpyDeviceToHost));
+    if (bsk_e) FHE_HIP_CHECK(hipMemcpy(bsk_e, c->comp_br.bsk_e, nd * 8, hipMemcpyDeviceToHost));
     return FHE_OK;
 }
 
 int fhe_set_server_key(fhe_ctx* c, const fhe_server_key* sk) {
     if (const int sim = refuse_simulated(c, "fhe_set_server_key")) return sim;
     if (!c || !sk) return FHE_ERR_INVALID;
-    FHE_HIP_CHECK(hipSetDevice(c->device));
-    const Params& p = sk->params;
-    const bool had_key = c->has_key;
-    int rc = release_key(c);
-    if (rc) return rc;
-    DeviceBuf<uint64_t> d_std;  // freed on return: behind install_tail's wait, or drop_key's
-    auto body = [&]() -> int {
-        FHE_HIP_CHECK(c->d_ksk.grow(sk->ksk.size()));
-        FHE_HIP_CHECK(hipMemcpyAsync(c->d_ksk, sk->ksk.data(), sk->ksk.size() * 8, hipMemcpyHostToDevice, c->stream));
-        const int npoly = (int)(p.ggsw_count() * 4);
+    DeviceBuf<uint64_t> d_std;  // freed on return: behind the install's wait, or its drop's
+    return install_server_key(c, sk->params, [&]() -> int {
+        if (sk->ksk.size() != c->key.ks.ksk.capacity()) return FHE_ERR_INVALID;  // (no key the library makes)
+        FHE_HIP_CHECK(hipMemcpyAsync(c->key.ks.ksk, sk->ksk.data(), sk->ksk.size() * 8, hipMemcpyHostToDevice, c->stream));
         FHE_HIP_CHECK(d_std.grow(sk->bsk.size()));
-        FHE_HIP_CHECK(c->d_bsk.grow((size_t)npoly * 1024));
         FHE_HIP_CHECK(hipMemcpyAsync(d_std, sk->bsk.data(), sk->bsk.size() * 8, hipMemcpyHostToDevice, c->stream));
-        FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, npoly, c->d_W, c->d_psi, c->d_bsk, c->stream));
-        return install_tail(c, p, had_key);
-    };
-    rc = body();
-    return rc ? drop_key(c, rc) : FHE_OK;
+        FHE_HIP_CHECK(launch_bsk_to_fourier(d_std, c->key.br.npoly, c->d_W, c->d_psi, c->key.br.bsk, c->stream));
+        return FHE_OK;
+    });
 }
 
 // The seeded install: the bodies are the only upload (82 KB + half of the standard-domain BSK, which is
@@ -911,45 +853,27 @@ int fhe_set_server_key_seeded(fhe_ctx* c, const fhe_seeded_server_key* ssk) {
         set_error(why ? why : "seeded server key: body counts differ from what its parameters need");
         return FHE_ERR_UNSUPPORTED;
     }
-    FHE_HIP_CHECK(hipSetDevice(c->device));
-    const bool had_key = c->has_key;
-    int rc = release_key(c);
-    if (rc) return rc;
     const KeyWords key = bytes_key(ssk->seed);
-    const int rows = (int)(kPolySize * p.ks_level), npoly = (int)(p.ggsw_count() * 4);
-    DeviceBuf<uint64_t> d_kb, d_bb;  // both freed on return: behind install_tail's wait, or drop_key's
-    auto body = [&]() -> int {
-        FHE_HIP_CHECK(d_kb.grow(ssk->ksk_bodies.size()));
-        FHE_HIP_CHECK(d_bb.grow(ssk->bsk_bodies.size()));
-        FHE_HIP_CHECK(c->d_ksk.grow((size_t)rows * (p.n + 1)));
-        FHE_HIP_CHECK(c->d_bsk.grow((size_t)npoly * 1024));
+    DeviceBuf<uint64_t> d_kb, d_bb;  // both freed on return: behind the install's wait, or its drop's
+    return install_server_key(c, p, [&]() -> int {
+        FHE_HIP_CHECK(grow_each(d_kb, ssk->ksk_bodies.size(), d_bb, ssk->bsk_bodies.size()));
         FHE_HIP_CHECK(hipMemcpyAsync(d_kb, ssk->ksk_bodies.data(), ssk->ksk_bodies.size() * 8, hipMemcpyHostToDevice,
                                      c->stream));
-        FHE_HIP_CHECK(launch_expand_ksk(chacha_stream_key(key.data(), kStreamSeededKsk), c->d_ksk, d_kb, rows,
-                                        (int)p.n, c->stream));
+        FHE_HIP_CHECK(launch_expand_ksk(chacha_stream_key(key.data(), kStreamSeededKsk), c->key.ks.ksk, d_kb,
+                                        (int)(kPolySize * p.ks_level), (int)p.n, c->stream));
         FHE_HIP_CHECK(hipMemcpyAsync(d_bb, ssk->bsk_bodies.data(), ssk->bsk_bodies.size() * 8, hipMemcpyHostToDevice,
                                      c->stream));
-        FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededBsk), d_bb, npoly, c->d_W,
-                                                c->d_psi, c->d_bsk, c->stream));
-        return install_tail(c, p, had_key);
-    };
-    rc = body();
-    return rc ? drop_key(c, rc) : FHE_OK;
+        FHE_HIP_CHECK(launch_expand_bsk_fourier(chacha_stream_key(key.data(), kStreamSeededBsk), d_bb, c->key.br.npoly,
+                                                c->d_W, c->d_psi, c->key.br.bsk, c->stream));
+        return FHE_OK;
+    });
 }
 
 // The re-keying key's install: the bodies are the only upload (82 KB); seeded_key.hip's KSK expansion regenerates
 // the masks under the key's own stream id, ks_mfma.hip derives the byte planes.  Same device words as an upload
 // of expand_rekey_key_host's KSK.
 int fhe_set_rekey_key(fhe_ctx* c, const fhe_rekey_key* key) {
-    if (const int sim = refuse_simulated(c, "fhe_set_rekey_key")) return sim;
-    if (!c || !key) {
-        set_error("null argument to fhe_set_rekey_key");
-        return FHE_ERR_INVALID;
-    }
-    if (!c->has_key) {
-        set_error("no server key installed (fhe_set_server_key)");
-        return FHE_ERR_NO_KEY;
-    }
+    if (const int rc = dependent_key_preamble(c, key != nullptr, "fhe_set_rekey_key")) return rc;
     const Params& p = key->params;
     Params checked;
     const char* why = nullptr;
@@ -965,29 +889,25 @@ int fhe_set_rekey_key(fhe_ctx* c, const fhe_rekey_key* key) {
         return FHE_ERR_INVALID;
     }
     FHE_HIP_CHECK(hipSetDevice(c->device));
-    int rc = c->release_rekey();
-    if (rc) return rc;
+    if (const int rc = c->release_rekey()) return rc;
     const KeyWords k = bytes_key(key->seed);
-    const int rows = (int)(kPolySize * p.ks_level);
-    DeviceBuf<uint64_t> d_kb;  // freed on return, behind the wait below
-    auto body = [&]() -> int {
-        FHE_HIP_CHECK(d_kb.grow(key->bodies.size()));
-        FHE_HIP_CHECK(c->d_rk_ksk.grow((size_t)rows * (p.n + 1)));
-        FHE_HIP_CHECK(c->d_rk_planes.grow(fhe::ks_planes_bytes((int)p.n)));
-        FHE_HIP_CHECK(hipMemcpyAsync(d_kb, key->bodies.data(), key->bodies.size() * 8, hipMemcpyHostToDevice, c->stream));
-        FHE_HIP_CHECK(launch_expand_ksk(chacha_stream_key(k.data(), kStreamRekeyKsk), c->d_rk_ksk, d_kb, rows, (int)p.n, c->stream));
-        FHE_HIP_CHECK(launch_ksk_to_planes(c->d_rk_ksk, (int)p.n, c->d_rk_planes, c->stream));
-        FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
-        return FHE_OK;
-    };
-    rc = body();
-    if (rc) {
-        (void)c->release_rekey();
-        return rc;
-    }
-    c->rkp = p;
-    c->has_rekey = true;
-    return FHE_OK;
+    DeviceBuf<uint64_t> d_kb;  // freed on return, behind the install's wait
+    return install_key(
+        c, c->rekey,
+        [&]() -> int {
+            FHE_HIP_CHECK(d_kb.grow(key->bodies.size()));
+            FHE_HIP_CHECK(c->rekey.size((int)p.n, (int)p.ks_level));
+            FHE_HIP_CHECK(hipMemcpyAsync(d_kb, key->bodies.data(), key->bodies.size() * 8, hipMemcpyHostToDevice, c->stream));
+            FHE_HIP_CHECK(launch_expand_ksk(chacha_stream_key(k.data(), kStreamRekeyKsk), c->rekey.ksk, d_kb,
+                                            (int)(kPolySize * p.ks_level), (int)p.n, c->stream));
+            return FHE_OK;
+        },
+        [&]() -> int {
+            c->rkp = p;
+            c->has_rekey = true;
+            return FHE_OK;
+        },
+        [&] { return c->release_rekey(); });
 }
 
 int fhe_ctx_export_fourier_bsk(fhe_ctx* c, double* out, size_t len) {
@@ -1000,7 +920,7 @@ int fhe_ctx_export_fourier_bsk(fhe_ctx* c, double* out, size_t len) {
     }
     FHE_HIP_CHECK(hipSetDevice(c->device));
     FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
-    FHE_HIP_CHECK(hipMemcpy(out, c->d_bsk, need * 8, hipMemcpyDeviceToHost));
+    FHE_HIP_CHECK(hipMemcpy(out, c->key.br.bsk, need * 8, hipMemcpyDeviceToHost));
     return FHE_OK;
 }
 
@@ -1075,10 +995,10 @@ int fhe_pbs_batch_device(fhe_ctx* c, const uint64_t* d_in, size_t count, const u
 }
 
 namespace {
-// d_ms rows (stride ms_stride) -> host rows of n + 1 words, behind the keyswitch on the stream
+// the keyswitched rows -> host rows of n + 1 words, behind the keyswitch on the stream
 hipError_t copy_small(fhe_ctx* c, uint64_t* small, size_t count) {
     const size_t row = ((size_t)c->p.n + 1) * 8;
-    return hipMemcpy2DAsync(small, row, c->d_ms, (size_t)c->ms_stride * 8, row, count, hipMemcpyDeviceToHost,
+    return hipMemcpy2DAsync(small, row, c->rows.rows(), (size_t)c->rows.stride() * 8, row, count, hipMemcpyDeviceToHost,
                             c->stream);
 }
 }  // namespace

@@ -1,7 +1,8 @@
 // context.h -- per-thread device context: GPU stream, installed server key, LUT registry,
 // PBS workspace.  The analogue of tfhe-rs's thread-local server key (src/schnorr.rs:443).  Every device
-// buffer is a DeviceBuf (device_buf.h): the context's destructor and the release_* functions wait, then the
-// members free themselves.
+// buffer is a DeviceBuf (device_buf.h), the keys are key sets (key_sets.h) and every workspace is a group of
+// buffers under one capacity (GroupCap, RowSpace): the context's destructor and the release_* functions wait,
+// then the members free themselves.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 
 #include "compress.h"
 #include "device_buf.h"
+#include "key_sets.h"
 #include "keys.h"
 #include "kernels.h"
 
@@ -62,13 +64,15 @@ struct fhe_ctx {
     // layer's entry points run on it, everything that needs device memory or a real key refuses (refuse_simulated)
     bool simulated = false;
     fhe::Params p;
-    fhe::DeviceBuf<uint64_t> d_ksk;
-    fhe::DeviceBuf<double2> d_bsk;  // Fourier BSK, blind-rotate layout
+    // The installed server key: the keyswitch and blind-rotate sets, which carry the n (and grouping) their
+    // buffers were sized for, and `rows`, the keyswitched small LWE the one writes and the other reads, whose
+    // stride follows the n it was grown for.  Replaced as a whole (install_key), never member by member.
+    fhe::ServerKeySet key;
+    fhe::RowSpace rows;
     fhe::DeviceBuf<double2> d_W;    // per-lane twiddle table [30][64]
     fhe::DeviceBuf<double2> d_psi;
     fhe::DeviceBuf<double2> d_tw_wide;   // [12][256]
     fhe::DeviceBuf<double2> d_psi_wide;  // [4][256]
-    fhe::DeviceBuf<double2> d_bsk_e;     // Fourier BSK in the throughput kernel's E layout (br_qy.hip)
     fhe::DeviceBuf<double2> d_zeta_full; // zeta(s, b) at [2^s + b], 1024 entries (br_qy.hip)
     fhe::DeviceBuf<double2> d_tw_quad;   // W[0..512)
     // [2][8][128] (quad_tables): the twist psi[128 r + t], which no kernel has read since the twisted
@@ -76,10 +80,9 @@ struct fhe_ctx {
     fhe::DeviceBuf<double2> d_psi_quad;
     fhe::DeviceBuf<double2> d_zeta_wide; // [10][256] (context.cpp:wide_zetas)
     fhe::DeviceBuf<double2> d_mono;      // monomial table E[4096] of the multi-bit blind rotation (mono_table)
-    fhe::DeviceBuf<int8_t> d_ksk_planes; // KSK as balanced signed-byte planes (ks_mfma.hip)
     int ks_kernel = FHE_KS_MFMA;
     // fhe_ctx_set_modulus_switch: FHE_MS_CENTERED makes keyswitch() follow its kernel with k_ms_center on
-    // d_ms (ms_center.hip), so every level launched from then on hands the blind rotation centered rows
+    // the rows it wrote (ms_center.hip), so every level launched from then on hands the blind rotation centered rows
     int ms_mode = FHE_MS_STANDARD;
     // classic throughput kernel (fhe_ctx_set_br_kernel): FHE_BR_AUTO = qz (two ciphertexts per workgroup,
     // one wave per polynomial; it replaced qy2 here, same quantisation) where its rounds of 1024 (256 CUs x
@@ -94,7 +97,7 @@ struct fhe_ctx {
     }
     fhe::DeviceBuf<int8_t> d_ks_digits;  // keyswitch digits workspace
     fhe::DeviceBuf<uint64_t> d_ks_body;
-    size_t ks_cap = 0;              // ciphertexts; 0 while either of the two is not grown
+    fhe::GroupCap ks_cap;           // ciphertexts
     // levels with at most this many bootstraps use the latency kernel (one ciphertext per CU at a
     // time -- >128 KB LDS -- so one round over the 256 CUs); the throughput kernel above, which holds
     // 2-3 per CU (profiles/r2/latency_sweep_r2b.txt: from 320 on it is as fast or faster)
@@ -104,14 +107,11 @@ struct fhe_ctx {
     std::vector<uint64_t> h_luts;
     fhe::DeviceBuf<uint64_t> d_luts;  // capacity() / kPolySize tables
     bool luts_dirty = false;
-    // PBS workspace
-    fhe::DeviceBuf<uint64_t> d_ms;  // keyswitched small LWE (u64, stride ms_stride >= n+1)
-    size_t ms_cap = 0;  // ciphertexts
-    int ms_stride = 0;
+    // staging of the raw batch entry points
     fhe::DeviceBuf<uint64_t> d_stage_in;
     fhe::DeviceBuf<uint64_t> d_stage_out;
     fhe::DeviceBuf<uint32_t> d_stage_lut;
-    size_t stage_cap = 0;  // ciphertexts; 0 while any of the three is not grown
+    fhe::GroupCap stage_cap;  // ciphertexts
     // timing
     bool timing = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -131,6 +131,7 @@ struct fhe_ctx {
     int fanout_emulate = 0;     // test hook: split levels over this many virtual ranks on one GPU
     size_t fanout_min = 257;  // above one ciphertext per CU (256 CUs) a level costs 2x the floor
     fhe::DeviceBuf<uint64_t> d_gather;   // [nranks * chunk][2049]
+    fhe::GroupCap gather_cap;            // ciphertexts
     // test hook (fhe_ctx_attach_test_transport): the collectives through host buffers and callbacks
     fhe_test_transport tx{};
     bool has_tx = false;
@@ -166,30 +167,31 @@ struct fhe_ctx {
     int allreduce_min_u8(uint8_t* flags, size_t n);
     fhe::DeviceBuf<uint8_t> d_flags;  // device staging of allreduce_min_u8 (grown, freed with the context)
 
-    int ensure_ms(size_t count);
+    // at least `count` rows in `rs` for dimension n, regrown behind a wait on the stream
+    int ensure_rows(fhe::RowSpace& rs, size_t n, size_t count);
+    int ensure_ms(size_t count) { return ensure_rows(rows, p.n, count); }
+    // the keys that belong to the installed server key and do not outlive it (compression, public, re-keying):
+    // each one that is installed is released behind its own wait
+    int release_dependants();
     // Commit point of every key install (fhe_set_server_key, the receivers of
     // fhe_ctx_broadcast_server_key), called once the new key's device buffers are in place: drops
-    // what the previous key's parameters sized or encoded -- the d_ms workspace (row stride from n:
-    // a stride kept across a change of dimension would overlap the keyswitch's rows) and, unless the
+    // what the previous key's parameters sized or encoded -- the dependent keys, the row space (row stride
+    // from n: a stride kept across a change of dimension would overlap the keyswitch's rows) and, unless the
     // message space and delta are unchanged, the LUT tables (their ids then start again at 0) --
     // and makes `np` the context's parameters.
     int adopt_key_params(const fhe::Params& np, bool had_key);
+    // the radix-layer executor, created with the first server key
+    int ensure_engine();
     int ensure_ks(size_t count);
-    // keyswitch of `count` inputs (contiguous big LWE in `in`, or descriptors) into d_ms; in centered mode
+    // keyswitch of `count` inputs (contiguous big LWE in `in`, or descriptors) into `rows`; in centered mode
     // the rows' bodies are then corrected in place (k_ms_center), behind the keyswitch on the stream
     hipError_t keyswitch(const uint64_t* in, const fhe::PbsDesc* desc, size_t count);
-    // The key set one keyswitch runs under, in the spirit of BrKeys below: the KSK in its two forms, the
-    // destination dimension and the workspace the rows go to.  main_ks() is what every level uses; rekey_ks() the
-    // re-keying key (fhe_set_rekey_key: another small key, its own workspace -- d_ms' stride is sized for p.n).
-    struct KsKeys {
-        const uint64_t* ksk;
-        const int8_t* planes;
-        int n;
-        uint64_t* ms;
-        int ms_stride;
-    };
-    KsKeys main_ks() const { return {d_ksk, d_ksk_planes, (int)p.n, d_ms, ms_stride}; }
-    KsKeys rekey_ks() const { return {d_rk_ksk, d_rk_planes, (int)rkp.n, d_rk_ms, rk_ms_stride}; }
+    // What one keyswitch runs under (key_sets.h): a keyswitch set on the row space its rows go to.  main_ks() is
+    // what every level uses; rekey_ks() the re-keying key (fhe_set_rekey_key: another small key and a row space
+    // of its own, strided for its own n).
+    using KsKeys = fhe::KsKeys;
+    KsKeys main_ks() const { return key.ks.on(rows); }
+    KsKeys rekey_ks() const { return rekey.on(rekey_rows); }
     hipError_t keyswitch(const KsKeys& ks, const uint64_t* in, const fhe::PbsDesc* desc, size_t count);
     int ensure_stage(size_t count);
     int sync_luts();
@@ -200,43 +202,35 @@ struct fhe_ctx {
     int register_lut_oprf(uint32_t bits, uint32_t* id);
     // KS + BR(+SE) over device arrays, async on `stream`
     int pbs_device(const uint64_t* d_in, size_t count, const uint32_t* d_lut, uint64_t* d_out);
-    // blind rotate (+SE) of `count` modulus-switched inputs in d_ms, kernel chosen by batch size
+    // blind rotate (+SE) of `count` modulus-switched inputs in `rows`, kernel chosen by batch size
     hipError_t blind_rotate(const fhe::PbsDesc* desc, const uint32_t* lut_idx, uint64_t* out, size_t count);
-    // The key set one blind rotation runs under: the two Fourier layouts, the LWE dimension, the grouping and
-    // the workspace holding the inputs.  main_keys() is what every bootstrap of the radix layer uses;
-    // comp_keys() the decompression key (classic, n = k' N', its own workspace: d_ms' stride is sized for p.n).
-    struct BrKeys {
-        const double2 *bsk, *bsk_e;
-        int n, grouping;
-        const uint64_t* ms;
-        int ms_stride;
-    };
-    BrKeys main_keys() const { return {d_bsk, d_bsk_e, (int)p.n, (int)p.grouping, d_ms, ms_stride}; }
-    BrKeys comp_keys() const { return {d_cbsk, d_cbsk_e, (int)cp.lwe_dim(), 1, d_cms, cms_stride}; }
+    // What one blind rotation runs under (key_sets.h): a blind-rotate set on the row space holding the inputs.
+    // main_keys() is what every bootstrap of the radix layer uses; comp_keys() the decompression key (classic,
+    // n = k' N', a row space of its own).
+    using BrKeys = fhe::BrKeys;
+    BrKeys main_keys() const { return key.br.on(rows); }
+    BrKeys comp_keys() const { return comp_br.on(comp_rows); }
     hipError_t blind_rotate(const BrKeys& ks, const fhe::PbsDesc* desc, const uint32_t* lut_idx, uint64_t* out,
                             size_t count);
 
     // Compression key (fhe_set_compression_key; dropped by every server-key install): the packing KSK as
-    // byte planes (compress.hip), the decompression BSK in the two Fourier layouts, and the workspaces.
+    // byte planes (compress.hip), the decompression BSK as a blind-rotate set, and the workspaces.
     bool has_comp = false;
     fhe::CompParams cp;
     fhe::DeviceBuf<int8_t> d_pk_planes;
-    fhe::DeviceBuf<double2> d_cbsk;    // latency layout
-    fhe::DeviceBuf<double2> d_cbsk_e;  // throughput (E) layout
+    fhe::BrKeySet comp_br;
     // compression workspace, `pk_cap` blocks: slot pointers, digits, bodies, contraction output, packed stream
     fhe::DeviceBuf<const uint64_t*> d_pk_src;
     fhe::DeviceBuf<int8_t> d_pk_digits;
     fhe::DeviceBuf<uint64_t> d_pk_body;
     fhe::DeviceBuf<uint64_t> d_pk_P;
     fhe::DeviceBuf<uint8_t> d_pk_out;
-    size_t pk_cap = 0;
-    // decompression workspace, `cms_cap` blocks: sample-extracted rows (stride cms_stride >= k' N' + 1),
-    // the uploaded 12-bit stream, one descriptor (LUT, destination slot) per block
-    fhe::DeviceBuf<uint64_t> d_cms;
+    fhe::GroupCap pk_cap;
+    // decompression workspace, one group under comp_rows' capacity: the sample-extracted rows (dimension
+    // k' N'), the uploaded 12-bit stream, one descriptor (LUT, destination slot) per block
+    fhe::RowSpace comp_rows;
     fhe::DeviceBuf<uint8_t> d_cpacked;
     fhe::DeviceBuf<fhe::PbsDesc> d_cdesc;
-    size_t cms_cap = 0;
-    int cms_stride = 0;
     int ensure_pk(size_t count);
     int ensure_cms(size_t count);
     int release_compression();  // waits for the stream, frees all of the above
@@ -250,16 +244,13 @@ struct fhe_ctx {
     int release_public_key();  // waits for the stream, frees all of the above
 
     // Re-keying key (fhe_set_rekey_key; dropped by every server-key install): the expanded KSK to the destination's
-    // small key (FHE_KS_VALU reads it) and its byte planes, the destination's parameters, and a row workspace of
-    // `rk_ms_cap` rows whose stride is sized for the destination's dimension.
+    // small key as a keyswitch set, the destination's parameters (what a re-keyed list is labelled with), and a
+    // row space strided for the destination's dimension.
     bool has_rekey = false;
     fhe::Params rkp;
-    fhe::DeviceBuf<uint64_t> d_rk_ksk;
-    fhe::DeviceBuf<int8_t> d_rk_planes;
-    fhe::DeviceBuf<uint64_t> d_rk_ms;
-    size_t rk_ms_cap = 0;
-    int rk_ms_stride = 0;
-    int ensure_rk_ms(size_t count);
+    fhe::KsKeySet rekey;
+    fhe::RowSpace rekey_rows;
+    int ensure_rk_ms(size_t count) { return ensure_rows(rekey_rows, (size_t)rekey.n, count); }
     int release_rekey();  // waits for the stream, frees all of the above
 
     // Resident client key (fhe_ctx_set_client_key, client_ops.cpp): for a process that holds the
@@ -278,3 +269,32 @@ struct fhe_ctx {
     hipError_t client_stage_stream(const fhe::ChaChaStream& at, uint32_t noise_log2);
     int release_client_key();  // waits for the stream, wipes, frees
 };
+
+namespace fhe {
+
+// The outline of every key install.  `fill` sizes the set's buffers and queues what fills them (an upload, an
+// expansion from a seed, a collective); the set derives its second layout behind that (byte planes, E layout);
+// the stream is drained; `commit` makes the key the context's.  On an error of any step `drop` waits for what
+// was queued and frees the half-built key.  What is replaced, and when, is the caller's discipline: a direct
+// install releases the old key before it calls this, a broadcast receiver swaps inside `commit`.
+template <class Set, class Fill, class Commit, class Drop>
+int install_key(fhe_ctx* c, Set& set, Fill&& fill, Commit&& commit, Drop&& drop) {
+    auto body = [&]() -> int {
+        if (const int rc = fill()) return rc;
+        FHE_HIP_CHECK(set.derive(c->stream));
+        FHE_HIP_CHECK(hipStreamSynchronize(c->stream));
+        return commit();
+    };
+    const int rc = body();
+    if (rc) (void)drop();
+    return rc;
+}
+
+// What every install of a key that depends on the server key starts with, under the entry point's name `fn`:
+// refuses a simulated context, a null argument (`args` false), a context without a server key, and, with `kp`,
+// a key whose parameters differ from the server key's (`what`: "compression key", ...).  fhe_set_rekey_key
+// passes no `kp`: it compares by its own rule after its own checks, and keeps its shorter no-key message.
+int dependent_key_preamble(const fhe_ctx* c, bool args, const char* fn, const Params* kp = nullptr,
+                           const char* what = nullptr);
+
+}  // namespace fhe

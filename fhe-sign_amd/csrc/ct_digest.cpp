@@ -9,6 +9,7 @@
 #include "ct_digest.h"
 #include "fhe_rocm.h"
 #include "public_key.h"  // parallel_chunks
+#include "capi_internal.h"
 
 namespace fhe {
 
@@ -79,22 +80,6 @@ const CtDigestMidstates& ct_digest_midstates() {
 using namespace fhe;
 
 namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
-template <class F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        set_error("out of memory");
-        return FHE_ERR_ALLOC;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return FHE_ERR_INVALID;
-    }
-}
 int add_item(fhe_rerand_context* rc, uint8_t kind, const uint8_t* p, size_t n, const char* who) {
     if (rc->finalized) return invalid(std::string(who) + ": the context gave out a seed already; a seed depends on everything added");
     rc->h.u8(kind);
@@ -109,7 +94,7 @@ extern "C" {
 int fhe_ct_digest_host(const uint64_t* rows, size_t nblocks, uint8_t* out) {
     if ((!rows || !out) && nblocks) return invalid("null argument to fhe_ct_digest_host");
     if (nblocks > kCtDigestMaxRows) return invalid("fhe_ct_digest_host: more than 2^24 rows");
-    return guarded([&] {
+    return guarded_alloc([&] {
         ct_digest_host(rows, nblocks, out);
         return (int)FHE_OK;
     });
@@ -128,7 +113,7 @@ int fhe_ct_value_digest_host(uint8_t kind, uint32_t bits, const uint8_t* tags, c
 
 int fhe_rerand_context_new(const uint8_t* domain, size_t domain_len, fhe_rerand_context** rc) {
     if (!rc || (domain_len && !domain)) return invalid("null argument to fhe_rerand_context_new");
-    return guarded([&] {
+    return guarded_alloc([&] {
         auto x = std::make_unique<fhe_rerand_context>();
         x->h = tagged_start(kTagRerandContext);
         x->h.u64le((uint64_t)domain_len);
@@ -194,7 +179,7 @@ int fhe_ctx_time_ct_digest(fhe_ctx* c, size_t nblocks, uint32_t reps, float* ms)
         *ms = total / (float)reps;
         return FHE_OK;
     };
-    const int r = guarded(body);
+    const int r = guarded_alloc(body);
     if (c->stream) (void)hipStreamSynchronize(c->stream);  // the buffers go: nothing may still read them
     for (hipEvent_t e : ev)
         if (e) (void)hipEventDestroy(e);

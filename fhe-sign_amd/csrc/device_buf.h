@@ -74,4 +74,75 @@ private:
 template <class T>
 using PinnedBuf = DeviceBuf<T, HipPinnedAlloc>;
 
+// grow_each(a, na, b, nb, ...): grows each buffer to its count, in order; stops at the first error
+inline hipError_t grow_each() { return hipSuccess; }
+template <class B, class... Rest>
+hipError_t grow_each(B& buf, size_t count, Rest&&... rest) {
+    const hipError_t e = buf.grow(count);
+    return e != hipSuccess ? e : grow_each(rest...);
+}
+
+// The capacity, in items, of a group of buffers that are grown together (a workspace).  It is 0 while any buffer
+// of the group is not grown: a regrowth that fails half-way leaves some buffers new, some empty, and the next
+// request, however small, regrows them all.  As with a DeviceBuf the caller waits first, when queued work may
+// still touch the old buffers.
+class GroupCap {
+public:
+    size_t get() const { return cap_; }
+    bool fits(size_t count) const { return count <= cap_; }
+    void drop() { cap_ = 0; }
+    // regrows the group for max(count, floor) items: grow(cap) grows every buffer of the group for `cap` items
+    // (grow_each) and returns the first error
+    template <class Grow>
+    hipError_t regrow(size_t count, size_t floor, Grow&& grow) {
+        cap_ = 0;
+        const size_t cap = count < floor ? floor : count;
+        const hipError_t e = grow(cap);
+        if (e == hipSuccess) cap_ = cap;
+        return e;
+    }
+
+private:
+    size_t cap_ = 0;
+};
+
+// Rows of u64 for LWE ciphertexts of one dimension: the buffer, how many rows it holds and the row stride, n + 1
+// words rounded up to 64 bytes, that it was grown with.  The stride is 0 whenever the rows are not grown, so a
+// stride never outlives the dimension it was derived from.
+template <class Alloc = HipDeviceAlloc>
+class RowSpaceOf {
+public:
+    static constexpr size_t kFloor = 256;
+    static int stride_of(size_t n) { return (int)((n + 1 + 7) / 8 * 8); }
+    uint64_t* rows() const { return rows_; }
+    size_t cap() const { return cap_.get(); }
+    int stride() const { return stride_; }
+    bool fits(size_t count) const { return cap_.fits(count); }
+    // at least `count` rows (and kFloor) for dimension n; more(cap) grows what else belongs to the group
+    template <class More>
+    hipError_t regrow(size_t count, size_t n, More&& more) {
+        stride_ = 0;
+        const hipError_t e = cap_.regrow(count, kFloor, [&](size_t cap) {
+            const hipError_t g = rows_.grow(cap * (size_t)stride_of(n));
+            return g != hipSuccess ? g : more(cap);
+        });
+        if (e == hipSuccess) stride_ = stride_of(n);
+        return e;
+    }
+    hipError_t regrow(size_t count, size_t n) {
+        return regrow(count, n, [](size_t) { return hipSuccess; });
+    }
+    hipError_t drop() {
+        cap_.drop();
+        stride_ = 0;
+        return rows_.reset();
+    }
+
+private:
+    DeviceBuf<uint64_t, Alloc> rows_;
+    GroupCap cap_;
+    int stride_ = 0;
+};
+using RowSpace = RowSpaceOf<>;
+
 }  // namespace fhe

@@ -256,11 +256,11 @@ void Engine::extract_rows(const fhe_compressed_list& x, uint64_t* rows) {
     hip_check(hipMemcpyAsync(ctx_->d_cpacked, x.packed.data(), x.packed.size(), hipMemcpyHostToDevice, ctx_->stream),
               "compressed upload");
     hip_check(launch_pk_unpack(ctx_->d_cpacked, (int)n, (int)cp.glwe_bytes(cp.L), (int)cp.L, (int)cp.N, (int)cp.k,
-                               ctx_->d_cms, ctx_->cms_stride, ctx_->stream),
+                               ctx_->comp_rows.rows(), ctx_->comp_rows.stride(), ctx_->stream),
               "unpack");
     if (rows) {
         const size_t row = ((size_t)cp.lwe_dim() + 1) * 8;
-        hip_check(hipMemcpy2DAsync(rows, row, ctx_->d_cms, (size_t)ctx_->cms_stride * 8, row, n, hipMemcpyDeviceToHost,
+        hip_check(hipMemcpy2DAsync(rows, row, ctx_->comp_rows.rows(), (size_t)ctx_->comp_rows.stride() * 8, row, n, hipMemcpyDeviceToHost,
                                    ctx_->stream),
                   "rows download");
         hip_check(hipStreamSynchronize(ctx_->stream), "rows sync");
@@ -303,7 +303,7 @@ Blocks Engine::oprf(const uint8_t seed[32], size_t count, uint32_t bits, uint32_
                  "oprf accumulator");
     // the workspace as it stands (at least kOprfChunk rows) is the chunk: a large call does not grow it
     constexpr size_t kOprfChunk = 4096;
-    const size_t chunk = std::min(n, std::max(ctx_->ms_cap, kOprfChunk));
+    const size_t chunk = std::min(n, std::max(ctx_->rows.cap(), kOprfChunk));
     engine_check(ctx_->ensure_ms(chunk) == FHE_OK, "bootstrap workspace");
     ensure_eager_desc(chunk);
     std::vector<uint32_t> degrees(n, (1u << bits) - 1);
@@ -319,7 +319,7 @@ Blocks Engine::oprf(const uint8_t seed[32], size_t count, uint32_t bits, uint32_
     const ChaChaKey ck = chacha_stream_key(key.data(), kStreamOprf);
     for (size_t at = 0; at < n; at += chunk) {
         const size_t m = std::min(chunk, n - at);
-        hip_check(launch_oprf_rows(ck, ctx_->d_ms, (uint32_t)at, (uint32_t)m, p.n, ctx_->stream), "oprf rows");
+        hip_check(launch_oprf_rows(ck, ctx_->rows.rows(), (uint32_t)at, (uint32_t)m, p.n, ctx_->stream), "oprf rows");
         hip_check(hipMemcpyAsync(d_oprf_desc_, desc.data() + at, m * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream),
                   "oprf descriptors");
         hip_check(ctx_->blind_rotate(ctx_->main_keys(), d_oprf_desc_, nullptr, nullptr, m), "oprf blind rotate");
@@ -365,7 +365,7 @@ void Engine::switched_compress(const std::vector<const Block*>& blocks, uint8_t*
         desc[i].coef[0] = 1;
         desc[i].nterms = 1;
     }
-    const size_t chunk = std::min(n, std::max(rekey ? ctx_->rk_ms_cap : ctx_->ms_cap, kSwitchedChunk));
+    const size_t chunk = std::min(n, std::max(rekey ? ctx_->rekey_rows.cap() : ctx_->rows.cap(), kSwitchedChunk));
     engine_check((rekey ? ctx_->ensure_rk_ms(chunk) : ctx_->ensure_ms(chunk)) == FHE_OK, "row workspace");
     ensure_eager_desc(chunk);
     const fhe_ctx::KsKeys ks = rekey ? ctx_->rekey_ks() : ctx_->main_ks();
@@ -401,7 +401,7 @@ Blocks Engine::switched_decompress(const fhe_switched_list& x) {
     for (uint32_t v = 0; v < ident.size(); ++v) ident[v] = v;
     uint32_t lut = 0;
     engine_check(ctx_->register_lut(ident.data(), &lut) == FHE_OK && ctx_->sync_luts() == FHE_OK, "identity table");
-    const size_t chunk = std::min(n, std::max(ctx_->ms_cap, kSwitchedChunk));
+    const size_t chunk = std::min(n, std::max(ctx_->rows.cap(), kSwitchedChunk));
     engine_check(ctx_->ensure_ms(chunk) == FHE_OK, "bootstrap workspace");
     ensure_eager_desc(chunk);
     if (!d_sw_packed_.fits(chunk * dev_bytes / 4)) {
@@ -416,7 +416,7 @@ Blocks Engine::switched_decompress(const fhe_switched_list& x) {
         for (size_t i = 0; i < m; ++i) std::memcpy(stage.data() + i * dev_bytes, x.rows.data() + (at + i) * bytes, bytes);
         hip_check(hipMemcpyAsync(d_sw_packed_, stage.data(), m * dev_bytes, hipMemcpyHostToDevice, ctx_->stream),
                   "stored rows upload");
-        hip_check(launch_ms_unpack(d_sw_packed_, ctx_->d_ms, m, p.n, ctx_->stream), "row unpacking");
+        hip_check(launch_ms_unpack(d_sw_packed_, ctx_->rows.rows(), m, p.n, ctx_->stream), "row unpacking");
         hip_check(hipMemcpyAsync(d_oprf_desc_, desc.data() + at, m * sizeof(PbsDesc), hipMemcpyHostToDevice, ctx_->stream),
                   "decompress descriptors");
         hip_check(ctx_->blind_rotate(ctx_->main_keys(), d_oprf_desc_, nullptr, nullptr, m), "decompression blind rotate");

@@ -3,6 +3,7 @@
 // measurement entries that run the kernel over host rows.  fhe_ctx::keyswitch (context.cpp) is the device path.
 #include "context.h"
 #include "fhe_rocm.h"
+#include "capi_internal.h"
 
 namespace fhe {
 
@@ -25,10 +26,6 @@ void ms_center_host(uint64_t* rows, size_t count, uint32_t n, size_t stride) {
 using namespace fhe;
 
 namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
 // 1 <= n <= 2048 keeps the sum inside int64; a row holds its n mask words and the body
 int check_shape(const char* who, uint32_t n, size_t stride) {
     if (n < 1 || n > FHE_MS_CENTER_MAX_N) return invalid(std::string(who) + ": n must be 1 .. 2048");

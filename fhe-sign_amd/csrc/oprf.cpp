@@ -7,6 +7,7 @@
 
 #include "oprf.h"
 #include "radix.h"
+#include "capi_internal.h"
 
 namespace fhe {
 
@@ -52,10 +53,6 @@ int fhe_ctx::register_lut_oprf(uint32_t bits, uint32_t* id) {
 }
 
 namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
 int check_rows(const char* who, uint32_t n, size_t count, size_t stride) {
     if (n < 1 || n > kBigDim) return invalid(std::string(who) + ": n must be 1 .. 2048");
     if (stride < (size_t)n + 1) return invalid(std::string(who) + ": stride must be at least n + 1");

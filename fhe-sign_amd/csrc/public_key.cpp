@@ -13,6 +13,7 @@
 #include "context.h"
 #include "fhe_rocm.h"
 #include "serial.h"
+#include "capi_internal.h"
 
 namespace fhe {
 
@@ -142,22 +143,6 @@ void expand_compact_host(const fhe_compact_list& x, size_t first, size_t n, uint
 using namespace fhe;
 
 namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
-template <class F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        set_error("out of memory");
-        return FHE_ERR_ALLOC;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return FHE_ERR_INVALID;
-    }
-}
 bool seed_or_entropy(const uint8_t* given, uint8_t out[32]) {
     if (given) {
         std::memcpy(out, given, 32);
@@ -171,7 +156,7 @@ extern "C" {
 
 int fhe_public_key_generate(fhe_client_key* ck, const uint8_t* mask_seed, fhe_public_key** out) {
     if (!ck || !out) return invalid("null argument to fhe_public_key_generate");
-    return guarded([&] {
+    return guarded_alloc([&] {
         uint8_t seed[32];
         if (!seed_or_entropy(mask_seed, seed)) {
             set_error("getrandom failed: no mask seed");
@@ -199,7 +184,7 @@ int fhe_public_key_export(const fhe_public_key* pk, uint8_t* seed, uint64_t* bod
 
 int fhe_public_key_serialize(const fhe_public_key* pk, uint8_t* buf, size_t cap, size_t* len) {
     if (!pk || !len) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Writer w;
         w.b.reserve(80 + kPolySize * 8);
         w.params(pk->params);
@@ -211,7 +196,7 @@ int fhe_public_key_serialize(const fhe_public_key* pk, uint8_t* buf, size_t cap,
 
 int fhe_public_key_deserialize(const uint8_t* buf, size_t len, fhe_public_key** out) {
     if (!out) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Reader r;
         std::string why;
         Params p;
@@ -233,7 +218,7 @@ void fhe_public_key_destroy(fhe_public_key* pk) { delete pk; }
 
 int fhe_compact_builder_new(const fhe_public_key* pk, fhe_compact_builder** out) {
     if (!pk || !out) return invalid("null argument to fhe_compact_builder_new");
-    return guarded([&] {
+    return guarded_alloc([&] {
         auto b = std::make_unique<fhe_compact_builder>();
         b->pk = *pk;
         *out = b.release();
@@ -246,7 +231,7 @@ int fhe_compact_builder_push_radix(fhe_compact_builder* b, const uint64_t* words
     if (bits < 2 || bits > FHE_RADIX_MAX_BITS || bits % 2)
         return invalid("fhe_compact_builder_push_radix: num_bits must be even, >= 2 and <= FHE_RADIX_MAX_BITS");
     if (b->values.size() >= kCompactMaxValues) return invalid("compact list: more than 2^16 values");
-    return guarded([&] {
+    return guarded_alloc([&] {
         fhe_compact_list::Value v;
         v.form = FHE_SEEDED_RADIX;
         v.count = bits;
@@ -260,7 +245,7 @@ int fhe_compact_builder_push_biguint(fhe_compact_builder* b, const uint32_t* lim
     if (!b || (n && !limbs)) return invalid("null argument to fhe_compact_builder_push_biguint");
     if (n > kCompactMaxCoefs / kLimbBlocks) return invalid("fhe_compact_builder_push_biguint: nlimbs makes more than 2^24 coefficients");
     if (b->values.size() >= kCompactMaxValues) return invalid("compact list: more than 2^16 values");
-    return guarded([&] {
+    return guarded_alloc([&] {
         fhe_compact_list::Value v;
         v.form = FHE_SEEDED_BIGUINT;
         v.count = (uint32_t)n;
@@ -274,7 +259,7 @@ int fhe_compact_builder_push_biguint(fhe_compact_builder* b, const uint32_t* lim
 int fhe_compact_builder_build(const fhe_compact_builder* b, int packed, const uint8_t* encryption_seed,
                               fhe_compact_list** out) {
     if (!b || !out) return invalid("null argument to fhe_compact_builder_build");
-    return guarded([&] {
+    return guarded_alloc([&] {
         std::vector<fhe_compact_list::Value> values = b->values;
         std::string why;
         size_t ncoef = 0;
@@ -336,7 +321,7 @@ int fhe_compact_list_export(const fhe_compact_list* x, uint64_t* ca, size_t ca_w
 
 int fhe_compact_list_serialize(const fhe_compact_list* x, uint8_t* buf, size_t cap, size_t* len) {
     if (!x || !len) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Writer w;
         w.b.reserve(96 + 8 * (x->values.size() + x->ca.size() + x->cb.size()));
         w.params(x->params);
@@ -354,7 +339,7 @@ int fhe_compact_list_serialize(const fhe_compact_list* x, uint8_t* buf, size_t c
 
 int fhe_compact_list_deserialize(const uint8_t* buf, size_t len, fhe_compact_list** out) {
     if (!out) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Reader r;
         std::string why;
         Params p;
@@ -393,7 +378,7 @@ void fhe_compact_list_destroy(fhe_compact_list* x) { delete x; }
 int fhe_compact_list_expand_host(const fhe_compact_list* x, uint64_t* rows, size_t nwords) {
     if (!x || (!rows && x->ncoef()) || nwords < x->ncoef() * kBigCt)
         return invalid("invalid arguments to fhe_compact_list_expand_host (ncoef x 2049 words)");
-    return guarded([&] {
+    return guarded_alloc([&] {
         expand_compact_host(*x, 0, x->ncoef(), rows);
         return (int)FHE_OK;
     });
@@ -411,7 +396,7 @@ int fhe_compact_list_decrypt(const fhe_client_key* ck, const fhe_compact_list* x
                        std::to_string(want) + ")");
     const auto& v = x->values[index];
     if (nwords * 64 < 2 * v.nblocks) return invalid("fhe_compact_list_decrypt: output too small");
-    return guarded([&] {
+    return guarded_alloc([&] {
         std::memset(words, 0, nwords * 8);
         const uint64_t* S = ck->glwe_sk.data();
         std::vector<uint64_t> AS(kPolySize);

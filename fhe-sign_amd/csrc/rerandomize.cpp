@@ -8,6 +8,7 @@
 #include "fhe_rocm.h"
 #include "keygen.h"
 #include "public_key.h"
+#include "capi_internal.h"
 
 namespace fhe {
 
@@ -75,31 +76,12 @@ int fhe_ctx::release_public_key() {
     return FHE_OK;
 }
 
-namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
-template <class F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        set_error("out of memory");
-        return FHE_ERR_ALLOC;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return FHE_ERR_INVALID;
-    }
-}
-}  // namespace
-
 extern "C" {
 
 int fhe_rerandomize_host(const fhe_public_key* pk, const uint8_t* seed, uint64_t* cts, size_t nblocks) {
     if (!pk || !seed || (!cts && nblocks)) return invalid("null argument to fhe_rerandomize_host");
     if (nblocks > kCompactMaxCoefs) return invalid("fhe_rerandomize_host: more than 2^24 blocks");
-    return guarded([&] {
+    return guarded_alloc([&] {
         rerandomize_host(*pk, seed, cts, nblocks);
         return (int)FHE_OK;
     });
@@ -111,28 +93,20 @@ int fhe_rerandomize_zero_host(const fhe_public_key* pk, const uint8_t* seed, siz
     if (nblocks > kCompactMaxCoefs) return invalid("fhe_rerandomize_zero_host: more than 2^24 blocks");
     if (za_words < (nblocks + kPolySize - 1) / kPolySize * kPolySize || zb_words < nblocks)
         return invalid("fhe_rerandomize_zero_host: buffer too small (2048 words per chunk, one per block)");
-    return guarded([&] {
+    return guarded_alloc([&] {
         rerandomize_zero_host(*pk, seed, nblocks, za, zb);
         return (int)FHE_OK;
     });
 }
 
 int fhe_set_public_key(fhe_ctx* c, const fhe_public_key* pk) {
-    if (const int sim = refuse_simulated(c, "fhe_set_public_key")) return sim;
-    if (!c || !pk) return invalid("null argument to fhe_set_public_key");
-    if (!c->has_key || !c->engine) {
-        set_error("no server key installed: fhe_set_public_key comes after fhe_set_server_key");
-        return FHE_ERR_NO_KEY;
-    }
-    uint32_t have = 0, want = 0;
-    if (const char* f = params_differ(pk->params, c->p, &have, &want))
-        return invalid(std::string("public key's ") + f + " (" + std::to_string(have) +
-                       ") differs from the context's server key (" + std::to_string(want) + ")");
+    if (const int rc = dependent_key_preamble(c, pk != nullptr, "fhe_set_public_key", pk ? &pk->params : nullptr, "public key"))
+        return rc;
     if (pk->body.size() != kPolySize) return invalid("public key: the body is not 2048 words");
     FHE_HIP_CHECK(hipSetDevice(c->device));
     int rc = c->release_public_key();
     if (rc) return rc;
-    return guarded([&] {
+    return guarded_alloc([&] {
         std::vector<uint64_t> ab(2 * kPolySize);
         public_key_mask(pk->seed, ab.data());
         std::memcpy(ab.data() + kPolySize, pk->body.data(), kPolySize * 8);

@@ -6,7 +6,7 @@
 //   BSK mask polynomial of GGSW q, row rho (stream kStreamSeededBsk): words [2048 (2 q + rho), + 2048)
 // The two kernels here write, word for word, what keys.cpp:expand_seeded_server_key_host followed by the
 // full install (context.cpp) leaves on the device:
-//   k_expand_ksk          d_ksk [N ks_level][n + 1]: masks regenerated, body appended
+//   k_expand_ksk          a KsKeySet's ksk [N ks_level][n + 1]: masks regenerated, body appended
 //   k_expand_bsk_fourier  the Fourier BSK (k_bsk_to_fourier's layout and bits): a mask polynomial's
 //                         coefficients are generated into LDS instead of loaded, so the standard-domain
 //                         BSK never exists in device memory; a body polynomial is read from the upload

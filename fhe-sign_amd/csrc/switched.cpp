@@ -15,6 +15,7 @@
 #include "fhe_rocm.h"
 #include "oprf.h"
 #include "serial.h"
+#include "capi_internal.h"
 
 namespace fhe {
 
@@ -68,22 +69,6 @@ void keyswitch_host(const Params& p, const uint64_t* ksk, const uint64_t* ct, ui
 using namespace fhe;
 
 namespace {
-int invalid(const std::string& why) {
-    set_error(why);
-    return FHE_ERR_INVALID;
-}
-template <class F>
-int guarded(F&& f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        set_error("out of memory");
-        return FHE_ERR_ALLOC;
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return FHE_ERR_INVALID;
-    }
-}
 int check_rows(const char* who, uint32_t n, size_t count, size_t stride, size_t byte_stride) {
     if (n < 1 || n > kBigDim) return invalid(std::string(who) + ": n must be 1 .. 2048");
     if (stride < (size_t)n + 1) return invalid(std::string(who) + ": stride must be at least n + 1 words");
@@ -142,7 +127,7 @@ int compress_host(const Params& p, const std::vector<uint64_t>& ksk, int ms_mode
         if (degrees[i] >= 16) return invalid("fhe_switched_compress_host: block degree >= 16");
     if (ksk.size() != (size_t)kBigDim * p.ks_level * (p.n + 1))
         return invalid("fhe_switched_compress_host: the KSK does not match its parameters");
-    return guarded([&] {
+    return guarded_alloc([&] {
         auto x = std::make_unique<fhe_switched_list>();
         x->params = p;
         x->form = form;
@@ -184,7 +169,7 @@ int fhe_switched_compress_host(const fhe_server_key* sk, int ms_mode, const uint
 int fhe_switched_compress_host_rekeyed(const fhe_rekey_key* key, int ms_mode, const uint64_t* cts, size_t nblocks,
                                        const uint8_t* degrees, uint32_t form, uint32_t count, fhe_switched_list** out) {
     if (!key) return invalid("null argument to fhe_switched_compress_host_rekeyed");
-    return guarded([&] {
+    return guarded_alloc([&] {
         std::vector<uint64_t> ksk;
         expand_rekey_key_host(*key, &ksk);
         return compress_host(key->params, ksk, ms_mode, cts, nblocks, degrees, form, count, out);
@@ -210,7 +195,7 @@ int fhe_rekey_key_generate(const fhe_client_key* src, fhe_client_key* dst, const
         set_error("getrandom failed: no mask seed");
         return FHE_ERR_UNSUPPORTED;
     }
-    return guarded([&] {
+    return guarded_alloc([&] {
         auto k = std::make_unique<fhe_rekey_key>();
         generate_rekey_key(src, dst, seed, k.get());
         *out = k.release();
@@ -226,7 +211,7 @@ int fhe_rekey_key_params(const fhe_rekey_key* key, fhe_params* out) {
 
 int fhe_rekey_key_serialize(const fhe_rekey_key* key, uint8_t* buf, size_t cap, size_t* len) {
     if (!key || !len) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Writer w;
         w.b.reserve(80 + key->bodies.size() * 8);
         w.params(key->params);
@@ -238,7 +223,7 @@ int fhe_rekey_key_serialize(const fhe_rekey_key* key, uint8_t* buf, size_t cap, 
 
 int fhe_rekey_key_deserialize(const uint8_t* buf, size_t len, fhe_rekey_key** out) {
     if (!out) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Reader r;
         std::string why;
         Params p;
@@ -262,7 +247,7 @@ int fhe_rekey_key_expand_host(const fhe_rekey_key* key, uint64_t* ksk, size_t le
     const size_t need = (size_t)kPolySize * key->params.ks_level * (key->params.n + 1);
     if (len < need || key->bodies.size() != (size_t)kPolySize * key->params.ks_level)
         return invalid("fhe_rekey_key_expand_host: buffer too small");
-    return guarded([&] {
+    return guarded_alloc([&] {
         std::vector<uint64_t> v;
         expand_rekey_key_host(*key, &v);
         std::memcpy(ksk, v.data(), need * 8);
@@ -288,7 +273,7 @@ int fhe_switched_list_params(const fhe_switched_list* x, fhe_params* main) {
 
 int fhe_switched_list_serialize(const fhe_switched_list* x, uint8_t* buf, size_t cap, size_t* len) {
     if (!x || !len) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Writer w;
         w.b.reserve(64 + x->degrees.size() + x->rows.size());
         w.params(x->params);
@@ -303,7 +288,7 @@ int fhe_switched_list_serialize(const fhe_switched_list* x, uint8_t* buf, size_t
 
 int fhe_switched_list_deserialize(const uint8_t* buf, size_t len, fhe_switched_list** out) {
     if (!out) return FHE_ERR_INVALID;
-    return guarded([&] {
+    return guarded_alloc([&] {
         ser::Reader r;
         std::string why;
         Params p;
@@ -344,7 +329,7 @@ int fhe_switched_decrypt(const fhe_client_key* ck, const fhe_switched_list* x, u
                        std::to_string(want) + ")");
     const uint32_t bits = x->form == FHE_SEEDED_RADIX ? x->count : 32 * x->count;
     if ((uint64_t)nwords * 64 < bits) return invalid("fhe_switched_decrypt: output too small");
-    return guarded([&] {
+    return guarded_alloc([&] {
         const uint32_t n = x->params.n;
         const size_t B = x->degrees.size(), bytes = switched_row_bytes(n);
         std::vector<uint32_t> vals(B);

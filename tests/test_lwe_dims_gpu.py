@@ -443,3 +443,84 @@ def test_rekey_through_broadcast_install():
     finally:
         root.close()
         recv.close()
+
+
+def _broadcast_log(sk):
+    """what a root holding `sk` sends: header, KSK, Fourier BSK"""
+    log = []
+    root = Context(0)
+    try:
+        root.set_server_key(sk)
+        keep = _attach_replay(root, 0, log)
+        root.broadcast_server_key(0)
+        root.detach_comm()
+        del keep
+    finally:
+        root.close()
+    assert len(log) == 3
+    return log
+
+
+def test_broadcast_install_drops_the_receivers_dependants():
+    """a receiver that holds a compression key, a public key and a re-keying key: the received server key
+    drops all three, as a direct install does (fhe_ctx::adopt_key_params) -- their entry points answer
+    FHE_ERR_NO_KEY -- and bootstraps under the received key are the oracle's words"""
+    from fhe_sign import CompactPublicKey, CompressionKeys, CompressionParams, RekeyKey
+    import compress_ref
+
+    tables = _luts()
+    ck, sk, ok = _keys(16, CLASSIC)
+    cp = compress_ref.SMALL_A
+    recv = Context(0)
+    try:
+        recv.set_server_key(sk)
+        recv.set_compression_key(CompressionKeys.generate(ck, CompressionParams(cp.k, cp.N, cp.L, cp.beta, cp.ell, cp.noise, 12))[1])
+        recv.set_public_key(CompactPublicKey.new(ck))
+        recv.set_rekey_key(RekeyKey.new(ck, generate_keys(product_params(15), seed=SEED)[0], bytes(range(9, 41))))
+        set_server_key(recv)
+        x = FheUint32.try_encrypt(7, ck)
+        dependants = (x.compress, lambda: x.re_randomize(bytes(range(3, 35))), lambda: x.compress_switched(rekey=True))
+        for call in dependants:
+            call()  # installed: each one runs
+        log = _broadcast_log(sk)
+        keep = _attach_replay(recv, 1, log)
+        recv.broadcast_server_key(0)
+        recv.detach_comm()
+        del keep
+        assert not log
+        for call in dependants:
+            with pytest.raises(FheError) as e:
+                call()
+            assert e.value.code == -3  # FHE_ERR_NO_KEY
+        del x
+        ids = np.array([recv.lut(t) for t in tables], np.uint32)
+        _rekey_checks(recv, ok, ids, tables, 8, 8, "received over dependants")
+    finally:
+        set_server_key(None)
+        recv.close()
+
+
+def test_failed_broadcast_leaves_the_installed_key():
+    """the root's last message (the Fourier BSK) never arrives: the transport reports a failed collective,
+    broadcast_server_key raises, and the receiver's installed key, its row space (sized by 300 bootstraps) and
+    its lookup tables are what they were -- the same words, the same ids.  The key on the wire is another one
+    of the same parameters, so a half-installed key would show as different words."""
+    tables = _luts()
+    _, sk, ok = _keys(16, CLASSIC)
+    recv = Context(0)
+    try:
+        recv.set_server_key(sk)
+        ids = np.array([recv.lut(t) for t in tables], np.uint32)
+        before = _rekey_checks(recv, ok, ids, tables, 300, 300, "installed key")
+        log = _broadcast_log(generate_keys(product_params(16), seed=SEED + 1)[1])
+        log.pop()
+        keep = _attach_replay(recv, 1, log)
+        with pytest.raises(FheError):
+            recv.broadcast_server_key(0)
+        recv.detach_comm()
+        del keep
+        after = _rekey_checks(recv, ok, ids, tables, 8, 8, "installed key after a failed broadcast")
+        assert np.array_equal(after, before[:8])
+        assert [recv.lut(t) for t in tables] == list(ids)
+    finally:
+        recv.close()

@@ -1,4 +1,4 @@
-// device_buf_host_check.cpp -- stand-alone driver of DeviceBuf (fhe-sign_amd/csrc/device_buf.h; no GPU call) over
+// device_buf_host_check.cpp -- stand-alone driver of DeviceBuf, GroupCap and RowSpace (fhe-sign_amd/csrc/device_buf.h; no GPU call) over
 // an allocator backed by malloc / free, for a host AddressSanitizer + UndefinedBehaviorSanitizer run with its own
 // main: a double free, a use after free or a leak of the buffer's is then the sanitizer's to report.
 //   clang++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -D__HIP_PLATFORM_AMD__ \
@@ -58,22 +58,28 @@ static bool usable(const Buf& b) {
     return true;
 }
 
-// the ensure_* pattern of the context: one count over a group, 0 while the group is touched
+// a workspace as the context builds one: three buffers under a GroupCap, floor 256 (fhe_ctx::ensure_stage)
 struct Group {
     Buf a, b, c;
-    size_t cap = 0;
+    fhe::GroupCap cap;
     hipError_t ensure(size_t count) {
-        if (count <= cap) return hipSuccess;
-        cap = 0;
-        const size_t want = count < 256 ? 256 : count;
-        hipError_t e;
-        if ((e = a.grow(want * 3)) != hipSuccess) return e;
-        if ((e = b.grow(want * 3)) != hipSuccess) return e;
-        if ((e = c.grow(want)) != hipSuccess) return e;
-        cap = want;
-        return hipSuccess;
+        if (cap.fits(count)) return hipSuccess;
+        return cap.regrow(count, 256, [&](size_t n) { return fhe::grow_each(a, n * 3, b, n * 3, c, n); });
     }
 };
+// a row space with two more buffers in its group (fhe_ctx::ensure_cms), rows of dimension n
+struct Rows {
+    fhe::RowSpaceOf<FakeAlloc> rs;
+    Buf x, y;
+    hipError_t ensure(size_t count, size_t n) {
+        if (rs.fits(count)) return hipSuccess;
+        return rs.regrow(count, n, [&](size_t cap) { return fhe::grow_each(x, cap * 2, y, cap); });
+    }
+};
+// empty, or whole at the old or at the new count
+static bool whole_or_empty(const Buf& b, size_t was, size_t now) {
+    return (!b && b.capacity() == 0) || ((b.capacity() == was || b.capacity() == now) && usable(b));
+}
 
 static int checks() {
     F::start();
@@ -164,17 +170,54 @@ static int checks() {
     F::start();
     {  // a three-buffer group: the second allocation of a regrowth fails, the next call regrows it whole
         Group g;
-        CHECK(g.ensure(8) == hipSuccess && g.cap == 256 && F::live == 3);
+        CHECK(g.ensure(8) == hipSuccess && g.cap.get() == 256 && F::live == 3);
         CHECK(g.ensure(200) == hipSuccess && F::allocs == 3);  // inside the floor: nothing moves
         F::fail_alloc = 2;
         CHECK(g.ensure(300) == hipErrorOutOfMemory);
-        CHECK(g.cap == 0 && g.a.capacity() == 900 && !g.b && g.b.capacity() == 0 && g.c.capacity() == 256 && F::live == 2);
+        CHECK(g.cap.get() == 0 && g.a.capacity() == 900 && !g.b && g.b.capacity() == 0 && g.c.capacity() == 256 && F::live == 2);
         CHECK(g.ensure(8) == hipSuccess);  // even a small request: the count says nothing is there
-        CHECK(g.cap == 256 && g.a.capacity() == 768 && g.b.capacity() == 768 && g.c.capacity() == 256 && F::live == 3);
+        CHECK(g.cap.get() == 256 && g.a.capacity() == 768 && g.b.capacity() == 768 && g.c.capacity() == 256 && F::live == 3);
         CHECK(usable(g.a) && usable(g.b) && usable(g.c));
-        CHECK(g.ensure(300) == hipSuccess && g.cap == 300 && g.c.capacity() == 300 && F::live == 3);
+        CHECK(g.ensure(300) == hipSuccess && g.cap.get() == 300 && g.c.capacity() == 300 && F::live == 3);
     }
     CHECK(F::live == 0 && F::allocs == F::frees + 1);  // one allocation failed, every other one was freed once
+
+    for (int k = 1; k <= 3; ++k) {  // the k-th allocation of a regrowth fails, for every buffer of both groups
+        F::start();
+        {
+            Group g;
+            CHECK(g.ensure(8) == hipSuccess);
+            F::fail_alloc = k;
+            CHECK(g.ensure(300) == hipErrorOutOfMemory && g.cap.get() == 0 && !g.cap.fits(1) && F::live == 2);
+            CHECK(whole_or_empty(g.a, 768, 900) && whole_or_empty(g.b, 768, 900) && whole_or_empty(g.c, 256, 300));
+            CHECK(!(k == 1 ? g.a : k == 2 ? g.b : g.c));
+            F::sizes.clear();
+            CHECK(g.ensure(300) == hipSuccess && g.cap.get() == 300 && F::live == 3);
+            CHECK(F::sizes == (std::vector<size_t>{900 * 8, 900 * 8, 300 * 8}));
+            CHECK(usable(g.a) && usable(g.b) && usable(g.c));
+        }
+        CHECK(F::live == 0);
+        F::start();
+        {
+            Rows r;  // n = 16: stride 24; n = 834: stride 840
+            CHECK(r.rs.stride() == 0 && r.rs.cap() == 0 && r.rs.rows() == nullptr);
+            CHECK(r.ensure(8, 16) == hipSuccess && r.rs.cap() == 256 && r.rs.stride() == 24 && F::live == 3);
+            CHECK(F::sizes == (std::vector<size_t>{256 * 24 * 8, 512 * 8, 256 * 8}));
+            F::fail_alloc = k;
+            CHECK(r.ensure(300, 16) == hipErrorOutOfMemory && r.rs.cap() == 0 && r.rs.stride() == 0 && F::live == 2);
+            CHECK(whole_or_empty(r.x, 512, 600) && whole_or_empty(r.y, 256, 300));
+            CHECK(k == 1 ? r.rs.rows() == nullptr : !(k == 2 ? r.x : r.y));
+            F::sizes.clear();
+            CHECK(r.ensure(8, 16) == hipSuccess && r.rs.cap() == 256 && r.rs.stride() == 24 && F::live == 3);
+            CHECK(F::sizes == (std::vector<size_t>{256 * 24 * 8, 512 * 8, 256 * 8}));
+            CHECK(r.rs.drop() == hipSuccess && r.rs.cap() == 0 && r.rs.stride() == 0 && !r.rs.rows() && F::live == 2);
+            F::sizes.clear();  // another dimension after a drop: the stride is the new one's
+            CHECK(r.ensure(300, 834) == hipSuccess && r.rs.cap() == 300 && r.rs.stride() == 840);
+            CHECK(F::sizes == (std::vector<size_t>{300 * 840 * 8, 600 * 8, 300 * 8}));
+            for (size_t i = 0; i < 300 * 840; ++i) r.rs.rows()[i] = i;  // every row is the buffer's to write
+        }
+        CHECK(F::live == 0);
+    }
     return 0;
 }
 
