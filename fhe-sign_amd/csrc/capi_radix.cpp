@@ -21,7 +21,10 @@ namespace {
 
 // sim_ok: the entry point runs on a simulated context too (fhe_host_sim_ctx_create: the radix and BigUintFHE
 // arithmetic, their encryptions and decryptions); every other one refuses it
-int need_engine(fhe_ctx* c, bool sim_ok = false) {
+// need_rows: the row-level hooks, which take blocks of any message space.  need_engine: every entry point that makes,
+// reads or computes on a radix value; on top it asks Params::radix_space() of the installed key, before anything
+// is encrypted, recorded or launched (the "LUT table size" check in Engine::run stays as the backstop).
+int need_rows(fhe_ctx* c, bool sim_ok = false) {
     if (!c) {
         set_error("null context");
         return FHE_ERR_INVALID;
@@ -36,6 +39,11 @@ int need_engine(fhe_ctx* c, bool sim_ok = false) {
         return FHE_ERR_HIP;
     }
     return FHE_OK;
+}
+
+int need_engine(fhe_ctx* c, bool sim_ok = false) {
+    if (const int rc = need_rows(c, sim_ok)) return rc;
+    return radix_space_check(c);
 }
 
 uint32_t word_bits(const uint64_t* w, uint32_t bit, uint32_t nbits_total) {
@@ -239,6 +247,7 @@ int fhe_radix_encrypt(fhe_ctx* c, fhe_client_key* ck, const uint64_t* words, uin
 
 int fhe_radix_trivial(fhe_ctx* c, const uint64_t* words, uint32_t bits, fhe_radix** out) {
     if (!c || !words || !out || !valid_bits(bits)) return FHE_ERR_INVALID;
+    if (const int rc = radix_space_check(c)) return rc;
     Radix r;
     for (uint32_t k = 0; k < bits / 2; ++k) r.blocks.push_back(Block::make_trivial(word_bits(words, 2 * k, bits)));
     *out = wrap(std::move(r), bits);
@@ -655,6 +664,11 @@ int fhe_ctx_lut_table(fhe_ctx* c, uint32_t id, int* kind, int32_t entries[16]) {
         } else if (key.size() == 3 && key[0] == 0xFFFFFFFEu) {
             *kind = FHE_LUT_OPRF;
             entries[0] = (int32_t)key[2];
+        } else if (mods > 16 && (key.size() == mods || (key.size() == (size_t)mods + 1 && key[0] == 0xFFFFFFFFu))) {
+            // entries[] is the radix layer's 16: the hook reads tables of message spaces up to 16 values
+            set_error("fhe_ctx_lut_table: a table of " + std::to_string(mods) + " entries (message_modulus * carry_modulus of the " +
+                      "installed key); the hook reports at most 16");
+            return FHE_ERR_INVALID;
         } else {
             set_error("fhe_ctx_lut_table: a table of no known kind");
             return FHE_ERR_INVALID;
@@ -1199,6 +1213,7 @@ extern "C" {
 int fhe_radix_encrypt_seeded(fhe_client_key* ck, const uint64_t* words, uint32_t bits, const uint8_t* mask_seed,
                              fhe_seeded** out) {
     if (!ck || !words || !out || !valid_bits(bits)) return invalid("invalid arguments to fhe_radix_encrypt_seeded");
+    if (!ck->params.radix_space()) return invalid(radix_space_refusal(ck->params, "fhe_radix_encrypt_seeded"));
     std::vector<uint64_t> pts(bits / 2);
     for (uint32_t k = 0; k < bits / 2; ++k) pts[k] = (uint64_t)word_bits(words, 2 * k, bits) * ck->params.delta();
     return seeded_encrypt(ck, FHE_SEEDED_RADIX, bits, pts, mask_seed, out);
@@ -1207,6 +1222,7 @@ int fhe_radix_encrypt_seeded(fhe_client_key* ck, const uint64_t* words, uint32_t
 int fhe_biguint_encrypt_seeded(fhe_client_key* ck, const uint32_t* limbs, size_t n, const uint8_t* mask_seed,
                                fhe_seeded** out) {
     if (!ck || !out || (n && !limbs)) return invalid("invalid arguments to fhe_biguint_encrypt_seeded");
+    if (!ck->params.radix_space()) return invalid(radix_space_refusal(ck->params, "fhe_biguint_encrypt_seeded"));
     if (n > kSeededMaxBlocks / kLimbBlocks)
         return invalid("seeded BigUintFHE: more than 2^24 blocks (the mask stream's 32-bit block counter)");
     return guarded([&] {
@@ -1247,6 +1263,7 @@ int fhe_seeded_deserialize(const uint8_t* buf, size_t len, fhe_seeded** out) {
         std::string why;
         Params p;
         if (!ser::unframe(buf, len, ser::kSeeded, &r, &why) || !r.params(&p, &why)) return invalid(why);
+        if (!p.radix_space()) return invalid(radix_space_refusal(p, "seeded object"));
         const uint32_t form = r.u32(), count = r.u32();
         size_t nblocks = 0;
         if (!r.ok) return invalid("truncated seeded header");
@@ -1324,7 +1341,7 @@ int compress_blocks(fhe_ctx* c, const std::vector<const Block*>& blocks, uint32_
         x->form = form;
         x->count = count;
         for (const Block* b : blocks) {
-            engine_check(b->degree < 16, "compress: block degree >= 16");
+            engine_check(b->degree < c->p.msg_carry(), "compress: block degree >= message_modulus * carry_modulus");
             x->degrees.push_back((uint8_t)b->degree);
         }
         x->packed.resize(c->cp.packed_bytes(blocks.size()));
@@ -1333,8 +1350,8 @@ int compress_blocks(fhe_ctx* c, const std::vector<const Block*>& blocks, uint32_
         return FHE_OK;
     });
 }
-int compressed_expand_check(fhe_ctx* c, const fhe_compressed_list* x, uint32_t form) {
-    int rc = need_engine(c);
+int compressed_expand_check(fhe_ctx* c, const fhe_compressed_list* x, uint32_t form, bool rows = false) {
+    int rc = rows ? need_rows(c) : need_engine(c);
     if (rc) return rc;
     if (!x) return invalid("null compressed list");
     if (!c->has_comp) {
@@ -1410,7 +1427,7 @@ int fhe_compressed_expand_biguint(fhe_ctx* c, const fhe_compressed_list* x, fhe_
 
 int fhe_compressed_extract_rows(fhe_ctx* c, const fhe_compressed_list* x, uint64_t* rows, size_t nwords) {
     if (!x) return invalid("null compressed list");
-    int rc = compressed_expand_check(c, x, x->form);
+    int rc = compressed_expand_check(c, x, x->form, true);
     if (rc) return rc;
     if (!rows || nwords < x->degrees.size() * ((size_t)x->cp.lwe_dim() + 1)) return invalid("fhe_compressed_extract_rows: buffer too small");
     return guarded([&] {
@@ -1421,7 +1438,7 @@ int fhe_compressed_extract_rows(fhe_ctx* c, const fhe_compressed_list* x, uint64
 
 int fhe_pack_keyswitch_words(fhe_ctx* c, const uint64_t* cts, size_t count, uint64_t* P, size_t p_words,
                              uint64_t* body) {
-    int rc = need_engine(c);
+    int rc = need_rows(c);
     if (rc) return rc;
     if (!c->has_comp) {
         set_error("no compression key installed (fhe_set_compression_key)");
@@ -1454,7 +1471,7 @@ int switched_blocks(fhe_ctx* c, const std::vector<const Block*>& blocks, uint32_
         x->form = form;
         x->count = count;
         for (const Block* b : blocks) {
-            engine_check(b->degree < 16, "compress_switched: block degree >= 16");
+            engine_check(b->degree < x->params.msg_carry(), "compress_switched: block degree >= message_modulus * carry_modulus");
             x->degrees.push_back((uint8_t)b->degree);
         }
         x->rows.resize(blocks.size() * switched_row_bytes(x->params.n));
@@ -1626,8 +1643,8 @@ int fhe_compact_list_extract_rows(fhe_ctx* c, const fhe_compact_list* x, uint64_
 // schnorr.cpp.
 namespace {
 // the checks of every re-randomization, before anything is flushed or launched; seed32 = the call's seed
-int rerandomize_check(fhe_ctx* c, const uint8_t* seed, uint8_t seed32[32]) {
-    int rc = need_engine(c);
+int rerandomize_check(fhe_ctx* c, const uint8_t* seed, uint8_t seed32[32], bool rows = false) {
+    int rc = rows ? need_rows(c) : need_engine(c);
     if (rc) return rc;
     if (!c->has_pk) {
         set_error("no public key installed (fhe_set_public_key)");
@@ -1702,10 +1719,10 @@ int fhe_rerandomize_rows(fhe_ctx* c, const uint8_t* seed, const uint64_t* rows, 
     if (!seed || ((!rows || !out) && nblocks)) return invalid("null argument to fhe_rerandomize_rows");
     if (nblocks > kCompactMaxCoefs) return invalid("fhe_rerandomize_rows: more than 2^24 blocks");
     uint8_t seed32[32];
-    int rc = rerandomize_check(c, seed, seed32);
+    int rc = rerandomize_check(c, seed, seed32, true);
     if (rc || !nblocks) return rc;
     return guarded([&] {
-        const Blocks in = c->engine->upload_many(rows, nblocks, kMsgMod - 1);
+        const Blocks in = c->engine->upload_many(rows, nblocks, std::min(kMsgMod, c->p.msg_carry()) - 1);
         std::vector<const Block*> blocks;
         for (const Block& b : in) blocks.push_back(&b);
         const Blocks res = c->engine->rerandomize(blocks, seed32);
@@ -1792,10 +1809,10 @@ int fhe_rerand_context_add_biguint(fhe_ctx* c, fhe_rerand_context* rc, const fhe
 int fhe_ct_digest_rows(fhe_ctx* c, const uint64_t* rows, size_t nblocks, uint8_t* out) {
     if ((!rows || !out) && nblocks) return invalid("null argument to fhe_ct_digest_rows");
     if (nblocks > kCtDigestMaxRows) return invalid("fhe_ct_digest_rows: more than 2^24 blocks");
-    int rc = need_engine(c);
+    int rc = need_rows(c);
     if (rc || !nblocks) return rc;
     return guarded([&] {
-        const Blocks in = c->engine->upload_many(rows, nblocks, kMsgMod - 1);
+        const Blocks in = c->engine->upload_many(rows, nblocks, std::min(kMsgMod, c->p.msg_carry()) - 1);
         std::vector<const Block*> blocks;
         for (const Block& b : in) blocks.push_back(&b);
         c->engine->digest(blocks, out);

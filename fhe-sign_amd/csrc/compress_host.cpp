@@ -579,7 +579,8 @@ int fhe_compress_host(const fhe_compression_key* key, const uint64_t* cts, size_
     if (!compressed_nblocks(form, count, &want, &why)) return invalid(why);
     if (want != nblocks) return invalid("fhe_compress_host: nblocks does not match form / count");
     for (size_t i = 0; i < nblocks; ++i)
-        if (degrees[i] >= 16) return invalid("fhe_compress_host: block degree >= 16");
+        if (degrees[i] >= key->params.msg_carry())
+            return invalid("fhe_compress_host: block degree >= message_modulus * carry_modulus = " + std::to_string(key->params.msg_carry()));
     return guarded_alloc([&] {
         auto x = std::make_unique<fhe_compressed_list>();
         x->params = key->params;
@@ -644,7 +645,8 @@ int fhe_compressed_deserialize(const uint8_t* buf, size_t len, fhe_compressed_li
         if (r.n - r.off != (size_t)B + cp.packed_bytes(B))
             return invalid("compressed list: payload length differs from what its parameters and block count need");
         for (size_t i = 0; i < B; ++i)
-            if (r.p[r.off + i] >= 16) return invalid("compressed list: block degree >= 16");
+            if (r.p[r.off + i] >= p.msg_carry())
+                return invalid("compressed list: block degree >= message_modulus * carry_modulus = " + std::to_string(p.msg_carry()));
         auto x = std::make_unique<fhe_compressed_list>();
         x->params = p;
         x->cp = cp;

@@ -137,6 +137,12 @@ int refuse_simulated(const fhe_ctx* c, const char* what) {
     return FHE_ERR_INVALID;
 }
 
+int radix_space_check(const fhe_ctx* c) {
+    if (!c || !c->has_key || c->p.radix_space()) return FHE_OK;
+    set_error(radix_space_refusal(c->p, "the context's server key"));
+    return FHE_ERR_INVALID;
+}
+
 }  // namespace fhe
 
 using namespace fhe;

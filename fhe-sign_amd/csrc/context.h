@@ -25,6 +25,9 @@ void set_error(const std::string& msg);
 const char* last_error();
 // FHE_OK on a device context; on a simulated one FHE_ERR_INVALID with a message that names it and `what`
 int refuse_simulated(const fhe_ctx* c, const char* what);
+// FHE_OK if the context's installed key is of the radix layer's message space (Params::radix_space) or no key is
+// installed (the entry point's own checks answer that); else FHE_ERR_INVALID with radix_space_refusal's text
+int radix_space_check(const fhe_ctx* c);
 #define FHE_HIP_CHECK(expr)                                                                   \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \

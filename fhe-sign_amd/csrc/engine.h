@@ -30,6 +30,9 @@ namespace fhe {
 
 constexpr uint32_t kMsgBits = 2;
 constexpr uint32_t kMsgMod = 4;
+// Params::radix_space() (keys.h) is the predicate of these two: a key of any other message space bootstraps raw
+// blocks on this engine, and every radix entry point refuses it at the door
+static_assert(kMsgMod == 1u << kMsgBits && kMsgMod == 4, "Params::radix_space() states message_modulus 4, carry_modulus 4");
 constexpr uint32_t kMaxNoise = 25;  // variance units (sigma <= 5 fresh sigmas, tfhe-rs 2_2 max noise level 5)
 
 // Size rules of the radix algorithms that tests move (fhe_host_set_tuning; process-wide, set before

@@ -6,6 +6,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "fhe_rocm.h"
@@ -44,7 +45,20 @@ struct Params {
         const uint64_t s0 = lwe_sk[2 * i] & 1, s1 = lwe_sk[2 * i + 1] & 1;
         return ((B & 1) ? s0 : 1 - s0) & ((B & 2) ? s1 : 1 - s1);
     }
+    // The one rule of the radix layer (FheUint, BigUintFHE, and their seeded, compact, stored and signed forms):
+    // it cuts values into 2-bit digits with 2 carry bits above them (engine.h kMsgBits / kMsgMod, 16-entry tables),
+    // so it needs message_modulus 4 and carry_modulus 4 exactly -- not another split of 16, and no other product.
+    // Keys, block encryption, LUTs, the raw bootstrap, the keyswitch, OPRF blocks and the block-level stored lists
+    // take any space Params::from_c admits.  Every radix entry point asks this before it encrypts, records or
+    // launches anything (radix_space_refusal is its answer).
+    bool radix_space() const { return message_modulus == 4 && carry_modulus == 4; }
 };
+
+// the text of a refusal under Params::radix_space: `who` names the entry point or the object
+inline std::string radix_space_refusal(const Params& p, const char* who) {
+    return std::string(who) + ": the radix layer needs message_modulus 4 and carry_modulus 4; this key has message_modulus " +
+           std::to_string(p.message_modulus) + ", carry_modulus " + std::to_string(p.carry_modulus);
+}
 
 // (The parameters and keys of the compressed computed ciphertexts -- tfhe-rs' compression parameters AS
 // RECALLED, like the defaults above -- are in compress.h: CompParams, fhe_compression_key.)

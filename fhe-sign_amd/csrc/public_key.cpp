@@ -228,6 +228,8 @@ int fhe_compact_builder_new(const fhe_public_key* pk, fhe_compact_builder** out)
 
 int fhe_compact_builder_push_radix(fhe_compact_builder* b, const uint64_t* words, uint32_t bits) {
     if (!b || !words) return invalid("null argument to fhe_compact_builder_push_radix");
+    // a list holds radix values, 2-bit digits (packed: two to a coefficient): refused where the first would be cut
+    if (!b->pk.params.radix_space()) return invalid(radix_space_refusal(b->pk.params, "fhe_compact_builder_push_radix"));
     if (bits < 2 || bits > FHE_RADIX_MAX_BITS || bits % 2)
         return invalid("fhe_compact_builder_push_radix: num_bits must be even, >= 2 and <= FHE_RADIX_MAX_BITS");
     if (b->values.size() >= kCompactMaxValues) return invalid("compact list: more than 2^16 values");
@@ -243,6 +245,7 @@ int fhe_compact_builder_push_radix(fhe_compact_builder* b, const uint64_t* words
 
 int fhe_compact_builder_push_biguint(fhe_compact_builder* b, const uint32_t* limbs, size_t n) {
     if (!b || (n && !limbs)) return invalid("null argument to fhe_compact_builder_push_biguint");
+    if (!b->pk.params.radix_space()) return invalid(radix_space_refusal(b->pk.params, "fhe_compact_builder_push_biguint"));
     if (n > kCompactMaxCoefs / kLimbBlocks) return invalid("fhe_compact_builder_push_biguint: nlimbs makes more than 2^24 coefficients");
     if (b->values.size() >= kCompactMaxValues) return invalid("compact list: more than 2^16 values");
     return guarded_alloc([&] {
@@ -344,6 +347,7 @@ int fhe_compact_list_deserialize(const uint8_t* buf, size_t len, fhe_compact_lis
         std::string why;
         Params p;
         if (!ser::unframe(buf, len, ser::kCompactList, &r, &why) || !r.params(&p, &why)) return invalid(why);
+        if (!p.radix_space()) return invalid(radix_space_refusal(p, "compact list"));
         const uint32_t packed = r.u32(), nvalues = r.u32();
         if (!r.ok) return invalid("truncated compact list header");
         if (packed > 1) return invalid("compact list: the packed flag is neither 0 nor 1");

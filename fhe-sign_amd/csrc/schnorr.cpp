@@ -565,6 +565,7 @@ extern "C" {
 static int sign_one(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, size_t len, const uint8_t k0[32],
                     const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, bool reduced, uint8_t sig[64]) {
     if (const int sim = fhe::refuse_simulated(ctx, "the signer")) return sim;
+    if (const int space = fhe::radix_space_check(ctx)) return space;  // before e and k are encrypted
     if (!sig) return FHE_ERR_INVALID;
     // before e and k are encrypted and uploaded: a refusal allocates nothing
     if (const int own = fhe::biguint_owned(ctx, privkey_fhe, "privkey_fhe")) return own;
@@ -610,6 +611,7 @@ int fhe_schnorr_eval_s(fhe_ctx* ctx, const fhe_biguint* e_fhe, const fhe_biguint
         set_error("invalid arguments to fhe_schnorr_eval_s (mode: FHE_BIGUINT_COMPAT or FHE_BIGUINT_FAST)");
         return FHE_ERR_INVALID;
     }
+    if (const int space = fhe::radix_space_check(ctx)) return space;
     if (const int own = fhe::biguint_owned(ctx, e_fhe, "e_fhe")) return own;
     if (const int own = fhe::biguint_owned(ctx, k_fhe, "k_fhe")) return own;
     if (const int own = fhe::biguint_owned(ctx, privkey_fhe, "privkey_fhe")) return own;
@@ -627,6 +629,7 @@ int fhe_schnorr_eval_s_public(fhe_ctx* ctx, const uint8_t e[32], const uint8_t k
         set_error("null argument to fhe_schnorr_eval_s_public");
         return FHE_ERR_INVALID;
     }
+    if (const int space = fhe::radix_space_check(ctx)) return space;
     if (const int own = fhe::biguint_owned(ctx, privkey_fhe, "privkey_fhe")) return own;
     return eval_s_public(ctx, U256::from_be(e), U256::from_be(k), privkey_fhe, s);
 }
@@ -638,6 +641,7 @@ static int sign_rerand(fhe_ctx* ctx, fhe_client_key* ck, const uint8_t* msg, siz
                        const uint8_t privkey[32], const fhe_biguint* privkey_fhe, int mode, const uint8_t* domain,
                        size_t domain_len, bool reduced, uint8_t sig[64]) {
     if (const int sim = fhe::refuse_simulated(ctx, "the signer")) return sim;
+    if (const int space = fhe::radix_space_check(ctx)) return space;  // before e and k are encrypted
     if (!ctx || !ck || (len && !msg) || !k0 || !privkey || !privkey_fhe || (domain_len && !domain) || !sig) {
         set_error("null argument to fhe_schnorr_sign_fhe_with_k0_rerand");
         return FHE_ERR_INVALID;
@@ -690,6 +694,7 @@ static int sign_batch(fhe_ctx* ctx, fhe_client_key* ck, size_t count, const uint
                       const uint8_t* k0s, const uint8_t* privkeys, const fhe_biguint* const* privkeys_fhe, int mode,
                       bool reduced, uint8_t* sigs) {
     if (const int sim = fhe::refuse_simulated(ctx, "the signer")) return sim;
+    if (const int space = fhe::radix_space_check(ctx)) return space;  // before e and k are encrypted
     if (count && (!msgs || !lens || !k0s || !privkeys || !privkeys_fhe || !sigs)) return FHE_ERR_INVALID;
     for (size_t i = 0; i < count; ++i)  // every key first: a refusal uploads nothing
         if (const int own = fhe::biguint_owned(ctx, privkeys_fhe[i], "privkeys_fhe")) return own;

@@ -30,7 +30,7 @@
 //           8 (2048 pks_level N' + 4096 k' N') bytes in all.  The masks are not stored: streams 107 (packing
 //           KSK) and 108 (decompression BSK) under the seed, one row per 256 ChaCha blocks (compress.h).
 //   kind 13 (modulus-switched stored list, switched.cpp): params | u32 form | u32 count | u32 B | B degree bytes
-//           (each < 16) | B rows of ceil(12 (n + 1) / 8) bytes, the 12-bit stream of a row's n + 1 values, the pad
+//           (each < mc) | B rows of ceil(12 (n + 1) / 8) bytes, the 12-bit stream of a row's n + 1 values, the pad
 //           nibble of an odd n + 1 zero -- 80 + B (1 + ceil(12 (n + 1) / 8)) bytes in all.
 //   kind 14 (re-keying key, switched.cpp): the DESTINATION's params | 32 seed bytes | 2048 ks_level u64 body words
 //           -- 100 + 8 (2048 ks_level) bytes in all.  The masks are not stored: stream 112 under the seed, one

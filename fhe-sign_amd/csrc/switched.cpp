@@ -124,7 +124,8 @@ int compress_host(const Params& p, const std::vector<uint64_t>& ksk, int ms_mode
     if (!compressed_nblocks(form, count, &want, &why)) return invalid(why);
     if (want != nblocks) return invalid("fhe_switched_compress_host: nblocks does not match form / count");
     for (size_t i = 0; i < nblocks; ++i)
-        if (degrees[i] >= 16) return invalid("fhe_switched_compress_host: block degree >= 16");
+        if (degrees[i] >= p.msg_carry())
+            return invalid("fhe_switched_compress_host: block degree >= message_modulus * carry_modulus = " + std::to_string(p.msg_carry()));
     if (ksk.size() != (size_t)kBigDim * p.ks_level * (p.n + 1))
         return invalid("fhe_switched_compress_host: the KSK does not match its parameters");
     return guarded_alloc([&] {
@@ -304,7 +305,8 @@ int fhe_switched_list_deserialize(const uint8_t* buf, size_t len, fhe_switched_l
         if (r.n - r.off != (size_t)B * (1 + bytes))
             return invalid("switched list: payload length differs from what its parameters and block count need");
         for (size_t i = 0; i < B; ++i)
-            if (r.p[r.off + i] >= 16) return invalid("switched list: block degree >= 16");
+            if (r.p[r.off + i] >= p.msg_carry())
+                return invalid("switched list: block degree >= message_modulus * carry_modulus = " + std::to_string(p.msg_carry()));
         if (!pads_zero(r.p + r.off + B, B, p.n)) return invalid("switched list: non-zero pad bits in a row");
         auto x = std::make_unique<fhe_switched_list>();
         x->params = p;

@@ -50,6 +50,6 @@ hipError_t launch_ms_unpack(const uint32_t* packed, uint64_t* ws, size_t count, 
 struct fhe_switched_list {
     fhe::Params params;
     uint32_t form = 0, count = 0;  // FHE_SEEDED_RADIX / FHE_SEEDED_BIGUINT semantics (compress.h compressed_nblocks)
-    std::vector<uint8_t> degrees;  // one per block, each < 16
+    std::vector<uint8_t> degrees;  // one per block, each < params.msg_carry()
     std::vector<uint8_t> rows;     // nblocks x switched_row_bytes(params.n)
 };

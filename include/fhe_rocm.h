@@ -87,13 +87,36 @@ typedef struct fhe_params {
     uint32_t ks_level;        /* 5 */
     uint32_t lwe_noise_log2;  /* TUniform bound, small key (45, recalled tfhe 0.10; 44 until r6) */
     uint32_t glwe_noise_log2; /* TUniform bound, big/GLWE key (17) */
-    uint32_t message_modulus; /* 4 */
-    uint32_t carry_modulus;   /* 4 */
+    uint32_t message_modulus; /* 4; a power of two, 2 .. 64 -- the message space, below */
+    uint32_t carry_modulus;   /* 4; a power of two, 1 .. 64, with message_modulus * carry_modulus <= 64 */
     uint32_t grouping;        /* blind rotation: 1 = classic (one CMUX per key bit, tfhe-rs'
                                  ClassicPBS, the default), 2 = multi-bit (tfhe-rs' MultiBitPBS shape:
                                  two key bits per external product, 3 GGSWs per pair; the client key
                                  and every decrypted result are unchanged).  0 is read as 1. */
 } fhe_params;
+/* The message space.  mc = message_modulus * carry_modulus values per block, delta = 2^63 / mc, one value's box
+ * in the accumulator polynomial 2048 / mc coefficients wide.
+ *   Any space: key generation and (de)serialization, fhe_encrypt_block(s) / fhe_decrypt_block, the resident
+ *     client key, fhe_lut_register (a table of exactly mc entries), fhe_pbs_batch(_device), fhe_keyswitch_batch,
+ *     fhe_pbs_lincomb_batch, fhe_oprf_blocks (bits <= log2 message_modulus), the compact public key, compression
+ *     and re-keying keys, fhe_compress_host / fhe_switched_compress_host and their readers (a block's degree
+ *     byte < mc), the row-level hooks.
+ *   Message 4, carry 4 exactly: everything that makes, reads or computes on a radix value -- fhe_radix_*,
+ *     fhe_biguint_*, fhe_columns_*, the seeded forms (fhe_*_encrypt_seeded, fhe_seeded_deserialize,
+ *     fhe_seeded_expand_*), compact lists (fhe_compact_builder_push_*, fhe_compact_list_deserialize,
+ *     fhe_compact_list_expand_*), fhe_compressed_expand_*, fhe_switched_expand_*, fhe_*_random*, and every
+ *     fhe_schnorr_* that takes a context.  Under a key of any other space -- another split of 16 included --
+ *     they return FHE_ERR_INVALID with a message that names message_modulus, before anything is encrypted,
+ *     recorded or launched; the client key's encryption stream does not move.
+ *   mc   box   half-box   half-box / sigma of the modulus switch at n = 834 (6.05 grid steps of 4096; derived)
+ *   2    1024  512        84.6
+ *   4    512   256        42.3
+ *   8    256   128        21.2
+ *   16   128   64         10.6
+ *   32   64    32         5.3
+ *   64   32    16         2.6  (about one wrong decode in 120 bootstraps: a space for small dimensions)
+ * Pinned word for word to the oracle at 2x1, 2x2, 4x2, 2x8, 8x2, 16x1, 4x8, 8x8, 64x1 (tests/test_msg_spaces_gpu.py);
+ * a context may be re-keyed between spaces: registered tables survive exactly when mc and delta do. */
 
 typedef struct fhe_client_key fhe_client_key;
 typedef struct fhe_server_key fhe_server_key;
@@ -489,7 +512,10 @@ int fhe_ctx_pending_info(fhe_ctx* ctx, uint64_t out[3]);
 int fhe_radix_block_addrs(fhe_ctx* ctx, const fhe_radix* x, uint64_t* addrs, uint32_t* values, size_t cap, size_t* n);
 int fhe_biguint_block_addrs(fhe_ctx* ctx, const fhe_biguint* x, uint64_t* addrs, uint32_t* values, size_t cap, size_t* n);
 /* the registered table `id`: its kind and entries -- an integer table's 16 outputs, a half-step table's 16 signed
- * outputs in half message steps, an OPRF staircase's bit count in entries[0] */
+ * outputs in half message steps, an OPRF staircase's bit count in entries[0].  A hook of the radix layer's tests:
+ * under a key of mc = message_modulus * carry_modulus <= 16 the first mc entries are the table and the rest 0;
+ * under a larger space an integer or half-step table has more entries than the hook holds, and the call returns
+ * FHE_ERR_INVALID with a message that says so ("the hook reports at most 16") */
 #define FHE_LUT_INTEGER 0
 #define FHE_LUT_HALF_STEP 1
 #define FHE_LUT_OPRF 2
@@ -852,13 +878,13 @@ int fhe_compression_key_deserialize(const uint8_t* buf, size_t len, fhe_compress
 
 /* CompressedCiphertextList holding ONE value.  Host object, needs no context.  Wire (kind 9): main params,
  * compression params (7 x u32), u32 form (FHE_SEEDED_RADIX / FHE_SEEDED_BIGUINT semantics), u32 count
- * (num_bits or nlimbs), u32 B (blocks), B degree bytes (each < 16), then per GLWE g = 0.. in order its
+ * (num_bits or nlimbs), u32 B (blocks), B degree bytes (each < mc of the main params), then per GLWE g = 0.. in order its
  * 12-bit values packed little-endian bit-contiguously (value i at bits [12 i, 12 i + 12)): k' N' mask
  * values, polynomial-major, then b_g = min(L, B - g L) bodies; every GLWE starts on a byte boundary:
  *   32 + 36 + 28 + 12 + B + sum_g ceil(12 (k' N' + b_g) / 8)  bytes. */
 typedef struct fhe_compressed_list fhe_compressed_list;
 /* The packing keyswitch on the host -- the word-for-word definition of the GPU path, and what a server
- * without a GPU uses: cts = nblocks x 2049 words, degrees = nblocks bytes (< 16), form / count as above
+ * without a GPU uses: cts = nblocks x 2049 words, degrees = nblocks bytes (< mc of the key), form / count as above
  * (count / 2, or 16 count, must equal nblocks). */
 int fhe_compress_host(const fhe_compression_key* key, const uint64_t* cts, size_t nblocks, const uint8_t* degrees,
                       uint32_t form, uint32_t count, fhe_compressed_list** out);
@@ -1231,8 +1257,8 @@ int fhe_biguint_random(fhe_ctx* ctx, const uint8_t seed[32] /* NULL: OS entropy 
  *          fhe_radix_decrypt assembles blocks.  The decode margin and the rounding noise are those of a
  *          bootstrap's modulus switch (see fhe_ctx_set_modulus_switch).
  * Wire (kind 13): main params, u32 form (FHE_SEEDED_RADIX / FHE_SEEDED_BIGUINT semantics), u32 count (num_bits or
- * nlimbs), u32 B (blocks), B degree bytes (each < 16), B rows:  80 + B (1 + ceil(12 (n + 1) / 8))  bytes.  The
- * reader refuses truncation, non-zero pad bits, a degree >= 16, a block count that does not match form / count
+ * nlimbs), u32 B (blocks), B degree bytes (each < mc of the main params), B rows:  80 + B (1 + ceil(12 (n + 1) / 8))  bytes.  The
+ * reader refuses truncation, non-zero pad bits, a degree >= mc, a block count that does not match form / count
  * and unsupported parameters. */
 typedef struct fhe_switched_list fhe_switched_list;
 /* The definitions on the host; no context, no GPU.  rows: count x stride words, stride >= n + 1, 1 <= n <= 2048,
@@ -1245,7 +1271,7 @@ int fhe_switched_unpack_host(const uint8_t* packed, size_t count, uint32_t n, si
                              size_t stride);
 /* The whole stored form on the host -- the word-for-word definition of fhe_radix_compress_switched, and what a
  * server without a GPU uses: ms_mode = FHE_MS_STANDARD / FHE_MS_CENTERED, cts = nblocks x 2049 words, degrees =
- * nblocks bytes (< 16), form / count as above (count / 2, or 16 count, must equal nblocks). */
+ * nblocks bytes (< mc = message_modulus * carry_modulus of the key), form / count as above (count / 2, or 16 count, must equal nblocks). */
 int fhe_switched_compress_host(const fhe_server_key* sk, int ms_mode, const uint64_t* cts, size_t nblocks,
                                const uint8_t* degrees, uint32_t form, uint32_t count, fhe_switched_list** out);
 int fhe_switched_list_info(const fhe_switched_list* x, uint32_t* form, uint32_t* count, size_t* nblocks);

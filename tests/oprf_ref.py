@@ -56,12 +56,14 @@ def values(rws, lwe_sk, bits):
     return np.where(m < N, m * p // (2 * N) + p // 2, p // 2 - 1 - (m - N) * p // (2 * N))
 
 
-def value_by_rotation(row, lwe_sk, bits, delta=DELTA):
+def value_by_rotation(row, lwe_sk, bits, delta=DELTA, mc=16):
     """the same for one row of n + 1 words through exact_pbs_ref.ideal_rotation: coefficient 0 of the noiseless
-    blind rotation of the accumulator, plus the body constant, decoded"""
+    blind rotation of the accumulator, plus the body constant, decoded in a message space of mc values
+    (delta = 2^63 / mc)"""
+    assert delta * mc == 1 << 63
     c0 = int(X.ideal_rotation(np.asarray(row, np.uint64)[:len(lwe_sk) + 1], lwe_sk, lut(bits, delta))[0])
     phase = (c0 + body_const(bits, delta)) % (1 << 64)
-    return ((phase + delta // 2) // delta) % 16
+    return ((phase + delta // 2) // delta) % mc
 
 
 def radix_value(seed32, lwe_sk, width_bits, random_bits):

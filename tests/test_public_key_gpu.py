@@ -244,12 +244,17 @@ def test_boundary_errors(env):
         FheUint.deserialize(x.serialize())
     # a parameter field that differs from the installed key's: refused at expansion, by name
     blob = bytearray(x.serialize())
-    struct.pack_into("<I", blob, 32 + 6 * 4, 2)  # message_modulus 4 -> 2
+    struct.pack_into("<I", blob, 32 + 5 * 4, 16)  # glwe_noise_log2 17 -> 16
     altered = CompactCiphertextList.deserialize(_refnv(blob))
-    with pytest.raises(FheError, match="message_modulus"):
+    with pytest.raises(FheError, match="glwe_noise_log2"):
         altered.expand()
-    with pytest.raises(FheError, match="message_modulus"):
+    with pytest.raises(FheError, match="glwe_noise_log2"):
         altered.extract_rows()
+    # a message space other than the radix layer's 4 x 4: the reader itself refuses it, by name
+    blob = bytearray(x.serialize())
+    struct.pack_into("<I", blob, 32 + 6 * 4, 2)  # message_modulus 4 -> 2
+    with pytest.raises(FheError, match="message_modulus"):
+        CompactCiphertextList.deserialize(_refnv(blob))
     a, b = x.expand()  # the context is as usable as before
     assert a.decrypt(ck) == 7 and b.to_biguint(ck) == 7
 

@@ -148,10 +148,15 @@ def test_boundary_errors(env):
         BigUintFHE.deserialize(b.serialize())
     # a parameter field that differs from the installed key's: refused at expansion, by name
     blob = bytearray(r.serialize())
-    struct.pack_into("<I", blob, 32 + 6 * 4, 2)  # message_modulus 4 -> 2
+    struct.pack_into("<I", blob, 32 + 5 * 4, 16)  # glwe_noise_log2 17 -> 16
     altered = CompressedFheUint.deserialize(_refnv(blob))
-    with pytest.raises(FheError, match="message_modulus"):
+    with pytest.raises(FheError, match="glwe_noise_log2"):
         altered.decompress()
+    # a message space other than the radix layer's 4 x 4: the reader itself refuses it, by name
+    blob = bytearray(r.serialize())
+    struct.pack_into("<I", blob, 32 + 6 * 4, 2)  # message_modulus 4 -> 2
+    with pytest.raises(FheError, match="message_modulus"):
+        CompressedFheUint.deserialize(_refnv(blob))
     assert r.decompress().decrypt(env) == 7  # the context is as usable as before
 
 
